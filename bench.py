@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- Mreads/s of minicom's sketch + index + overlap hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--genome uniform|repeats]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--genome uniform|repeats] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 One step = one full pass of the hot path (the reference's timed region, Stage 1 + Stage 2, preprocess.c:137-234) over one
 batch of synthetic reads that are already resident in HBM.  The step ends with the result digest read back
-(mcomh_result_digest), which every timed step must share with an untimed run whose result was CHECKED (minicom_amd/check.py:
-every read in exactly one place, every member on and like its contig).
+(mcomh_result_digest), which every timed step must share; with --full also with an untimed run whose result was CHECKED
+(minicom_amd/check.py: every read in exactly one place, every member on and like its contig).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, per-step counters, kernel-class times of the
+timed steps).  --full adds what takes runs or work of its own: the checked run, the event and Stage-2 join A/B, the host-to-host
+and file -> stream files figures, the strong-scaling figure (N > 1), the sequential oracle's digest verdict and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (dump_outputs below).
 
 Workload.  N = 1: BASELINE.json configs[1], 100 M x 150 bp, k = 31, default parameters.  N > 1: configs[3]'s shape, ONE job of
 62.5 M x N reads (500 M at N = 8) sharded over the GPUs -- reads per GPU fixed, "scaling": "weak" -- and, beside it,
@@ -54,7 +59,8 @@ def cpu_baseline(L, sample):
                 out = os.path.join(td, "out"); os.makedirs(out)
                 cwd = os.path.join(td, "cwd"); os.makedirs(os.path.join(cwd, "output_ref"))
                 t0 = time.perf_counter()
-                p = subprocess.run([exe, fq, out], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+                # paths relative to cwd: the reference builds its file names in char[100] buffers
+                p = subprocess.run([exe, os.path.relpath(fq, cwd), os.path.relpath(out, cwd)], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
                 wall = time.perf_counter() - t0
                 t = [float(x) for x in re.findall(r"\[Stage \d\] Real time: ([\d.]+)", p.stdout.decode())]
                 if p.returncode == 0 and len(t) == 2:
@@ -187,6 +193,57 @@ def oracle_digest_verdict(n, L, seed, genome, digest):
     return {"equal": None, "note": "the oracle has not been run on this read set (tests/golden/scale_digests.json)"}
 
 
+DUMP_CHARS = 4_000_000          # contig characters of the sampled contigs (float32: 16 MB)
+DUMP_MEMBERS = 1_000_000        # members of the sampled contigs (read id, offset, direction: 20 MB)
+DUMP_CONTIGS = 65_536
+DUMP_LIST = 65_536              # entries per id list (list, position, id in float64: 1.5 MB per list)
+DUMP_LIMIT = 64_000_000
+
+
+def dump_outputs(p, digest, out_dir):
+    """What a caller of the timed path receives from a step -- the contig set (consensus strings, member lists) and the id lists
+    of the reads that joined no contig -- written as out_dir/<name>.npy.  Every value is an integer below 2^53 and is stored
+    exactly in float64 (characters and direction bits in float32).  Beyond the sizes above, a fixed seeded sample: contigs in a
+    seeded random order until the character or member budget is spent, list entries at seeded random positions (the
+    positions are written beside them; the lists share one array, most of them are empty at the benchmark's workload).  An array
+    that would hold nothing is not written.  Same reads and same result: same files."""
+    import numpy as np
+    from minicom_amd.check import LIST_NAMES
+    ref, roff, mem, moff = p.contig_set()
+    nc = len(roff) - 1
+    clen, cmem = np.diff(roff).astype(np.int64), np.diff(moff).astype(np.int64)
+    order = np.random.default_rng(SEED).permutation(nc)[:DUMP_CONTIGS]
+    fits = (np.cumsum(clen[order]) <= DUMP_CHARS) & (np.cumsum(cmem[order]) <= DUMP_MEMBERS)
+    pick = np.sort(order[:int(np.argmin(fits)) if not fits.all() else len(order)])
+    chars = np.concatenate([ref[roff[i]:roff[i + 1]] for i in pick]) if len(pick) else np.zeros(0, np.uint8)
+    words = np.concatenate([mem[moff[i]:moff[i + 1]] for i in pick]) if len(pick) else np.zeros(0, np.uint64)
+    d = np.array(digest, dtype=np.uint64)
+    out = {"digest": np.stack([d >> np.uint64(32), d & np.uint64(0xFFFFFFFF)], 1).astype(np.float64),      # [8, 2]: high, low 32 bits
+           "counts": np.array([nc, len(ref), len(mem)], dtype=np.float64),                                    # contigs, characters, members
+           "contig_id": pick.astype(np.float64),
+           "contig_length": clen[pick].astype(np.float64),
+           "contig_member_count": cmem[pick].astype(np.float64),
+           "contig_chars": chars.astype(np.float32),
+           "member_read_id": (words >> np.uint64(32)).astype(np.float64),
+           "member_offset": ((words & np.uint64(0xFFFFFFFF)) >> np.uint64(1)).astype(np.float64),
+           "member_reverse": (words & np.uint64(1)).astype(np.float32)}
+    lengths, rows = [], []
+    for i, name in enumerate(LIST_NAMES):
+        ids = p.id_list(name)
+        pos = np.arange(len(ids)) if len(ids) <= DUMP_LIST else np.sort(np.random.default_rng(SEED + 1 + i).choice(len(ids), DUMP_LIST, replace=False))
+        lengths.append(len(ids))
+        rows.append(np.stack([np.full(len(pos), i), pos, ids[pos]], 1).astype(np.float64))
+    out["list_lengths"] = np.array(lengths, dtype=np.float64)                                                # in LIST_NAMES order
+    out["list_sample"] = np.concatenate(rows)                                                                # [m, 3]: list, position, read id
+    out = {name: v for name, v in out.items() if v.size}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT, f"outputs of {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {"dir": out_dir, "files": len(out), "bytes": int(total), "contigs_sampled": int(len(pick)), "members_sampled": int(len(words))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -196,15 +253,19 @@ def main():
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--genome", choices=("uniform", "repeats"), default="uniform", help="repeats: the repeat-rich device genome (forty-copy segments, tandem repeats, poly-A, (AT)n)")
     ap.add_argument("--host-threads", type=int, default=0)
-    ap.add_argument("--cpu-sample", type=int, default=4_000_000)
-    ap.add_argument("--e2e-reads", type=int, default=20_000_000, help="reads of the file -> stream files measurement (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB)")
+    ap.add_argument("--full", action="store_true", help="also the checks and figures beyond the headline (see the --no-* options); off: headline only")
+    ap.add_argument("--cpu-sample", type=int, default=4_000_000, help="--full: reads of the CPU baseline")
+    ap.add_argument("--e2e-reads", type=int, default=20_000_000, help="--full: reads of the file -> stream files measurement (0 = skip)")
     ap.add_argument("--force-exchange", action="store_true", help="run the distributed pipeline (one-rank RCCL communicator) even with one GPU (testing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the checked run (the digest comparison between steps stays)")
-    ap.add_argument("--no-host-to-host", action="store_true")
-    ap.add_argument("--no-event-ab", action="store_true", help="skip the K extra steps without profiler events (the A/B of what the events cost)")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling 100 M-read figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the checked run (the digest comparison between steps stays)")
+    ap.add_argument("--no-host-to-host", action="store_true", help="--full: skip the host-to-host figure")
+    ap.add_argument("--no-event-ab", action="store_true", help="--full: skip the K extra steps without profiler events (the A/B of what the events cost)")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the strong-scaling 100 M-read figure")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -263,8 +324,9 @@ def main():
              "ra_singletons", "cix_slots", "cix_entries", "sketch_records", "x_records", "x_cindex_entries", "contigs_bucket", "contigs_combine",
              "t_x_reads", "t_x_records", "t_x_contigs", "t_x_sketch", "t_x_index", "t_x_pairs", "t_x_merged", "t_x_cindex", "store_grows", "store_contigs", "store_chars", "join_passes", "join_fallbacks", "join_deferred", "ra_passing")
 
-    def measure(n_total, seed, steps, warmup, check, ab_events=False):
-        """K timed steps of one job of n_total reads; returns (seconds, aggregate stats, digests, reads, make)."""
+    def measure(n_total, seed, steps, warmup, check, ab_events=False, dump=None):
+        """K timed steps of one job of n_total reads; returns (seconds, aggregate stats, digests, reads, make).  dump: a directory for
+        what the last timed step computed (its pipeline is closed after the timed region instead of inside it)."""
         n_local = n_total // world
         n_total = n_local * world
         # synthetic input, resident in HBM before any timed region: this rank's shard of one n_total-read set.  (The ranks agree that
@@ -285,7 +347,7 @@ def main():
             return DistPipeline(reads, rank * n_local, n_total, comm, L=L, device=local_rank, host_threads=threads)
         agg, digests, observed = {}, [], {}
 
-        def step(timed, events=True):
+        def step(timed, events=True, keep=False):
             p = make()
             # HIP events around the hot kernel classes, on the launch stream, inside the timed steps (the contract's live kernel times):
             # about a hundred event pairs per step out of a process-wide pool; what they cost is measured below (`event_overhead`)
@@ -307,20 +369,27 @@ def main():
                 o = observed.setdefault("*", {})
                 for kn, c in p.prof_kernels("*").items():
                     o[kn] = o.get(kn, 0) + c
+            if keep:
+                return p
             p.close()
             return dg
         for _ in range(warmup):
             step(False)
         barrier()
+        last = None
         t0 = time.perf_counter()
-        for _ in range(steps):
-            step(True)
+        for i in range(steps):
+            last = step(True, keep=dump is not None and i == steps - 1)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if dump is not None:
+            if rank == 0:
+                agg["_dump"] = dump_outputs(last, digests[-1], dump)
+            last.close()
         # A/B of the event profiler: the same K steps again with the events off (untimed for `value`; reported beside it)
         agg["_events_off_s"] = None
         if ab_events:
@@ -379,7 +448,8 @@ def main():
     try:
         ok, err = True, None
         try:
-            dt, agg, ref_digest, checked, reads, n_total, n_local = measure(n_job, seed, a.steps, a.warmup, not a.no_check, ab_events=not a.no_event_ab and world == 1)
+            dt, agg, ref_digest, checked, reads, n_total, n_local = measure(n_job, seed, a.steps, a.warmup, a.full and not a.no_check,
+                                                                            ab_events=a.full and not a.no_event_ab and world == 1, dump=a.dump_outputs)
         except (McomError, RuntimeError) as e:                                  # e.g. out of memory at a size no single card could rehearse
             ok, err = False, f"{type(e).__name__}: {e}"
         if not agree(ok):
@@ -388,13 +458,13 @@ def main():
             fell_back = f"the {n_job // 1_000_000} M-read job failed on some rank ({err}); this line is the 100 M-read job sharded over the GPUs instead"
             pool_trim(); torch.cuda.empty_cache()
             weak, n_job, seed = False, 100_000_000, SEED
-            dt, agg, ref_digest, checked, reads, n_total, n_local = measure(n_job, seed, a.steps, a.warmup, not a.no_check)
+            dt, agg, ref_digest, checked, reads, n_total, n_local = measure(n_job, seed, a.steps, a.warmup, a.full and not a.no_check, dump=a.dump_outputs)
     finally:
         pass
 
     # ---- N > 1: the strong-scaling figure beside the weak one -- configs[1]'s 100 M-read job over the same GPUs
     strong = None
-    if world > 1 and weak and not a.no_strong:
+    if a.full and world > 1 and weak and not a.no_strong:
         del reads
         pool_trim(); torch.cuda.empty_cache()
         try:
@@ -409,7 +479,7 @@ def main():
     # ---- host to host (one GPU): reads in page-locked host memory, uploaded in chunks beside classify / pack / sketch, and the
     # whole result copied back, all inside the timed region -- what a caller pays who hands over host buffers (never `value`)
     h2h = None
-    if world == 1 and not distributed and not a.no_host_to_host and rank == 0 and a.genome == "uniform":
+    if a.full and world == 1 and not distributed and not a.no_host_to_host and rank == 0 and a.genome == "uniform":
         try:
             import psutil
             need = n_local * L
@@ -446,7 +516,7 @@ def main():
 
     # ---- file -> stream files (one GPU): what the `minicom` command's user waits for, before the external entropy coder
     e2e, e2e_modes = None, {}
-    if world == 1 and not distributed and rank == 0 and a.e2e_reads > 0 and a.genome == "uniform":
+    if a.full and world == 1 and not distributed and rank == 0 and a.e2e_reads > 0 and a.genome == "uniform":
         reads = None
         pool_trim(); torch.cuda.empty_cache()
         try:
@@ -613,29 +683,35 @@ def main():
                                                                                   "sort_overflow_segments", "x_records", "x_cindex_entries", "store_grows", "store_contigs", "store_chars", "join_passes", "join_fallbacks", "join_deferred")},
                        "stage_ms_rank0": {q: round(agg.get(q, 0.0) / ppp, 1) for q in ("t_reads", "t_bucket", "t_combine", "t_realign", "t_gpu", "t_x_reads", "t_x_records",
                                                                                         "t_x_contigs", "t_x_sketch", "t_x_index", "t_x_pairs", "t_x_merged", "t_x_cindex")},
-                       "kernel_timing": "HIP events around the hot kernel classes on the launch stream, inside the timed steps (pooled events, ~100 pairs per step; cost: event_overhead)",
+                       "kernel_timing": "HIP events around the hot kernel classes on the launch stream, inside the timed steps (pooled events, ~100 pairs per step; cost: event_overhead, --full)",
                        "results": "contig set (strings + member lists) complete in HBM at the end of a step, its digest read back inside the step; host copy on demand"},
             "result": {"digest": [str(v) for v in ref_digest], "digest_fields": "contigs, chars, members, unclustered, strings, member words, offsets, lists",
-                       "every_timed_step_equal": True, "checked_run": checked, "sequential_oracle": oracle_digest_verdict(n_total, L, seed, a.genome, ref_digest)},
-            "value_host_to_host": h2h,
-            "value_file_to_streams": e2e,
-            "value_file_to_streams_order_preserving": e2e_modes.get("order"),
-            "value_file_to_streams_paired_end": e2e_modes.get("paired"),
-            "value_file_to_streams_gz": e2e_modes.get("gz"),
-            "value_file_to_streams_gz_one_member": e2e_modes.get("gz_one"),
-            "stage2_join_ab": join_ab,
-            "value_strong_100m": strong,
+                       "every_timed_step_equal": True},
             "whole_step": whole,
-            "event_overhead": ev_ab,
             "roofline": roof,
         }
+        if a.dump_outputs is not None:
+            res["outputs"] = agg["_dump"]
         if comm is not None:
             sent, calls = comm.stats()
             res["config"]["rccl_bytes_sent_rank0_total"] = int(sent)
-        if not a.no_cpu_baseline and world == 1:
-            res["cpu_baseline"] = cpu_baseline(L, a.cpu_sample)
-        elif not a.no_cpu_baseline:
-            res["cpu_baseline"] = None
+        if a.full:
+            res["result"].update({"checked_run": checked, "sequential_oracle": oracle_digest_verdict(n_total, L, seed, a.genome, ref_digest)})
+            res.update({
+                "value_host_to_host": h2h,
+                "value_file_to_streams": e2e,
+                "value_file_to_streams_order_preserving": e2e_modes.get("order"),
+                "value_file_to_streams_paired_end": e2e_modes.get("paired"),
+                "value_file_to_streams_gz": e2e_modes.get("gz"),
+                "value_file_to_streams_gz_one_member": e2e_modes.get("gz_one"),
+                "stage2_join_ab": join_ab,
+                "value_strong_100m": strong,
+                "event_overhead": ev_ab,
+            })
+            if not a.no_cpu_baseline and world == 1:
+                res["cpu_baseline"] = cpu_baseline(L, a.cpu_sample)
+            elif not a.no_cpu_baseline:
+                res["cpu_baseline"] = None
         print(json.dumps(res), flush=True)
     if comm is not None:
         comm.close()

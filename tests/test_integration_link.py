@@ -29,7 +29,8 @@ def test_reference_main_linked_against_the_library_writes_the_reference_streams(
     synth.write_fastq(fq, reads)
     out = tmp_path / "out"; out.mkdir()
     cwd = tmp_path / "cwd"; (cwd / "output_ref").mkdir(parents=True)
-    r = subprocess.run([exe, fq, str(out)], cwd=str(cwd), capture_output=True, text=True, timeout=600)
+    # paths relative to the working directory: the reference builds its file names in char[100] buffers (kthread_dump.c:244)
+    r = subprocess.run([exe, "../in.fastq", "../out"], cwd=str(cwd), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "[Stage 1]" in r.stdout and "[Stage 2]" in r.stdout                  # the reference's own pre_process ran the stages
     with gzip.open(os.path.join(golden_dir, "streams_" + tag + ".tar.gz"), "rb") as g:

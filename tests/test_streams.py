@@ -315,7 +315,8 @@ def test_one_stream_set_per_thread_as_the_reference_writes_them(tmp_path, mode):
     if not os.path.exists(exe):
         pytest.skip("oracle/_ref is not built here")
     r1, r2 = tmp_path / "r1.txt", tmp_path / "r2.txt"
-    subprocess.run([exe, str(five), str(r1), "true" if mode == "paired" else "false", "true" if mode == "order" else "false", "4", str(r2)], check=True, cwd=str(tmp_path),
+    # paths relative to the working directory: the reference builds its file names in char[100] buffers (decompress.c:111)
+    subprocess.run([exe, five.name, r1.name, "true" if mode == "paired" else "false", "true" if mode == "order" else "false", "4", r2.name], check=True, cwd=str(tmp_path),
                    stdout=subprocess.DEVNULL)
     if mode == "order":
         check(r1.read_bytes().split(b"\n")[:-1])

@@ -243,7 +243,8 @@ def _reference_on_prefix(fq, td, n, L, ref_reads):
     cwd = os.path.join(td, "ref_cwd"); os.makedirs(os.path.join(cwd, "output_ref"))
     t = time.perf_counter()
     try:
-        pr = subprocess.run([exe, pre, out], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+        # paths relative to cwd: the reference builds its file names in char[100] buffers
+        pr = subprocess.run([exe, os.path.relpath(pre, cwd), os.path.relpath(out, cwd)], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     except subprocess.TimeoutExpired:
         return {"value": None, "note": f"the reference did not finish {m} reads in 900 s"}
     dt = time.perf_counter() - t

@@ -18,10 +18,12 @@ for r in csv.DictReader(open('gpurun_out/cx1_top.csv')):
     if n.startswith('k_cx'):
         print('%-28s calls %3s avg %9.1f us' % (n[:28], r['total_calls'], float(r['average'])))
 PY
-python3 bench.py --steps 3 --no-cpu-baseline --no-host-to-host --e2e-reads 0 --no-event-ab > gpurun_out/bench_short.json 2> gpurun_out/bench_short.err || { tail -5 gpurun_out/bench_short.err; exit 1; }
-python3 - <<'PY'
+ERR=$(mktemp); trap 'rm -f "$ERR"' EXIT
+LINE=$(python3 bench.py --full --steps 3 --no-cpu-baseline --no-host-to-host --e2e-reads 0 --no-event-ab 2> "$ERR") || { tail -5 "$ERR"; exit 1; }
+LINE="$LINE" python3 - <<'PY'
 import json
-d = json.loads(open('gpurun_out/bench_short.json').read().strip().splitlines()[-1])
+import os
+d = json.loads(os.environ['LINE'].strip().splitlines()[-1])
 print(d['value'], 'Mreads/s', d['ms_per_step'], 'ms', d['config']['stage_ms_rank0'])
 print(d['roofline']['device_ms_per_step_by_kernel'], 'launches', d['whole_step'])
 PY

@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 O=gpurun_out/prof_$TAG
 rm -rf "$O"; mkdir -p "$O"
 python3 tools/source_sha.py > "$O/source_sha.json"
-PROFILED="--steps 2 --warmup 1 --no-event-ab --no-cpu-baseline --no-host-to-host --e2e-reads 0"
+PROFILED="--full --steps 2 --warmup 1 --no-event-ab --no-cpu-baseline --no-host-to-host --e2e-reads 0"
 COUNTED="--steps 1 --warmup 0 --no-event-ab --no-cpu-baseline --no-host-to-host --no-check --e2e-reads 0"
 echo "[1/6] kernel trace + stats: bench.py $PROFILED"
 rocprofv3 --kernel-trace --stats -d "$O/kt" -o kt -- python3 bench.py $PROFILED > "$O/line_profiled.json" 2> "$O/kt.err"
@@ -33,8 +33,8 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_V
 echo "[5/6] SQ pass B (instruction mix)"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU SQ_INSTS_VALU_INT64 SQ_LDS_BANK_CONFLICT \
     --output-format csv -d "$O/sqb" -o s -- python3 bench.py $COUNTED --reads "$SQ_READS" > "$O/sqb.out" 2> "$O/sqb.err"
-echo "[6/6] the unprofiled line: python3 bench.py (defaults)"
-python3 bench.py > "$O/line_default.json" 2> "$O/default.err"
+echo "[6/6] the unprofiled line: python3 bench.py --full (defaults otherwise)"
+python3 bench.py --full > "$O/line_default.json" 2> "$O/default.err"
 # keep what travels back small: the counter CSVs only
 find "$O" -name '*kernel_trace.csv' -delete
 find "$O" -name "*agent_info.csv" -delete
