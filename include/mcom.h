@@ -641,6 +641,60 @@ int mcom_offsets_rebase(mcom_ctx *ctx, uint64_t *d_off, size_t n, uint64_t delta
  * aligned.  Synchronous.                                                                                            */
 int mcom_digest(mcom_ctx *ctx, const void *d_data, size_t bytes, uint64_t *h_sum_xor);
 
+/* ---- decoder: stream files back into reads (csrc/decode.hip, the inverse of mcom_streams_*) ----------------------
+ * The archive is untrusted input.  Every call that reads file bytes as indices takes d_flag, one zeroed 32-bit word of
+ * device memory: a violation sets a bit of it and the access is skipped; the caller reads the word back and refuses the
+ * archive when it is not zero.                                                                                       */
+enum mcom_decode_flag {
+	MCOM_DECODE_F_BOUNDS = 1,   /* an index derived from the files leaves the buffer it indexes                         */
+	MCOM_DECODE_F_LINE = 2,     /* a line of a text stream that decode_line refuses (bad character, run or length)      */
+	MCOM_DECODE_F_DUP = 4,      /* two reads for one output row                                                        */
+	MCOM_DECODE_F_DEST = 8      /* an output row outside the table (id >= n_seq, mate row >= half, too many reads)     */
+};
+/* The chain of contig headers of a beg_pos.bin image in HOST memory (per contig: uint32 num, then num uint16 deltas):
+ * h_moff[c] = members before contig c, h_moff[*n_contigs] = *n_members.  h_moff NULL: only the two counts.  Trailing bytes
+ * short of a header are ignored as the host decoder does; MCOM_E_ARG when a contig's deltas leave the file.  Plain host code. */
+int mcom_decode_walk_headers(const uint8_t *h_bpos, uint64_t bytes, uint64_t *h_moff, uint64_t cap_contigs, uint64_t *n_contigs, uint64_t *n_members);
+/* Line index of a text stream: *h_n_lines = number of '\n'; d_line_start (optional, cap_lines + 1 entries) gets
+ * d_line_start[m] = offset behind the m-th newline, d_line_start[0] = 0, so line m is [start[m], start[m + 1] - 1).  Bytes
+ * behind the last newline belong to no line.  Synchronous.                                                            */
+int mcom_decode_line_index(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint64_t *d_line_start, uint64_t cap_lines,
+                           uint64_t *h_n_lines, uint32_t *d_flag);
+/* Member table of one stream set: d_cid[q] = contig of member q, d_pos[q] = its begin position (sum of the deltas inside
+ * the contig), d_coff[c] = bases of ref.bin before contig c (a contig is last position + L bases long; the 2-bit stream
+ * runs on across contigs), d_coff[n_contigs] = *h_ref_bases.  d_moff: mcom_decode_walk_headers' table, on the device.
+ * Synchronous.                                                                                                        */
+int mcom_decode_member_table(mcom_ctx *ctx, const uint8_t *d_bpos, uint64_t bpos_bytes, const uint64_t *d_moff, uint64_t n_contigs, uint64_t n_members,
+                             int L, uint32_t *d_cid, uint32_t *d_pos, uint64_t *d_coff, uint64_t *h_ref_bases, uint32_t *d_flag);
+/* -p: ids of a list = running sum of its uint32 deltas (64 bit, not wrapped)                                           */
+int mcom_decode_list_ids(mcom_ctx *ctx, const uint32_t *d_delta, uint64_t n, uint64_t *d_dest);
+/* -p: ids of the members of a set from ids.bin: absolute for the first member of a contig and where the begin position
+ * changes, else a difference to the member before (32 bit, wrapped)                                                   */
+int mcom_decode_member_ids(mcom_ctx *ctx, const uint32_t *d_ids, uint64_t n_members, const uint64_t *d_moff, const uint32_t *d_cid, const uint32_t *d_pos,
+                           uint64_t *d_dest);
+/* Paired end: rows of the n reads whose file bits are bits bit0 .. bit0 + n - 1 of d_fbits (missing bytes read as zero).
+ * A zero bit: row zero_base + (zero bits before it); a one bit: row half + d_peids[one bits before it].  A row that
+ * would leave its half is ~0 and flagged.  *h_ones = number of one bits.  Synchronous.                                */
+int mcom_decode_pe_dest(mcom_ctx *ctx, const uint8_t *d_fbits, uint64_t fb_bytes, uint64_t bit0, uint64_t n, const uint32_t *d_peids, uint64_t n_peids,
+                        uint64_t zero_base, uint64_t half, uint64_t *d_dest, uint64_t *h_ones, uint32_t *d_flag);
+/* The first n lines of a text stream against the host decoder's acceptance (letters and decimal runs, at most L bases;
+ * verbatim: exactly L bytes): MCOM_DECODE_F_LINE when one fails.  Run before mcom_decode_reads.                       */
+int mcom_decode_check_lines(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_line_start, uint64_t n, int L, int verbatim,
+                            uint32_t *d_flag);
+/* What n reads are decoded from.  Read m = window of the reference (d_ref 2 bits per base: bases [d_coff[d_cid[m]] + d_pos[m], + L),
+ * or [m L, m L + L) when d_cid is NULL; d_ref NULL: L times the character ref_const) with line m of d_text laid over it (NULL: none;
+ * verbatim: the line is the read), reverse-complemented when bit m of d_dir is set (NULL or short: not).                          */
+typedef struct {
+	const uint8_t *d_text; uint64_t text_bytes; const uint64_t *d_line_start; int verbatim;
+	const uint8_t *d_ref; uint64_t ref_bytes; int ref_const;
+	const uint32_t *d_cid; const uint32_t *d_pos; const uint64_t *d_coff; uint64_t n_contigs;
+	const uint8_t *d_dir; uint64_t dir_bytes;
+} mcom_decode_src;
+/* Read m goes to row d_dest[m] (NULL: dest0 + m) of d_out, n_rows rows of L characters and a newline.  d_seen (optional): one bit
+ * per row, zeroed by the caller; a row written twice is flagged.  Asynchronous.                                                  */
+int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
+                      uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag);
+
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,
                      uint64_t first, uint64_t count, uint8_t *d_ascii, size_t pitch);

@@ -125,6 +125,16 @@ int mcomh_decompress_order(const char *folder, const char *out_path, uint64_t *n
  * file's reads to out_path1 and every mate to the same line of out_path2.                                          */
 int mcomh_cluster_dump_pe(mcomh_pipeline *p, const char *folder);
 int mcomh_decompress_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs);
+/* The three decoders with the reads rebuilt on GPU `device` (host/mcom_decompress_gpu.cpp over csrc/decode.hip): the same files in,
+ * byte-identical output files; the same archives accepted and refused.  -1 and no output file when the archive is refused, when
+ * there is no such GPU (no fall back to the host decoders above: they are calls of their own) or when the rows, n x (L + 1) bytes
+ * beside the stream files, do not fit the card.                                                                                  */
+int mcomh_decompress_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device);
+int mcomh_decompress_order_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device);
+int mcomh_decompress_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device);
+/* Where the last of those calls spent its time, in ms: [0] reading the files, [1] upload + indices + destinations, [2] decode (wall),
+ * [3] decode kernels (device events), [4] download + write, [5] of that inside fwrite, [6] the whole call, [7] unused.              */
+void mcomh_decompress_gpu_times(double *ms8);
 /* both files of a pair into one device matrix, second file behind the first; MCOM_E_ARG when the counts differ      */
 int mcomh_fastq_pair_to_device(const char *path1, const char *path2, int device, int *L, size_t chunk_reads, uint8_t **d_reads, size_t *n,
                                char *err, size_t err_cap);

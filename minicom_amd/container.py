@@ -188,9 +188,10 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.close()
 
 
-def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8) -> int:
+def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None) -> int:
     """`.minicom` -> reads, one per line: the original order for an archive written with -p, two files (line i of both a
-    pair) for a paired-end archive.  Host only.  Returns the number of reads (pairs for paired end)."""
+    pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
+    integer: the entropy stage on the host, the reads rebuilt on that GPU (pipeline.decompress(..., device=))."""
     import tempfile
     from .pipeline import decompress, decompress_pe
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
@@ -198,5 +199,5 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
         if kinds["paired"]:
             if out_path2 is None:
                 raise ValueError("a paired-end archive decodes into two files")
-            return decompress_pe(td, out_path, out_path2)
-        return decompress(td, out_path, order=kinds["order"])
+            return decompress_pe(td, out_path, out_path2, device=device)
+        return decompress(td, out_path, order=kinds["order"], device=device)

@@ -15,6 +15,17 @@ class McomError(RuntimeError):
     pass
 
 
+class DecodeSrc(C.Structure):
+    """mcom_decode_src of include/mcom.h"""
+    _fields_ = [("d_text", C.c_void_p), ("text_bytes", C.c_uint64), ("d_line_start", C.c_void_p), ("verbatim", C.c_int),
+                ("d_ref", C.c_void_p), ("ref_bytes", C.c_uint64), ("ref_const", C.c_int),
+                ("d_cid", C.c_void_p), ("d_pos", C.c_void_p), ("d_coff", C.c_void_p), ("n_contigs", C.c_uint64),
+                ("d_dir", C.c_void_p), ("dir_bytes", C.c_uint64)]
+
+
+DECODE_F_BOUNDS, DECODE_F_LINE, DECODE_F_DUP, DECODE_F_DEST = 1, 2, 4, 8
+
+
 def lib_path() -> str:
     return os.path.join(HERE, "lib", "libmcom_hip.so")
 
@@ -126,6 +137,15 @@ def load_library():
     L.mcom_records_carry.restype = i32; L.mcom_records_carry.argtypes = [vp, vp, vp, vp, sz, u32, u32, vp, sz, vp, C.POINTER(u64)]
     L.mcom_claim_pairs.restype = i32
     L.mcom_claim_pairs.argtypes = [vp, vp, sz, sz, i32, vp, vp, C.POINTER(u64), C.POINTER(i32)]
+    # decoder (csrc/decode.hip)
+    L.mcom_decode_walk_headers.restype = i32; L.mcom_decode_walk_headers.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_decode_line_index.restype = i32; L.mcom_decode_line_index.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), vp]
+    L.mcom_decode_member_table.restype = i32; L.mcom_decode_member_table.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, vp, vp, C.POINTER(u64), vp]
+    L.mcom_decode_list_ids.restype = i32; L.mcom_decode_list_ids.argtypes = [vp, vp, u64, vp]
+    L.mcom_decode_member_ids.restype = i32; L.mcom_decode_member_ids.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+    L.mcom_decode_pe_dest.restype = i32; L.mcom_decode_pe_dest.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, u64, vp, C.POINTER(u64), vp]
+    L.mcom_decode_check_lines.restype = i32; L.mcom_decode_check_lines.argtypes = [vp, vp, u64, vp, u64, i32, i32, vp]
+    L.mcom_decode_reads.restype = i32; L.mcom_decode_reads.argtypes = [vp, C.POINTER(DecodeSrc), u64, i32, vp, u64, vp, u64, vp, vp]
     L.mcom_synth_reads.restype = i32
     L.mcom_synth_reads.argtypes = [vp, u64, u64, i32, i32, C.c_double, u64, u64, vp, sz]
     L.mcom_synth_reads_genome.restype = i32
@@ -757,6 +777,107 @@ class Context:
         out = torch.empty((count, pitch), dtype=torch.uint8, device=self.device)
         self._check(self.lib.mcom_synth_reads_genome(self._h, seed, n_reads, L, coverage, sub_rate, {"uniform": 0, "repeats": 1}[genome], first, count, self._p(out), pitch))
         return out
+
+    # ---- decoder (csrc/decode.hip).  uint64 / uint32 arrays travel as int64 / int32 tensors, bytes as uint8 -------------------
+    def _dflag(self):
+        torch = _torch()
+        return torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def decode_walk_headers(self, bpos: np.ndarray):
+        """mcom_decode_walk_headers on a host uint8 array.  Returns moff (uint64 [n_contigs + 1]); McomError when the chain leaves the file."""
+        b = np.ascontiguousarray(bpos, dtype=np.uint8)
+        nc, nm = C.c_uint64(), C.c_uint64()
+        if self.lib.mcom_decode_walk_headers(b.ctypes.data, b.size, None, 0, C.byref(nc), C.byref(nm)):
+            raise McomError("beg_pos.bin: a contig's deltas leave the file")
+        moff = np.zeros(nc.value + 1, dtype=np.uint64)
+        if self.lib.mcom_decode_walk_headers(b.ctypes.data, b.size, moff.ctypes.data, nc.value, C.byref(nc), C.byref(nm)):
+            raise McomError("beg_pos.bin: a contig's deltas leave the file")
+        return moff
+
+    def decode_line_index(self, text):
+        """mcom_decode_line_index.  text: uint8 device tensor.  Returns (line_start int64 [n_lines + 1], flag)."""
+        torch = _torch()
+        n = C.c_uint64()
+        flag = self._dflag()
+        nb = int(text.shape[0])
+        self._check(self.lib.mcom_decode_line_index(self._h, self._p(text, torch.uint8) if nb else None, nb, None, 0, C.byref(n), self._p(flag)))
+        start = torch.empty(n.value + 1, dtype=torch.int64, device=self.device)
+        self._check(self.lib.mcom_decode_line_index(self._h, self._p(text, torch.uint8) if nb else None, nb, self._p(start), n.value, C.byref(n), self._p(flag)))
+        self.sync()
+        return start, int(flag.item())
+
+    def decode_member_table(self, bpos, moff, L: int):
+        """mcom_decode_member_table.  bpos: uint8 device tensor, moff: int64 device tensor [n_contigs + 1] (decode_walk_headers).
+        Returns (cid int32 [n], pos int32 [n], coff int64 [n_contigs + 1], ref_bases, flag)."""
+        torch = _torch()
+        nc = int(moff.shape[0]) - 1
+        nm = int(moff[-1].item())
+        cid = torch.zeros(max(nm, 1), dtype=torch.int32, device=self.device)
+        pos = torch.zeros(max(nm, 1), dtype=torch.int32, device=self.device)
+        coff = torch.zeros(nc + 1, dtype=torch.int64, device=self.device)
+        rb = C.c_uint64()
+        flag = self._dflag()
+        self._check(self.lib.mcom_decode_member_table(self._h, self._p(bpos, torch.uint8) if bpos.numel() else None, int(bpos.shape[0]), self._p(moff, torch.int64), nc, nm, L,
+                                                      self._p(cid), self._p(pos), self._p(coff), C.byref(rb), self._p(flag)))
+        return cid[:nm], pos[:nm], coff, int(rb.value), int(flag.item())
+
+    def decode_list_ids(self, delta):
+        torch = _torch()
+        n = int(delta.shape[0])
+        dest = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        self._check(self.lib.mcom_decode_list_ids(self._h, self._p(delta, torch.int32) if n else None, n, self._p(dest)))
+        self.sync()
+        return dest[:n]
+
+    def decode_member_ids(self, ids, moff, cid, pos):
+        torch = _torch()
+        n = int(ids.shape[0])
+        dest = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if n:
+            self._check(self.lib.mcom_decode_member_ids(self._h, self._p(ids, torch.int32), n, self._p(moff, torch.int64), self._p(cid.contiguous(), torch.int32),
+                                                        self._p(pos.contiguous(), torch.int32), self._p(dest)))
+        self.sync()
+        return dest[:n]
+
+    def decode_pe_dest(self, fbits, n: int, peids, zero_base: int, half: int, bit0: int = 0):
+        """mcom_decode_pe_dest.  Returns (dest int64 [n], ones, flag); a refused row is -1."""
+        torch = _torch()
+        dest = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        ones = C.c_uint64()
+        flag = self._dflag()
+        self._check(self.lib.mcom_decode_pe_dest(self._h, self._p(fbits, torch.uint8) if fbits.numel() else None, int(fbits.shape[0]), bit0, n,
+                                                 self._p(peids, torch.int32) if peids.numel() else None, int(peids.shape[0]), zero_base, half, self._p(dest), C.byref(ones), self._p(flag)))
+        return dest[:n], int(ones.value), int(flag.item())
+
+    def decode_reads(self, n: int, L: int, n_rows: int, text=None, line_start=None, verbatim=False, ref=None, ref_const="A", cid=None, pos=None, coff=None,
+                     dirbits=None, dest=None, dest0: int = 0, out=None, seen=None, check=True):
+        """mcom_decode_check_lines + mcom_decode_reads into `out` (uint8 [n_rows * (L + 1)], made when None).  Returns (out, flag)."""
+        torch = _torch()
+        if out is None:
+            out = torch.zeros(n_rows * (L + 1), dtype=torch.uint8, device=self.device)
+        flag = self._dflag()
+        src = DecodeSrc()
+        keep = []
+        def ptr(t, dt):
+            if t is None or t.numel() == 0:
+                return None
+            t = t.contiguous(); keep.append(t)
+            assert t.is_cuda and t.dtype == dt, (t.dtype, dt)
+            return t.data_ptr()
+        src.d_text = ptr(text, torch.uint8) if text is not None and line_start is not None else None
+        if text is not None and line_start is not None and src.d_text is None and n:       # an empty text with lines asked for: one byte nobody reads
+            text = torch.zeros(1, dtype=torch.uint8, device=self.device); keep.append(text); src.d_text = text.data_ptr(); src.text_bytes = 0
+        else:
+            src.text_bytes = int(text.shape[0]) if text is not None else 0
+        src.d_line_start = ptr(line_start, torch.int64); src.verbatim = int(verbatim)
+        src.d_ref = ptr(ref, torch.uint8); src.ref_bytes = int(ref.shape[0]) if ref is not None else 0; src.ref_const = ord(ref_const)
+        src.d_cid = ptr(cid, torch.int32); src.d_pos = ptr(pos, torch.int32); src.d_coff = ptr(coff, torch.int64); src.n_contigs = (int(coff.shape[0]) - 1) if coff is not None else 0
+        src.d_dir = ptr(dirbits, torch.uint8); src.dir_bytes = int(dirbits.shape[0]) if dirbits is not None else 0
+        if check and src.d_text:
+            self._check(self.lib.mcom_decode_check_lines(self._h, src.d_text, src.text_bytes, src.d_line_start, n, L, int(verbatim), self._p(flag)))
+        self._check(self.lib.mcom_decode_reads(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, self._p(out), n_rows, self._p(seen) if seen is not None else None, self._p(flag)))
+        self.sync()
+        return out, int(flag.item())
 
 
 class Index:

@@ -1,0 +1,368 @@
+// minicom_amd/host/mcom_decompress_gpu.cpp -- the three decoders of mcom_decompress.cpp with the reads rebuilt on the device.
+//
+// Same stream files in, byte-identical output files out; mcom_decompress.cpp stays the specification (what it accepts is accepted,
+// what it refuses is refused) and the cross-check.  The work is cut in two:
+//   A. every stream file is read and uploaded whole; line indices, member tables and destination rows are made by the scans of
+//      csrc/decode.hip; the counts they give (lines against members, id words, file bits, n_seq, half, bases of ref.bin) and the flag
+//      word the kernels raise are compared on the host.  An archive that fails here is refused before anything is decoded.
+//   B. one mcom_decode_reads per list / stream set writes its reads into a table of rows in HBM (L characters and a newline each:
+//      the file image); the table comes back through two page-locked buffers, the copy of piece i + 1 under the write of piece i.
+// The only serial step is the chain of contig headers in beg_pos.bin (mcom_decode_walk_headers: four bytes read per contig).
+// No output file is left behind by a refused archive; there is no fall back to the host decoder.
+#include "../../include/mcom_host.h"
+#include "../../include/mcom.h"
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cstdio>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+enum Mode { DEFAULT = 0, ORDER = 1, PE = 2 };
+const size_t PIECE_BYTES = (size_t)64 << 20;          // one page-locked buffer; two of them bound the host memory of the download
+
+double g_times[8];                                      // ms: read files | upload + indices + destinations | decode, wall | decode, device events |
+                                                        //     download + write, wall | of that inside fwrite | whole call | unused
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+bool slurp(const std::string &path, std::vector<uint8_t> &out)
+{
+	FILE *f = fopen(path.c_str(), "rb");
+	if (!f) return false;
+	fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
+	if (n < 0) { fclose(f); return false; }
+	out.resize((size_t)n);
+	size_t got = n ? fread(out.data(), 1, (size_t)n, f) : 0;
+	fclose(f);
+	return got == (size_t)n;
+}
+
+struct Refuse { const char *why; };                     // thrown inside run(), caught there: never crosses the C boundary
+
+// device memory and page-locked buffers of one call, released when it ends however it ends
+struct Arena {
+	std::vector<void*> dev, pinned;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	mcom_ctx *ctx = nullptr;
+	~Arena()
+	{
+		if (ctx) (void)mcom_sync(ctx);
+		for (void *p : dev) (void)hipFree(p);
+		for (void *p : pinned) (void)hipHostFree(p);
+		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+		if (ctx) mcom_destroy(ctx);
+	}
+	template <class T> T *alloc(size_t n)
+	{
+		void *p = nullptr;
+		if (hipMalloc(&p, (n ? n : 1) * sizeof(T) + 16) != hipSuccess) throw Refuse{"the card has no room for the stream files and the rows"};
+		dev.push_back(p);
+		return (T*)p;
+	}
+	template <class T> T *upload(const T *h, size_t n)
+	{
+		T *d = alloc<T>(n);
+		if (n && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) throw Refuse{"upload failed"};
+		return d;
+	}
+};
+
+// one run of reads that a single mcom_decode_reads call rebuilds
+struct Seg {
+	mcom_decode_src src;
+	uint64_t n = 0;
+	const uint64_t *d_dest = nullptr; uint64_t dest0 = 0;
+};
+
+void ok(mcom_ctx *ctx, int rc) { if (rc) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(ctx)); throw Refuse{"a device call failed"}; } }
+
+struct Text { const uint8_t *d = nullptr; uint64_t bytes = 0, lines = 0; const uint64_t *start = nullptr; };
+
+Text index_text(Arena &A, const std::vector<uint8_t> &h, uint32_t *d_flag)
+{
+	Text t;
+	t.bytes = h.size();
+	t.d = A.upload(h.data(), h.size());
+	ok(A.ctx, mcom_decode_line_index(A.ctx, t.d, t.bytes, nullptr, 0, &t.lines, d_flag));
+	uint64_t *st = A.alloc<uint64_t>(t.lines + 1);
+	uint64_t again = 0;
+	ok(A.ctx, mcom_decode_line_index(A.ctx, t.d, t.bytes, st, t.lines, &again, d_flag));
+	t.start = st;
+	return t;
+}
+
+uint32_t read_flag(Arena &A, const uint32_t *d_flag)
+{
+	uint32_t f = 0;
+	ok(A.ctx, mcom_sync(A.ctx));
+	if (hipMemcpy(&f, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"cannot read the flag word"};
+	return f;
+}
+
+int run(Mode mode, const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_out, int device)
+{
+	const double t_begin = now_ms();
+	memset(g_times, 0, sizeof(g_times));
+	const std::string dir(folder);
+	// ---- info.txt, as the host routes read it
+	int L = 0, nth = 0; long na = 0, nt = 0, nn = 0, half = 0; unsigned long n_seq = 0;
+	{
+		FILE *fi = fopen((dir + "/info.txt").c_str(), "r");
+		if (!fi) return -1;
+		int got, want;
+		if (mode == DEFAULT) { want = 5; got = fscanf(fi, "%d %d %ld %ld %ld", &L, &nth, &na, &nt, &nn); }
+		else if (mode == ORDER) { want = 6; got = fscanf(fi, "%d %d %ld %ld %ld %lu", &L, &nth, &na, &nt, &nn, &n_seq); }
+		else { want = 6; got = fscanf(fi, "%d %d %ld %ld %ld %ld", &L, &nth, &half, &na, &nt, &nn); }
+		fclose(fi);
+		if (got != want) return -1;
+	}
+	if (L < 1 || L > 256 || nth < 1 || nth > 4096 || na < 0 || nt < 0 || nn < 0 || half < 0) return -1;
+
+	// ---- the stream files, whole
+	double t0 = now_ms();
+	const char *list_txt[3] = {"AA.txt", "TT.txt", "NN.txt"};
+	const char *cnt_ids[3] = {"allA.ids.bin", "allT.ids.bin", "allN.ids.bin"}, *list_ids[3] = {"AA.ids.bin", "TT.ids.bin", "NN.ids.bin"};
+	std::vector<uint8_t> h_txt[3], h_cnt_ids[3], h_list_ids[3], h_nseq, h_nids, h_single, h_sids, h_fsp, h_psp;
+	struct SetFiles { std::vector<uint8_t> ref, pos, dir, dif, ids, fb, pe; };
+	std::vector<SetFiles> sets((size_t)nth);
+	for (int q = 0; q < 3; ++q) {
+		if (!slurp(dir + "/" + list_txt[q], h_txt[q])) return -1;
+		if (mode == ORDER && (!slurp(dir + "/" + cnt_ids[q], h_cnt_ids[q]) || !slurp(dir + "/" + list_ids[q], h_list_ids[q]))) return -1;
+	}
+	if (!slurp(dir + "/single_N.seq", h_nseq) || !slurp(dir + "/single.seq", h_single)) return -1;
+	if (mode == ORDER && (!slurp(dir + "/Nfile.ids.bin", h_nids) || !slurp(dir + "/singleFile.ids.bin", h_sids))) return -1;
+	if (mode == PE && (!slurp(dir + "/file.bin.sp", h_fsp) || !slurp(dir + "/peids.bin.sp", h_psp))) return -1;
+	for (int th = 0; th < nth; ++th) {
+		SetFiles &s = sets[(size_t)th];
+		const std::string sfx = "." + std::to_string(th);
+		if (!slurp(dir + "/ref.bin" + sfx, s.ref) || !slurp(dir + "/beg_pos.bin" + sfx, s.pos) || !slurp(dir + "/dir.bin" + sfx, s.dir) ||
+		    !slurp(dir + "/dif_char.txt" + sfx, s.dif)) return -1;
+		if (mode == ORDER && !slurp(dir + "/ids.bin" + sfx, s.ids)) return -1;
+		if (mode == PE && (!slurp(dir + "/file.bin" + sfx, s.fb) || !slurp(dir + "/peids.bin" + sfx, s.pe))) return -1;
+	}
+	g_times[0] = now_ms() - t0;
+	// the host routes' first size checks
+	if (mode == ORDER) {
+		size_t idb = h_nids.size() + h_sids.size();
+		for (int q = 0; q < 3; ++q) idb += h_cnt_ids[q].size() + h_list_ids[q].size();
+		for (const SetFiles &s : sets) idb += s.ids.size();
+		if ((size_t)n_seq > idb / 4) return -1;
+	}
+	if (mode == PE) {
+		size_t fbb = h_fsp.size();
+		for (const SetFiles &s : sets) fbb += s.fb.size();
+		if ((size_t)half > fbb * 8) return -1;
+	}
+	// the serial part: the chain of contig headers
+	std::vector<std::vector<uint64_t>> moff((size_t)nth);
+	std::vector<uint64_t> n_contigs((size_t)nth), n_members((size_t)nth);
+	for (int th = 0; th < nth; ++th) {
+		const SetFiles &s = sets[(size_t)th];
+		if (mcom_decode_walk_headers(s.pos.data(), s.pos.size(), nullptr, 0, &n_contigs[th], &n_members[th])) return -1;
+		moff[th].resize(n_contigs[th] + 1);
+		if (mcom_decode_walk_headers(s.pos.data(), s.pos.size(), moff[th].data(), n_contigs[th], &n_contigs[th], &n_members[th])) return -1;
+	}
+
+	// ---- the card
+	Arena A;
+	{
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
+			fprintf(stderr, "minicom gpu decoder: no GPU %d (%d visible); the host decoder is a call of its own\n", device, n_dev);
+			return -1;
+		}
+		if (mcom_create(&A.ctx, device, nullptr)) { fprintf(stderr, "minicom gpu decoder: cannot create a context on GPU %d\n", device); A.ctx = nullptr; return -1; }
+	}
+	try {
+		t0 = now_ms();
+		uint32_t *d_flag = A.alloc<uint32_t>(1);
+		if (hipMemset(d_flag, 0, 4) != hipSuccess) throw Refuse{"memset failed"};
+		std::vector<Seg> segs;
+		auto blank = [&]() { Seg s; memset(&s.src, 0, sizeof(s.src)); return s; };
+		const char bases[3] = {'A', 'T', 'N'};
+		const long counted[3] = {na, nt, nn};
+		// A.1 the lists: counted reads, near-constant reads, N reads, unclustered reads
+		for (int q = 0; q < 3; ++q) {
+			Seg s = blank(); s.src.ref_const = bases[q]; s.n = (uint64_t)counted[q];
+			if (mode == ORDER) {
+				if (h_cnt_ids[q].size() / 4 < s.n) throw Refuse{"fewer ids than counted reads"};
+				const uint32_t *d = A.upload((const uint32_t*)h_cnt_ids[q].data(), (size_t)s.n);
+				uint64_t *dest = A.alloc<uint64_t>(s.n);
+				ok(A.ctx, mcom_decode_list_ids(A.ctx, d, s.n, dest));
+				s.d_dest = dest;
+			}
+			segs.push_back(s);
+		}
+		auto text_seg = [&](const std::vector<uint8_t> &h, int ref_const, int verbatim, const std::vector<uint8_t> &h_ids) {
+			const Text t = index_text(A, h, d_flag);
+			Seg s = blank();
+			s.src.d_text = t.d; s.src.text_bytes = t.bytes; s.src.d_line_start = t.start; s.src.verbatim = verbatim; s.src.ref_const = ref_const;
+			s.n = t.lines;
+			ok(A.ctx, mcom_decode_check_lines(A.ctx, t.d, t.bytes, t.start, s.n, L, verbatim, d_flag));
+			if (mode == ORDER) {
+				if (h_ids.size() / 4 < s.n) throw Refuse{"fewer ids than lines"};
+				const uint32_t *d = A.upload((const uint32_t*)h_ids.data(), (size_t)s.n);
+				uint64_t *dest = A.alloc<uint64_t>(s.n);
+				ok(A.ctx, mcom_decode_list_ids(A.ctx, d, s.n, dest));
+				s.d_dest = dest;
+			}
+			segs.push_back(s);
+		};
+		for (int q = 0; q < 3; ++q) text_seg(h_txt[q], bases[q], 0, h_list_ids[q]);
+		auto single_seg = [&]() {
+			Seg s = blank();
+			s.n = (uint64_t)h_single.size() * 4 / (uint64_t)L;                 // whole reads only: the last byte may be padded
+			if (mode == ORDER && h_sids.size() / 4 < s.n) s.n = h_sids.size() / 4;  // (the host route stops, without an error, where the ids end)
+			s.src.d_ref = A.upload(h_single.data(), h_single.size()); s.src.ref_bytes = h_single.size();
+			if (mode == ORDER) {
+				const uint32_t *d = A.upload((const uint32_t*)h_sids.data(), (size_t)s.n);
+				uint64_t *dest = A.alloc<uint64_t>(s.n);
+				ok(A.ctx, mcom_decode_list_ids(A.ctx, d, s.n, dest));
+				s.d_dest = dest;
+			}
+			segs.push_back(s);
+		};
+		// the host routes take the N reads before the unclustered ones, except -p (ids of their own: the order does not show)
+		if (mode == ORDER) { single_seg(); text_seg(h_nseq, 'N', 1, h_nids); }
+		else { text_seg(h_nseq, 'N', 1, h_nids); single_seg(); }
+		const size_t n_list_segs = segs.size();
+		// A.2 the stream sets
+		for (int th = 0; th < nth; ++th) {
+			const SetFiles &f = sets[(size_t)th];
+			const uint64_t nm = n_members[th], nc = n_contigs[th];
+			Seg s = blank();
+			s.n = nm;
+			const Text t = index_text(A, f.dif, d_flag);
+			if (t.lines < nm) throw Refuse{"fewer dif_char lines than members"};
+			if (mode == ORDER && f.ids.size() / 4 < nm) throw Refuse{"fewer id words than members"};
+			const uint8_t *d_bpos = A.upload(f.pos.data(), f.pos.size());
+			const uint64_t *d_moff = A.upload(moff[th].data(), moff[th].size());
+			uint32_t *cid = A.alloc<uint32_t>(nm), *pos = A.alloc<uint32_t>(nm);
+			uint64_t *coff = A.alloc<uint64_t>(nc + 1);
+			uint64_t ref_bases = 0;
+			ok(A.ctx, mcom_decode_member_table(A.ctx, d_bpos, f.pos.size(), d_moff, nc, nm, L, cid, pos, coff, &ref_bases, d_flag));
+			if (ref_bases > 4 * (uint64_t)f.ref.size()) throw Refuse{"ref.bin is shorter than its contigs"};
+			ok(A.ctx, mcom_decode_check_lines(A.ctx, t.d, t.bytes, t.start, nm, L, 0, d_flag));
+			s.src.d_text = t.d; s.src.text_bytes = t.bytes; s.src.d_line_start = t.start;
+			s.src.d_ref = A.upload(f.ref.data(), f.ref.size()); s.src.ref_bytes = f.ref.size();
+			s.src.d_cid = cid; s.src.d_pos = pos; s.src.d_coff = coff; s.src.n_contigs = nc;
+			s.src.d_dir = A.upload(f.dir.data(), f.dir.size()); s.src.dir_bytes = f.dir.size();
+			if (mode == ORDER) {
+				const uint32_t *d = A.upload((const uint32_t*)f.ids.data(), (size_t)nm);
+				uint64_t *dest = A.alloc<uint64_t>(nm);
+				ok(A.ctx, mcom_decode_member_ids(A.ctx, d, nm, d_moff, cid, pos, dest));
+				s.d_dest = dest;
+			}
+			segs.push_back(s);
+		}
+		// A.3 rows
+		uint64_t total = 0;
+		for (const Seg &s : segs) total += s.n;
+		uint64_t n_rows = total;
+		if (mode == ORDER) { if (total != (uint64_t)n_seq) throw Refuse{"the streams do not hold n_seq reads"}; }
+		if (mode == PE) {
+			if (total != 2 * (uint64_t)half) throw Refuse{"the streams do not hold 2 x half reads"};
+			// the eight lists share file.bin.sp / peids.bin.sp; every set has its own pair
+			uint64_t zeros = 0, n_sp = 0;
+			for (size_t i = 0; i < n_list_segs; ++i) n_sp += segs[i].n;
+			{
+				const uint8_t *fb = A.upload(h_fsp.data(), h_fsp.size());
+				const uint32_t *pe = A.upload((const uint32_t*)h_psp.data(), h_psp.size() / 4);
+				uint64_t *dest = A.alloc<uint64_t>(n_sp), ones = 0;
+				ok(A.ctx, mcom_decode_pe_dest(A.ctx, fb, h_fsp.size(), 0, n_sp, pe, h_psp.size() / 4, 0, (uint64_t)half, dest, &ones, d_flag));
+				uint64_t at = 0;
+				for (size_t i = 0; i < n_list_segs; ++i) { segs[i].d_dest = dest + at; at += segs[i].n; }
+				zeros = n_sp - ones;
+			}
+			for (int th = 0; th < nth; ++th) {
+				const SetFiles &f = sets[(size_t)th];
+				Seg &s = segs[n_list_segs + (size_t)th];
+				const uint8_t *fb = A.upload(f.fb.data(), f.fb.size());
+				const uint32_t *pe = A.upload((const uint32_t*)f.pe.data(), f.pe.size() / 4);
+				uint64_t *dest = A.alloc<uint64_t>(s.n), ones = 0;
+				ok(A.ctx, mcom_decode_pe_dest(A.ctx, fb, f.fb.size(), 0, s.n, pe, f.pe.size() / 4, zeros, (uint64_t)half, dest, &ones, d_flag));
+				s.d_dest = dest;
+				zeros += s.n - ones;
+			}
+			if (zeros != (uint64_t)half) throw Refuse{"the first file does not get half of the reads"};
+		}
+		if (mode == DEFAULT) { uint64_t at = 0; for (Seg &s : segs) { s.dest0 = at; at += s.n; } }
+		// everything the files say about sizes has been checked: a raised flag refuses the archive before a read is decoded
+		if (read_flag(A, d_flag)) throw Refuse{"the stream files are inconsistent"};
+		const uint64_t row = (uint64_t)L + 1, table_bytes = n_rows * row;
+		{
+			size_t fr = 0, tot = 0;
+			if (hipMemGetInfo(&fr, &tot) != hipSuccess || table_bytes + n_rows / 8 + ((size_t)64 << 20) > fr) {
+				fprintf(stderr, "minicom gpu decoder: %llu rows of %d + 1 bytes do not fit the card (%zu bytes free)\n", (unsigned long long)n_rows, L, fr);
+				throw Refuse{"the rows do not fit the card"};
+			}
+		}
+		uint8_t *table = A.alloc<uint8_t>(table_bytes);
+		uint32_t *seen = nullptr;
+		if (mode != DEFAULT) {
+			seen = A.alloc<uint32_t>(n_rows / 32 + 1);
+			if (hipMemset(seen, 0, (n_rows / 32 + 1) * 4) != hipSuccess) throw Refuse{"memset failed"};
+		}
+		g_times[1] = now_ms() - t0;                                            // upload, indices and destinations (interleaved per stream)
+
+		// ---- B. decode
+		if (hipEventCreate(&A.ev[0]) != hipSuccess || hipEventCreate(&A.ev[1]) != hipSuccess) throw Refuse{"no events"};
+		t0 = now_ms();
+		(void)hipEventRecord(A.ev[0], nullptr);
+		for (const Seg &s : segs) ok(A.ctx, mcom_decode_reads(A.ctx, &s.src, s.n, L, s.d_dest, s.dest0, table, n_rows, seen, d_flag));
+		(void)hipEventRecord(A.ev[1], nullptr);
+		const uint32_t fl = read_flag(A, d_flag);
+		{ float ms = 0; if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_times[3] = ms; }
+		g_times[2] = now_ms() - t0;
+		if (fl) throw Refuse{"a read cannot be decoded or placed"};
+
+		// ---- the file(s): copy of piece i + 1 under the write of piece i
+		t0 = now_ms();
+		uint8_t *pin[2] = {nullptr, nullptr};
+		for (int b = 0; b < 2; ++b) { void *p = nullptr; if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"}; A.pinned.push_back(p); pin[b] = (uint8_t*)p; }
+		const int n_files = mode == PE ? 2 : 1;
+		const char *paths[2] = {out_path1, out_path2};
+		bool wrote_ok = true;
+		for (int fi = 0; fi < n_files && wrote_ok; ++fi) {
+			const uint64_t first = mode == PE ? (uint64_t)fi * (uint64_t)half * row : 0, bytes = mode == PE ? (uint64_t)half * row : table_bytes;
+			FILE *out = fopen(paths[fi], "wb");
+			if (!out) { wrote_ok = false; break; }
+			const uint64_t pieces = (bytes + PIECE_BYTES - 1) / PIECE_BYTES;
+			auto piece_bytes = [&](uint64_t i) { const uint64_t at = i * PIECE_BYTES; return (size_t)(bytes - at < PIECE_BYTES ? bytes - at : PIECE_BYTES); };
+			if (pieces && hipMemcpyAsync(pin[0], table + first, piece_bytes(0), hipMemcpyDeviceToHost, nullptr) != hipSuccess) wrote_ok = false;
+			for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
+				if (hipStreamSynchronize(nullptr) != hipSuccess) { wrote_ok = false; break; }
+				if (i + 1 < pieces && hipMemcpyAsync(pin[(i + 1) & 1], table + first + (i + 1) * PIECE_BYTES, piece_bytes(i + 1), hipMemcpyDeviceToHost, nullptr) != hipSuccess) { wrote_ok = false; break; }
+				const double tw = now_ms();
+				if (fwrite(pin[i & 1], 1, piece_bytes(i), out) != piece_bytes(i)) wrote_ok = false;
+				g_times[5] += now_ms() - tw;
+			}
+			(void)hipStreamSynchronize(nullptr);
+			if (fclose(out) != 0) wrote_ok = false;
+		}
+		if (!wrote_ok) { for (int fi = 0; fi < n_files; ++fi) remove(paths[fi]); return -1; }
+		g_times[4] = now_ms() - t0;
+		if (n_out) *n_out = mode == PE ? (uint64_t)half : n_rows;
+	} catch (const Refuse &r) {
+		fprintf(stderr, "minicom gpu decoder: %s refused: %s\n", folder, r.why);
+		return -1;
+	}
+	g_times[6] = now_ms() - t_begin;
+	return 0;
+}
+
+int guarded(Mode mode, const char *folder, const char *o1, const char *o2, uint64_t *n, int device)
+{
+	if (!folder || !o1 || (mode == PE && !o2)) return -1;
+	try { return run(mode, folder, o1, o2, n, device); } catch (...) { return -1; }   // no C++ exception crosses the C boundary
+}
+
+} // namespace
+
+extern "C" int mcomh_decompress_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(DEFAULT, folder, out_path, nullptr, n_reads, device); }
+extern "C" int mcomh_decompress_order_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(ORDER, folder, out_path, nullptr, n_reads, device); }
+extern "C" int mcomh_decompress_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device) { return guarded(PE, folder, out_path1, out_path2, n_pairs, device); }
+extern "C" void mcomh_decompress_gpu_times(double *ms8) { if (ms8) memcpy(ms8, g_times, sizeof(g_times)); }

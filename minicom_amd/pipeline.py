@@ -52,6 +52,10 @@ def load_host_library():
     L.mcomh_decompress_order.restype = i32; L.mcomh_decompress_order.argtypes = [cp, cp, C.POINTER(C.c_uint64)]
     L.mcomh_cluster_dump_pe.restype = i32; L.mcomh_cluster_dump_pe.argtypes = [vp, cp]
     L.mcomh_decompress_pe.restype = i32; L.mcomh_decompress_pe.argtypes = [cp, cp, cp, C.POINTER(C.c_uint64)]
+    L.mcomh_decompress_gpu.restype = i32; L.mcomh_decompress_gpu.argtypes = [cp, cp, C.POINTER(C.c_uint64), i32]
+    L.mcomh_decompress_order_gpu.restype = i32; L.mcomh_decompress_order_gpu.argtypes = [cp, cp, C.POINTER(C.c_uint64), i32]
+    L.mcomh_decompress_pe_gpu.restype = i32; L.mcomh_decompress_pe_gpu.argtypes = [cp, cp, cp, C.POINTER(C.c_uint64), i32]
+    L.mcomh_decompress_gpu_times.restype = None; L.mcomh_decompress_gpu_times.argtypes = [C.POINTER(C.c_double)]
     L.mcomh_fastq_pair_to_device.restype = i32
     L.mcomh_fastq_pair_to_device.argtypes = [cp, cp, i32, C.POINTER(i32), sz, C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
     L.mcomh_n_contigs.restype = sz; L.mcomh_n_contigs.argtypes = [vp]
@@ -81,6 +85,7 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_list", "mcomh_stat", "mcomh_prof_enable", "mcomh_prof_read", "mcomh_prof_kernels", "mcomh_fastq_read", "mcomh_fastq_to_device",
                     "mcomh_device_free", "mcomh_cluster_dump_order", "mcomh_decompress_order",
                     "mcomh_cluster_dump_pe", "mcomh_decompress_pe", "mcomh_fastq_pair_to_device",
+                    "mcomh_decompress_gpu", "mcomh_decompress_order_gpu", "mcomh_decompress_pe_gpu", "mcomh_decompress_gpu_times",
                     "mcomh_contig_set", "mcomh_result_digest",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
@@ -88,15 +93,27 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_comm_stats", "mcomh_comm_seconds", "mcomh_create_dist", "mcomh_pool_trim"]
 
 
-def decompress(folder: str, out_path: str, order: bool = False) -> int:
+def decompress(folder: str, out_path: str, order: bool = False, device: int | None = None) -> int:
     """mcomh_decompress(_order): stream files -> one read per line (order=True: the -p file set, original order).
-    Returns the number of reads.  Host only."""
+    Returns the number of reads.  device=None: the host decoder; an integer: the reads are rebuilt on that GPU
+    (mcomh_decompress(_order)_gpu: the same bytes; an error, never the host decoder, when there is no such GPU)."""
     n = C.c_uint64()
     lib = load_host_library()
-    rc = (lib.mcomh_decompress_order if order else lib.mcomh_decompress)(folder.encode(), out_path.encode(), C.byref(n))
+    if device is None:
+        rc = (lib.mcomh_decompress_order if order else lib.mcomh_decompress)(folder.encode(), out_path.encode(), C.byref(n))
+    else:
+        rc = (lib.mcomh_decompress_order_gpu if order else lib.mcomh_decompress_gpu)(folder.encode(), out_path.encode(), C.byref(n), int(device))
     if rc:
-        raise McomError(f"cannot decode the stream files in {folder}")
+        raise McomError(f"cannot decode the stream files in {folder}" + ("" if device is None else f" on GPU {device}"))
     return int(n.value)
+
+
+def decompress_gpu_times() -> dict:
+    """mcomh_decompress_gpu_times: where the last GPU decode of this process spent its time, in ms."""
+    t = (C.c_double * 8)()
+    load_host_library().mcomh_decompress_gpu_times(t)
+    return {"read_files_ms": t[0], "upload_index_ms": t[1], "decode_wall_ms": t[2], "decode_kernels_ms": t[3],
+            "download_write_ms": t[4], "write_ms": t[5], "total_ms": t[6]}
 
 
 def pool_trim():
@@ -104,12 +121,16 @@ def pool_trim():
     load_host_library().mcomh_pool_trim()
 
 
-def decompress_pe(folder: str, out_path1: str, out_path2: str) -> int:
-    """mcomh_decompress_pe: the paired-end file set -> two files, line i of both is a pair.  Returns the number of pairs."""
+def decompress_pe(folder: str, out_path1: str, out_path2: str, device: int | None = None) -> int:
+    """mcomh_decompress_pe: the paired-end file set -> two files, line i of both is a pair.  Returns the number of pairs.
+    device: as for decompress()."""
     n = C.c_uint64()
-    rc = load_host_library().mcomh_decompress_pe(folder.encode(), out_path1.encode(), out_path2.encode(), C.byref(n))
+    if device is None:
+        rc = load_host_library().mcomh_decompress_pe(folder.encode(), out_path1.encode(), out_path2.encode(), C.byref(n))
+    else:
+        rc = load_host_library().mcomh_decompress_pe_gpu(folder.encode(), out_path1.encode(), out_path2.encode(), C.byref(n), int(device))
     if rc:
-        raise McomError(f"cannot decode the paired-end stream files in {folder}")
+        raise McomError(f"cannot decode the paired-end stream files in {folder}" + ("" if device is None else f" on GPU {device}"))
     return int(n.value)
 
 
