@@ -695,6 +695,23 @@ typedef struct {
 int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
                       uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag);
 
+/* ---- the built-in entropy stage: `.rans` members (csrc/entropy.hip; format and host twin: DESIGN.md section 3.6, include/mcom_host.h) ----
+ * A static rANS coder, 12-bit frequencies, one model per member: stored, order-0 or order-1 (context = the previous byte of the same
+ * plane), each over byte planes of stride 1, 2 or 4 (byte i belongs to plane i mod stride).  The member is cut into segments of 2 KiB,
+ * one rANS state and one byte run per segment, one lane per segment.  Device pointers in and out, work on the context's stream;
+ * both calls are synchronous.  The bytes equal those of mcomh_rans_encode for the same input and hint.
+ *   mcom_rans_bound   room that is enough for n raw bytes under ANY model hint (the chosen model never needs more than 32 + n)
+ *   mcom_rans_encode  model_hint 0: the (model, stride) with the smallest estimated size, made from the histograms alone (ties: the
+ *                     simpler one); MCOM_RANS_HINT(model, stride) forces one (model 0 stored, 1 order-0, 2 order-1; tests).
+ *                     MCOM_E_OVERFLOW when cap is too small (nothing valid in d_out)
+ *   mcom_rans_decode  *out_len = the raw length.  MCOM_E_OVERFLOW (with *out_len = the room needed) when cap is too small; MCOM_E_ARG
+ *                     for a member that is truncated, malformed or fails its CRC-32 -- d_out then holds nothing valid.  Untrusted
+ *                     input never makes a kernel leave its buffers (it raises a flag word and skips the access).                    */
+#define MCOM_RANS_HINT(model, stride) (0x100 | ((model) << 4) | (stride))
+uint64_t mcom_rans_bound(uint64_t n);
+int mcom_rans_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, int model_hint);
+int mcom_rans_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
+
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,
                      uint64_t first, uint64_t count, uint8_t *d_ascii, size_t pitch);

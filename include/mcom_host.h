@@ -206,6 +206,25 @@ int  mcomh_create_dist(mcomh_pipeline **out, int device, void *hip_stream, mcomh
                        const uint8_t *d_reads, size_t pitch, size_t n_local, uint64_t rid0, uint64_t n_total, int L,
                        const mcomh_params *p);
 
+/* ---- the built-in entropy stage: `.rans` members (host/mcom_entropy.cpp) ----
+ * The host twin of mcom_rans_encode / mcom_rans_decode (include/mcom.h): plain C++ on host buffers, no GPU, no HIP call; the same
+ * bytes out for the same input and hint, the same members accepted and refused.  0 on success, -4 when cap is too small (decode:
+ * *out_len = the room needed), -1 for bad arguments and for a member that is truncated, malformed or fails its CRC-32.
+ *   mcomh_rans_bound     room that is enough under any model hint (hint 0 never needs more than 32 + n)
+ *   mcomh_rans_estimate  the estimated coded sizes the choice compares, in the order of its preference on ties: stored, order-0 with
+ *                        stride 1 / 2 / 4, order-1 with stride 1 / 2 / 4
+ * File forms (what bin/mcomz runs): device = -1 the host twin, otherwise that GPU -- the file goes up and the result comes down through
+ * two page-locked pieces, each copy beside the read / write of the next piece; an error, never the host twin, when there is no such
+ * GPU.  No output file is left by a call that fails.  mcomh_entropy_times, ms of the last file call: [0] read (+ upload), [1] the
+ * codec, [2] (download +) write, [3] the whole call, [4] raw bytes, [5] coded bytes.                                               */
+uint64_t mcomh_rans_bound(uint64_t n);
+int mcomh_rans_estimate(const uint8_t *in, uint64_t n, uint64_t est7[7]);
+int mcomh_rans_encode(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, int model_hint);
+int mcomh_rans_decode(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int mcomh_entropy_pack_file(const char *in_path, const char *out_path, int device);
+int mcomh_entropy_unpack_file(const char *in_path, const char *out_path, int device);
+void mcomh_entropy_times(double *ms8);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

@@ -10,7 +10,9 @@ stage is built in: every member goes through one of the codecs below and carries
 member names; everything else about the layout is the reference's, so an archive written with `bsc` present is
 what the reference's script unpacks.
 
-This is packaging on the host, nothing here touches the GPU; the stream files themselves are the parity boundary
+`codec="rans"` is the project's own entropy stage: a static rANS coder whose host twin and GPU kernels emit the
+same bytes.  With `device=None` the members are coded by the host twin, with an integer by that GPU (libmcom_hip.so through
+libmcom_host.so); every other codec is packaging on the host.  The stream files themselves are the parity boundary
 (tests/test_streams.py compares them byte for byte with the reference's).
 """
 import bz2
@@ -35,7 +37,7 @@ GROUPS = (
     ("filebin", ("file.bin.*",)),                    # :259-262, paired end only
 )
 SINGLES = ("single_N.seq", "single.seq", "AA.txt", "TT.txt", "NN.txt")      # :136-137, :144-146
-CODECS = ("xz", "bz2", "gz", "raw", "bsc")
+CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans")
 
 
 def _encode(data: bytes, codec: str) -> bytes:
@@ -76,6 +78,24 @@ def _bsc(args, src: bytes, tmpdir: str, tag: str) -> bytes:
     return out
 
 
+def _rans(data: bytes, pack_it: bool, device, tmpdir: str, tag: str) -> bytes:
+    """One member through the built-in entropy stage: the host twin on the bytes, or -- device given -- the file route on that GPU."""
+    from . import pipeline
+    if device is None:
+        return pipeline.rans_encode(data) if pack_it else pipeline.rans_decode(data)
+    a, b = os.path.join(tmpdir, tag + ".rin"), os.path.join(tmpdir, tag + ".rout")
+    with open(a, "wb") as f:
+        f.write(data)
+    try:
+        pipeline.entropy_file(a, b, pack_it, device)
+        with open(b, "rb") as f:
+            return f.read()
+    finally:
+        for p in (a, b):
+            if os.path.exists(p):
+                os.remove(p)
+
+
 def _inner_tar(folder: str, names) -> bytes:
     """`tar -cf X.tar -C X .` of the reference: plain member names, sorted for a reproducible archive."""
     buf = io.BytesIO()
@@ -89,8 +109,9 @@ def _inner_tar(folder: str, names) -> bytes:
     return buf.getvalue()
 
 
-def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8) -> dict:
-    """Stream files in `folder` (as cluster_dump left them) -> one `.minicom` file.  Returns the member sizes."""
+def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device: int | None = None) -> dict:
+    """Stream files in `folder` (as cluster_dump left them) -> one `.minicom` file.  Returns the member sizes.
+    device (codec "rans" only): None = the host twin, an integer = that GPU, one member at a time."""
     if codec not in CODECS:
         raise ValueError("codec must be one of %s" % (CODECS,))
     if not os.path.isfile(os.path.join(folder, "info.txt")):
@@ -111,9 +132,11 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8) -> dic
         name, data = item
         if codec == "bsc":                               # minicom:115 etc.: bsc e IN OUT -b64p -tN -e2
             return name + ".bsc", _bsc(("e", "-b64p", "-t%d" % threads, "-e2"), data, folder, name)
+        if codec == "rans":
+            return name + ".rans", _rans(data, True, device, folder, name)
         return name + "." + ext, _encode(data, codec)
 
-    with ThreadPoolExecutor(max(1, threads)) as ex:
+    with ThreadPoolExecutor(max(1, threads) if device is None else 1) as ex:
         packed = list(ex.map(enc, members))
     sizes = {}
     with tarfile.open(out_path, mode="w", format=tarfile.GNU_FORMAT) as t:
@@ -128,9 +151,10 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8) -> dic
     return sizes
 
 
-def unpack(path: str, folder: str, threads: int = 8) -> dict:
+def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) -> dict:
     """`.minicom` file -> the stream files in `folder` (created if absent).  Returns what the archive says about itself:
-    {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334)."""
+    {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334).
+    device: where `.rans` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
         items = [(m.name.lstrip("./"), t.extractfile(m).read()) for m in t.getmembers() if m.isfile()]
@@ -145,9 +169,11 @@ def unpack(path: str, folder: str, threads: int = 8) -> dict:
             return base, _bsc(("d", "-t%d" % threads), data, folder, base)
         if ext == "7z":
             raise RuntimeError("member %s needs 7z; archives written here use one codec for every member" % name)
+        if ext == "rans":
+            return base, _rans(data, False, device, folder, base)
         return base, _decode(data, ext)
 
-    with ThreadPoolExecutor(max(1, threads)) as ex:
+    with ThreadPoolExecutor(max(1, threads) if device is None else 1) as ex:
         plain = list(ex.map(dec, items))
     for name, data in plain:
         if name.startswith("idsbin.tar"):
@@ -171,7 +197,8 @@ def unpack(path: str, folder: str, threads: int = 8) -> dict:
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
-    fallback), the stream writer and the packaging on the host.  Returns pack()'s member sizes plus the read count."""
+    fallback), the stream writer and the packaging on the host -- except codec "rans", whose members are coded on `device` too.
+    Returns pack()'s member sizes plus the read count."""
     import tempfile
     from .pipeline import Pipeline
     if order and path2 is not None:
@@ -181,7 +208,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.pre_process()
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
             p.cluster_dump(td, order=order, paired=path2 is not None)
-            sizes = pack(td, out_path, codec=codec, threads=threads)
+            sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec == "rans" else None)
         sizes["n_reads"] = p.n
         return sizes
     finally:
@@ -191,11 +218,12 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
 def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None) -> int:
     """`.minicom` -> reads, one per line: the original order for an archive written with -p, two files (line i of both a
     pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
-    integer: the entropy stage on the host, the reads rebuilt on that GPU (pipeline.decompress(..., device=))."""
+    integer: `.rans` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
+    are host code either way."""
     import tempfile
     from .pipeline import decompress, decompress_pe
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
-        kinds = unpack(path, td, threads=threads)
+        kinds = unpack(path, td, threads=threads, device=device)
         if kinds["paired"]:
             if out_path2 is None:
                 raise ValueError("a paired-end archive decodes into two files")

@@ -26,6 +26,11 @@ class DecodeSrc(C.Structure):
 DECODE_F_BOUNDS, DECODE_F_LINE, DECODE_F_DUP, DECODE_F_DEST = 1, 2, 4, 8
 
 
+def rans_hint(model: int, stride: int = 1) -> int:
+    """MCOM_RANS_HINT of include/mcom.h"""
+    return 0x100 | (model << 4) | stride
+
+
 def lib_path() -> str:
     return os.path.join(HERE, "lib", "libmcom_hip.so")
 
@@ -146,6 +151,9 @@ def load_library():
     L.mcom_decode_pe_dest.restype = i32; L.mcom_decode_pe_dest.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, u64, vp, C.POINTER(u64), vp]
     L.mcom_decode_check_lines.restype = i32; L.mcom_decode_check_lines.argtypes = [vp, vp, u64, vp, u64, i32, i32, vp]
     L.mcom_decode_reads.restype = i32; L.mcom_decode_reads.argtypes = [vp, C.POINTER(DecodeSrc), u64, i32, vp, u64, vp, u64, vp, vp]
+    L.mcom_rans_bound.restype = u64; L.mcom_rans_bound.argtypes = [u64]
+    L.mcom_rans_encode.restype = i32; L.mcom_rans_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcom_rans_decode.restype = i32; L.mcom_rans_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.mcom_synth_reads.restype = i32
     L.mcom_synth_reads.argtypes = [vp, u64, u64, i32, i32, C.c_double, u64, u64, vp, sz]
     L.mcom_synth_reads_genome.restype = i32
@@ -878,6 +886,34 @@ class Context:
         self._check(self.lib.mcom_decode_reads(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, self._p(out), n_rows, self._p(seen) if seen is not None else None, self._p(flag)))
         self.sync()
         return out, int(flag.item())
+
+    # ---- the built-in entropy stage (csrc/entropy.hip) ----
+    def rans_encode(self, raw, model=None, stride=1):
+        """mcom_rans_encode.  raw: uint8 device tensor.  model None: chosen by estimated size; 0 stored, 1 order-0, 2 order-1 with
+        `stride` 1, 2 or 4 force one.  Returns the `.rans` member as a uint8 device tensor."""
+        torch = _torch()
+        n = int(raw.shape[0])
+        hint = 0 if model is None else rans_hint(model, stride)
+        cap = 32 + n if model is None else int(self.lib.mcom_rans_bound(n))
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        got = C.c_uint64()
+        self._check(self.lib.mcom_rans_encode(self._h, self._p(raw, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got), hint))
+        return out[:got.value]
+
+    def rans_decode(self, member, cap=None):
+        """mcom_rans_decode.  member: uint8 device tensor.  Returns the raw bytes as a uint8 device tensor; McomError for a member that is
+        truncated, malformed or fails its CRC-32.  cap: room to offer (default: what the member's header asks for, at most 1 TB)."""
+        torch = _torch()
+        n = int(member.shape[0])
+        if cap is None:
+            head = bytes(member[:16].cpu().numpy()) if n >= 16 else b""
+            cap = int.from_bytes(head[8:16], "little") if len(head) == 16 else 0
+            if cap > 1 << 40:
+                raise McomError("rans_decode: the header asks for %d bytes" % cap)
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
+        got = C.c_uint64()
+        self._check(self.lib.mcom_rans_decode(self._h, self._p(member, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
+        return out[:got.value]
 
 
 class Index:

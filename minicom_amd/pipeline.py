@@ -75,6 +75,14 @@ def load_host_library():
     L.mcomh_fastq_to_device.restype = i32
     L.mcomh_fastq_to_device.argtypes = [cp, i32, C.POINTER(i32), sz, C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
     L.mcomh_device_free.restype = None; L.mcomh_device_free.argtypes = [vp]
+    u64 = C.c_uint64
+    L.mcomh_rans_bound.restype = u64; L.mcomh_rans_bound.argtypes = [u64]
+    L.mcomh_rans_estimate.restype = i32; L.mcomh_rans_estimate.argtypes = [vp, u64, C.POINTER(u64)]
+    L.mcomh_rans_encode.restype = i32; L.mcomh_rans_encode.argtypes = [vp, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcomh_rans_decode.restype = i32; L.mcomh_rans_decode.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcomh_entropy_pack_file.restype = i32; L.mcomh_entropy_pack_file.argtypes = [cp, cp, i32]
+    L.mcomh_entropy_unpack_file.restype = i32; L.mcomh_entropy_unpack_file.argtypes = [cp, cp, i32]
+    L.mcomh_entropy_times.restype = None; L.mcomh_entropy_times.argtypes = [C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -87,6 +95,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_cluster_dump_pe", "mcomh_decompress_pe", "mcomh_fastq_pair_to_device",
                     "mcomh_decompress_gpu", "mcomh_decompress_order_gpu", "mcomh_decompress_pe_gpu", "mcomh_decompress_gpu_times",
                     "mcomh_contig_set", "mcomh_result_digest",
+                    # the built-in entropy stage (host/mcom_entropy.cpp)
+                    "mcomh_rans_bound", "mcomh_rans_estimate", "mcomh_rans_encode", "mcomh_rans_decode", "mcomh_entropy_pack_file",
+                    "mcomh_entropy_unpack_file", "mcomh_entropy_times",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -114,6 +125,61 @@ def decompress_gpu_times() -> dict:
     load_host_library().mcomh_decompress_gpu_times(t)
     return {"read_files_ms": t[0], "upload_index_ms": t[1], "decode_wall_ms": t[2], "decode_kernels_ms": t[3],
             "download_write_ms": t[4], "write_ms": t[5], "total_ms": t[6]}
+
+
+RANS_MODELS = ((0, 1), (1, 1), (1, 2), (1, 4), (2, 1), (2, 2), (2, 4))     # (model, stride) in the order of mcomh_rans_estimate
+
+
+def rans_encode(data: bytes, model: int | None = None, stride: int = 1) -> bytes:
+    """mcomh_rans_encode, the host twin of the GPU coder: raw bytes -> a `.rans` member.  model None: chosen by estimated size;
+    0 stored, 1 order-0, 2 order-1 with `stride` 1, 2 or 4 force one."""
+    lib = load_host_library()
+    n = len(data)
+    cap = 32 + n if model is None else int(lib.mcomh_rans_bound(n))
+    out = C.create_string_buffer(cap)
+    got = C.c_uint64()
+    src = (C.c_char * n).from_buffer_copy(data) if n else None
+    rc = lib.mcomh_rans_encode(src, n, out, cap, C.byref(got), 0 if model is None else 0x100 | (model << 4) | stride)
+    if rc:
+        raise McomError(f"rans_encode: error {rc}")
+    return out.raw[:got.value]
+
+
+def rans_decode(member: bytes, cap: int | None = None) -> bytes:
+    """mcomh_rans_decode: a `.rans` member -> the raw bytes; McomError for one that is truncated, malformed or fails its CRC-32."""
+    lib = load_host_library()
+    n = len(member)
+    if cap is None:
+        cap = int.from_bytes(member[8:16], "little") if n >= 16 else 0
+        if cap > 1 << 40:
+            raise McomError("rans_decode: the header asks for %d bytes" % cap)
+    out = C.create_string_buffer(max(cap, 1))
+    got = C.c_uint64()
+    src = (C.c_char * n).from_buffer_copy(member) if n else None
+    rc = lib.mcomh_rans_decode(src, n, out, cap, C.byref(got))
+    if rc:
+        raise McomError(f"rans_decode: error {rc}: not a complete, intact .rans member")
+    return out.raw[:got.value]
+
+
+def rans_estimate(data: bytes) -> list[int]:
+    """mcomh_rans_estimate: the estimated coded size of every candidate, in the order of RANS_MODELS."""
+    est = (C.c_uint64 * 7)()
+    n = len(data)
+    load_host_library().mcomh_rans_estimate((C.c_char * n).from_buffer_copy(data) if n else None, n, est)
+    return [int(v) for v in est]
+
+
+def entropy_file(in_path: str, out_path: str, pack: bool, device: int | None = None) -> dict:
+    """mcomh_entropy_pack_file / _unpack_file: a file -> a `.rans` member file or back.  device None: the host twin; an integer:
+    that GPU (an error, never the host twin, when there is none).  Returns mcomh_entropy_times as a dict."""
+    lib = load_host_library()
+    fn = lib.mcomh_entropy_pack_file if pack else lib.mcomh_entropy_unpack_file
+    if fn(in_path.encode(), out_path.encode(), -1 if device is None else int(device)):
+        raise McomError(("cannot pack %s" if pack else "%s is not a complete, intact .rans member") % in_path + ("" if device is None else f" (GPU {device})"))
+    t = (C.c_double * 8)()
+    lib.mcomh_entropy_times(t)
+    return {"read_upload_ms": t[0], "codec_ms": t[1], "download_write_ms": t[2], "total_ms": t[3], "raw_bytes": int(t[4]), "coded_bytes": int(t[5])}
 
 
 def pool_trim():
