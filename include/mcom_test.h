@@ -44,6 +44,15 @@ int mcom_screen_fallbacks(const mcom_ctx *ctx);
  * workgroup lists the (singleton, pair) tasks whose keys this share owns on a stack in LDS and a thread takes one task (k_realign_owned);
  * 1 = the kernel of the whole index with several pairs per lane, a lane dropping the pairs it does not own.  Same claims either way.  */
 int mcom_set_lookup_route(mcom_ctx *ctx, int route);
+/* The entropy stage (csrc/entropy.hip) has two kernels whose output never leaves the library: the histograms are only seen through the
+ * 12-bit tables of the chosen model, the per-segment CRCs only after the host has joined them.  These run the very launches of
+ * mcom_rans_encode / mcom_rans_decode (same grid, same aligned / byte-wise choice from the pointer, same cleared table) and hand the
+ * result out.  d_in: n > 0 bytes on the device, at any address.
+ * mcom_test_rans_hist: d_counts gets 4 * 256 + 7 * 65536 u64, as the encoder downloads them: the order-0 counts [i mod 4][symbol], then
+ * the order-1 counts [plane][context][symbol] of the planes 0 | 1 2 | 3 4 5 6 (stride 1 | 2 | 4).
+ * mcom_test_rans_seg_crc: d_crc gets one CRC-32 per segment of 2^seg_log2 bytes (8 .. 15), the last one of what is left.                */
+int mcom_test_rans_hist(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_counts);
+int mcom_test_rans_seg_crc(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t seg_log2, uint32_t *d_crc);
 
 
 /* ---- libmcom_host.so ---- */

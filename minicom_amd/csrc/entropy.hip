@@ -296,15 +296,39 @@ struct Blocks {                                             // pooled device blo
 };
 unsigned blocks_for(uint64_t items) { return (unsigned)((items + RN_THREADS - 1) / RN_THREADS); }
 
-int device_crc(mcom_ctx *ctx, Blocks &B, const uint8_t *d, uint64_t n, uint32_t seg_log2, int vec, uint32_t *crc_out)
+// The two launches whose results stay inside the library, each in ONE place: the codec calls below and the hooks of include/mcom_test.h
+// go through these, so a hook cannot test a launch (grid, `vec`, cleared table) that the product does not make.
+// d_hist: 4 * 256 + 7 * 65536 u64, cleared here; n > 0
+int launch_hist(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, unsigned long long *d_hist)
+{
+	const size_t hist_words = 4 * 256 + (size_t)N_PLANES_ALL * 65536;
+	const int vec = ((uintptr_t)d_in & 15) == 0;
+	MCOM_HIP(ctx, hipMemsetAsync(d_hist, 0, hist_words * 8, ctx->stream));
+	uint64_t g = (n + 16 * RN_THREADS - 1) / (16 * RN_THREADS), gmax = (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 64) * 8;
+	if (g > gmax) g = gmax;
+	MCOM_LAUNCH(k_rans_hist, dim3((unsigned)g), dim3(RN_THREADS), 0, ctx->stream, d_in, n, d_hist, d_hist + 4 * 256, vec);
+	MCOM_LAUNCH_CHECK(ctx);
+	return MCOM_OK;
+}
+// d_crc: one u32 per segment of 2^seg_log2 bytes; n > 0
+int launch_seg_crc(mcom_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t seg_log2, uint32_t *d_crc)
+{
+	const uint64_t n_seg = (n + ((uint64_t)1 << seg_log2) - 1) >> seg_log2;
+	const int vec = ((uintptr_t)d & 15) == 0;
+	MCOM_LAUNCH(k_rans_crc, dim3(blocks_for(n_seg)), dim3(RN_THREADS), 0, ctx->stream, d, n, n_seg, seg_log2, d_crc, vec);
+	MCOM_LAUNCH_CHECK(ctx);
+	return MCOM_OK;
+}
+
+int device_crc(mcom_ctx *ctx, Blocks &B, const uint8_t *d, uint64_t n, uint32_t seg_log2, uint32_t *crc_out)
 {
 	*crc_out = 0;
 	if (!n) return MCOM_OK;
 	const uint64_t seg_bytes = (uint64_t)1 << seg_log2, n_seg = (n + seg_bytes - 1) >> seg_log2;
 	uint32_t *d_crc = nullptr;
 	MCOM_HIP(ctx, B.get(&d_crc, n_seg * 4));
-	MCOM_LAUNCH(k_rans_crc, dim3(blocks_for(n_seg)), dim3(RN_THREADS), 0, ctx->stream, d, n, n_seg, seg_log2, d_crc, vec);
-	MCOM_LAUNCH_CHECK(ctx);
+	int rc = launch_seg_crc(ctx, d, n, seg_log2, d_crc);
+	if (rc) return rc;
 	std::vector<uint32_t> h(n_seg);
 	MCOM_HIP(ctx, hipMemcpyAsync(h.data(), d_crc, n_seg * 4, hipMemcpyDeviceToHost, ctx->stream));
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
@@ -345,14 +369,11 @@ extern "C" int mcom_rans_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, 
 		unsigned long long *d_hist = nullptr;
 		const size_t hist_words = 4 * 256 + (size_t)N_PLANES_ALL * 65536;
 		MCOM_HIP(ctx, B.get(&d_hist, hist_words * 8));
-		MCOM_HIP(ctx, hipMemsetAsync(d_hist, 0, hist_words * 8, ctx->stream));
-		uint64_t g = (n + 16 * RN_THREADS - 1) / (16 * RN_THREADS), gmax = (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 64) * 8;
-		if (g > gmax) g = gmax;
-		MCOM_LAUNCH(k_rans_hist, dim3((unsigned)g), dim3(RN_THREADS), 0, ctx->stream, d_in, n, d_hist, d_hist + 4 * 256, vec);
-		MCOM_LAUNCH_CHECK(ctx);
+		int rc = launch_hist(ctx, d_in, n, d_hist);
+		if (rc) return rc;
 		MCOM_HIP(ctx, hipMemcpyAsync(hist.o0.data(), d_hist, 4 * 256 * 8, hipMemcpyDeviceToHost, ctx->stream));
 		MCOM_HIP(ctx, hipMemcpyAsync(hist.o1.data(), d_hist + 4 * 256, (size_t)N_PLANES_ALL * 65536 * 8, hipMemcpyDeviceToHost, ctx->stream));
-		int rc = device_crc(ctx, B, d_in, n, SEG_LOG2, vec, &hd.crc);        // (synchronises: the histograms are down as well)
+		rc = device_crc(ctx, B, d_in, n, SEG_LOG2, &hd.crc);             // (synchronises: the histograms are down as well)
 		if (rc) return rc;
 	}
 	Model m;
@@ -470,9 +491,32 @@ extern "C" int mcom_rans_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 		if (flag) { *out_len = 0; return mcom_fail(ctx, MCOM_E_ARG, "rans_decode: corrupt member (flag 0x%x)", flag); }
 	}
 	uint32_t crc = 0;
-	int rc = device_crc(ctx, B, d_out, hd.raw_len, hd.seg_log2, vec, &crc);
+	int rc = device_crc(ctx, B, d_out, hd.raw_len, hd.seg_log2, &crc);
 	if (rc) return rc;
 	if (crc != hd.crc) { *out_len = 0; return mcom_fail(ctx, MCOM_E_ARG, "rans_decode: CRC mismatch"); }
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	return MCOM_OK;
+}
+
+// ---- test hooks (include/mcom_test.h) ----------------------------------------------------------------------------------------------
+extern "C" int mcom_test_rans_hist(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_counts)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (!d_counts || !d_in || !n) return mcom_fail(ctx, MCOM_E_ARG, "test_rans_hist: null pointer or no bytes");
+	if (n > ((uint64_t)1 << 34)) return mcom_fail(ctx, MCOM_E_ARG, "test_rans_hist: %llu bytes (members of up to 16 GB)", (unsigned long long)n);
+	int rc = launch_hist(ctx, d_in, n, (unsigned long long*)d_counts);
+	if (rc) return rc;
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	return MCOM_OK;
+}
+
+extern "C" int mcom_test_rans_seg_crc(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t seg_log2, uint32_t *d_crc)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (!d_crc || !d_in || !n) return mcom_fail(ctx, MCOM_E_ARG, "test_rans_seg_crc: null pointer or no bytes");
+	if (seg_log2 < SEG_LOG2_MIN || seg_log2 > SEG_LOG2_MAX) return mcom_fail(ctx, MCOM_E_ARG, "test_rans_seg_crc: segments of 2^%u bytes", seg_log2);
+	int rc = launch_seg_crc(ctx, d_in, n, seg_log2, d_crc);
+	if (rc) return rc;
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
 	return MCOM_OK;
 }

@@ -888,21 +888,24 @@ class Context:
         return out, int(flag.item())
 
     # ---- the built-in entropy stage (csrc/entropy.hip) ----
-    def rans_encode(self, raw, model=None, stride=1):
+    def rans_encode(self, raw, model=None, stride=1, out=None):
         """mcom_rans_encode.  raw: uint8 device tensor.  model None: chosen by estimated size; 0 stored, 1 order-0, 2 order-1 with
-        `stride` 1, 2 or 4 force one.  Returns the `.rans` member as a uint8 device tensor."""
+        `stride` 1, 2 or 4 force one.  Returns the `.rans` member as a uint8 device tensor.  out: a uint8 device tensor to write the
+        member into (a slice of a larger buffer, as the container passes; its length is the room offered) instead of a fresh one."""
         torch = _torch()
         n = int(raw.shape[0])
         hint = 0 if model is None else rans_hint(model, stride)
-        cap = 32 + n if model is None else int(self.lib.mcom_rans_bound(n))
-        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        cap = int(out.shape[0]) if out is not None else 32 + n if model is None else int(self.lib.mcom_rans_bound(n))
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
         got = C.c_uint64()
         self._check(self.lib.mcom_rans_encode(self._h, self._p(raw, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got), hint))
         return out[:got.value]
 
-    def rans_decode(self, member, cap=None):
+    def rans_decode(self, member, cap=None, out=None):
         """mcom_rans_decode.  member: uint8 device tensor.  Returns the raw bytes as a uint8 device tensor; McomError for a member that is
-        truncated, malformed or fails its CRC-32.  cap: room to offer (default: what the member's header asks for, at most 1 TB)."""
+        truncated, malformed or fails its CRC-32.  cap: room to offer (default: what the member's header asks for, at most 1 TB).
+        out: a uint8 device tensor to decode into (its length is the room offered) instead of a fresh one."""
         torch = _torch()
         n = int(member.shape[0])
         if cap is None:
@@ -910,10 +913,33 @@ class Context:
             cap = int.from_bytes(head[8:16], "little") if len(head) == 16 else 0
             if cap > 1 << 40:
                 raise McomError("rans_decode: the header asks for %d bytes" % cap)
-        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
+        if out is not None:
+            cap = int(out.shape[0])
+        else:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
         got = C.c_uint64()
         self._check(self.lib.mcom_rans_decode(self._h, self._p(member, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
         return out[:got.value]
+
+    def rans_test_hist(self, raw):
+        """Test hook (mcom_test_rans_hist): the counts of k_rans_hist for the uint8 device tensor `raw` (at least one byte), launched as
+        mcom_rans_encode launches it.  Returns (o0 int64 [4, 256], o1 int64 [7, 256, 256]) on the device."""
+        torch = _torch()
+        self.lib.mcom_test_rans_hist.restype = C.c_int; self.lib.mcom_test_rans_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        counts = torch.empty(4 * 256 + 7 * 65536, dtype=torch.int64, device=self.device)
+        self._check(self.lib.mcom_test_rans_hist(self._h, self._p(raw, torch.uint8), int(raw.shape[0]), self._p(counts)))
+        return counts[:1024].view(4, 256), counts[1024:].view(7, 256, 256)
+
+    def rans_test_seg_crc(self, raw, seg_log2: int = 11):
+        """Test hook (mcom_test_rans_seg_crc): the CRC-32 of every segment of 2^seg_log2 bytes of `raw`, as k_rans_crc makes them for
+        the codec calls.  Returns int64 [n_seg] on the device (values below 2^32)."""
+        torch = _torch()
+        self.lib.mcom_test_rans_seg_crc.restype = C.c_int
+        self.lib.mcom_test_rans_seg_crc.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        n = int(raw.shape[0])
+        crc = torch.empty(max(1, -(-n // (1 << seg_log2))), dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_test_rans_seg_crc(self._h, self._p(raw, torch.uint8), n, seg_log2, self._p(crc)))
+        return crc.to(torch.int64) & 0xFFFFFFFF
 
 
 class Index:

@@ -121,3 +121,120 @@ def big_member(golden_dir, size: int) -> np.ndarray:
     at = np.arange(0, size, 97)
     out[at] = rng.integers(0, 256, size=at.size, dtype=np.uint8)
     return out
+
+
+# ---- members made with the independent reference (tests/rans_reference.py) --------------------------------------------------------------
+CODED_MODELS = MODELS[1:]
+
+
+def split_member(member: bytes):
+    """a coded member -> (header dict, serialised tables, list of runs)"""
+    import rans_reference as rr
+    h = rr.parse_header(member)
+    at = HEADER + h["table_bytes"]
+    lens = [int.from_bytes(member[at + 2 * s:at + 2 * s + 2], "little") for s in range(h["n_seg"])]
+    at += 2 * h["n_seg"]
+    runs = []
+    for l in lens:
+        runs.append(member[at:at + l]); at += l
+    assert at == len(member)
+    return h, member[HEADER:HEADER + h["table_bytes"]], runs
+
+
+def join_member(h, tables: bytes, runs, lens=None, **over) -> bytes:
+    """the parts back into a member whose header describes it to the byte (table_bytes and payload_bytes recomputed); lens: the stored
+    run lengths when they are to differ from the runs'; over: header fields to overwrite"""
+    import rans_reference as rr
+    f = dict(h, table_bytes=len(tables), payload_bytes=sum(len(r) for r in runs))
+    f.update(over)
+    lens = [len(r) for r in runs] if lens is None else lens
+    return (rr.ref_header(f["model"], f["stride"], f["seg_log2"], f["raw_len"], f["crc"], f["table_bytes"], f["payload_bytes"])
+            + tables + b"".join(l.to_bytes(2, "little") for l in lens) + b"".join(runs))
+
+
+_CRAFTED = None
+
+
+def crafted_refusals():
+    """(raw, good member, {label: member}): one member per refusal rule of DESIGN 3.6, each made from the reference's order-1 stride-1
+    member of three segments so that the named rule is the first thing wrong with it.  Everything but the "header" cases passes the
+    header check: the sizes are recomputed."""
+    global _CRAFTED
+    if _CRAFTED is not None:
+        return _CRAFTED
+    import rans_reference as rr
+    raw = synthetic_members()["three_segments_minus_1"]
+    good = rr.ref_encode(raw, 2, 1)
+    h, tables, runs = split_member(good)
+    assert h["n_seg"] == 3 and join_member(h, tables, runs) == good
+    state = lambda v: [runs[0], v.to_bytes(4, "little") + runs[1][4:], runs[2]]
+    out = {}
+    # run lengths: the runs as they are, the boundary between the first two moved by one byte
+    out["length_moved_to_neighbour"] = join_member(h, tables, runs, lens=[len(runs[0]) - 1, len(runs[1]) + 1, len(runs[2])])
+    out["run_of_length_3"] = join_member(h, tables, [runs[0], runs[1][:3], runs[2]])
+    out["state_2^23-1"] = join_member(h, tables, state((1 << 23) - 1))
+    out["state_2^31"] = join_member(h, tables, state(1 << 31))
+    out["byte_appended_to_run"] = join_member(h, tables, [runs[0], runs[1] + b"\x00", runs[2]])
+    # tables: rows are n u16, n x (symbol u8, freq u16); the row of context c
+    rows, at = [], 0
+    for c in range(256):
+        n = int.from_bytes(tables[at:at + 2], "little")
+        rows.append(tables[at:at + 2 + 3 * n]); at += 2 + 3 * n
+    assert at == len(tables) and all(len(rows[c]) > 2 for c in range(1, 7))        # the contexts 1 .. 6 occur in every segment
+    emptied = list(rows); emptied[3] = b"\x00\x00"
+    out["table_row_emptied"] = join_member(h, b"".join(emptied), runs)
+    r = bytearray(rows[3])
+    k = next(k for k in range(2, len(r), 3) if int.from_bytes(r[k + 1:k + 3], "little") >= 2)
+    r[k + 1:k + 3] = (int.from_bytes(r[k + 1:k + 3], "little") - 1).to_bytes(2, "little")
+    short = list(rows); short[3] = bytes(r)
+    out["table_row_sums_to_4095"] = join_member(h, b"".join(short), runs)
+    out["header_seg_log2_7"] = join_member(h, tables, runs, seg_log2=7)
+    out["header_seg_log2_16"] = join_member(h, tables, runs, seg_log2=16)
+    # ... and with one segment at any segment size, so that the segment size alone is out of range
+    tiny = rr.ref_encode(raw[:100], 2, 1, seg_log2=8)
+    out["header_seg_log2_7_one_segment"] = tiny[:7] + b"\x07" + tiny[8:]
+    out["header_seg_log2_16_one_segment"] = tiny[:7] + b"\x10" + tiny[8:]
+    out["wrong_crc"] = join_member(h, tables, runs, crc=h["crc"] ^ 1)
+    _CRAFTED = (raw, good, out)
+    return _CRAFTED
+
+
+def worst_case_raw() -> bytes:
+    """100 segments of zeros, one segment that holds only the 255 other symbols, 3 segments of zeros: under order-0 stride 1 every symbol
+    of that segment has frequency 1 (12 bits each), the longest run a segment of 2048 bytes can get"""
+    z = np.zeros(SEG, dtype=np.uint8)
+    rare = ((np.arange(SEG) % 255) + 1).astype(np.uint8)
+    return np.concatenate([np.tile(z, 100), rare, np.tile(z, 3)]).tobytes()
+
+
+def exact_segment(seg_log2: int) -> bytes:
+    """exactly one segment of 2^seg_log2 bytes drawn from 7 symbols"""
+    return np.random.default_rng(4400 + seg_log2).integers(0, 7, size=1 << seg_log2, dtype=np.uint8).tobytes()
+
+
+def all_frequency_1_member(seg_log2: int = 15):
+    """(raw, member): one segment of 2^seg_log2 bytes, every one a symbol of frequency 1 under the order-0 table the member carries
+    (symbol 0, which does not occur, holds the rest): 12 bits per symbol, a run of 1.5 * 2^seg_log2 + 4 bytes"""
+    import rans_reference as rr
+    raw = ((np.arange(1 << seg_log2) % 255) + 1).astype(np.uint8).tobytes()
+    freq = np.ones((1, 1, 256), dtype=np.int64)
+    freq[0, 0, 0] = 4096 - 255
+    return raw, rr.ref_encode(raw, 1, 1, seg_log2=seg_log2, freq=freq)
+
+
+def words_bytes(n: int, seed: int = 31) -> bytes:
+    """n bytes of 32-bit little-endian words like words_u32: the four byte positions have four different distributions"""
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 300, size=n // 4 + 1).astype("<u4") * 7).view(np.uint8)[:n].tobytes()
+
+
+_REF_MEMBERS = {}
+
+
+def ref_member(raw: bytes, model: int, stride: int, seg_log2: int = 11) -> bytes:
+    """rans_reference.ref_encode, kept: the Python coder takes about a second per megabyte and several tests want the same members"""
+    import rans_reference as rr
+    key = (raw, model, stride, seg_log2)
+    if key not in _REF_MEMBERS:
+        _REF_MEMBERS[key] = rr.ref_encode(raw, model, stride, seg_log2=seg_log2)
+    return _REF_MEMBERS[key]

@@ -197,3 +197,71 @@ def test_the_symbols_are_exported():
     assert {"mcom_rans_bound", "mcom_rans_encode", "mcom_rans_decode"} <= set(minicom_amd.ABI_SYMBOLS)
     assert {"mcomh_rans_encode", "mcomh_rans_decode", "mcomh_entropy_pack_file", "mcomh_entropy_unpack_file"} <= set(pipeline.HOST_ABI_SYMBOLS)
     assert "rans" in __import__("minicom_amd.container", fromlist=["CODECS"]).CODECS
+
+
+# ---- the host twin against the independent reference (tests/rans_reference.py, written from DESIGN 3.6) --------------------------------
+def test_host_encode_equals_reference_encode():
+    """every synthetic member x every forced (model, stride), and the default choice under the (model, stride) its header names: the
+    host twin's bytes are the reference's, whose tables come from its own counts and its own normalisation"""
+    from minicom_amd import pipeline
+    for name, raw in ec.synthetic_members().items():
+        for model, stride in ec.MODELS:
+            assert pipeline.rans_encode(raw, model=model, stride=stride) == ec.ref_member(raw, model, stride), (name, model, stride)
+        member = pipeline.rans_encode(raw)
+        assert member == ec.ref_member(raw, member[5], member[6]), (name, "default", member[5], member[6])
+
+
+@pytest.mark.parametrize("seg_log2", [8, 9, 10, 12, 15])
+def test_host_decodes_reference_members_at_other_segment_sizes(seg_log2):
+    """the encoders write segments of 2^11 bytes only; the decoder takes 2^8 .. 2^15.  Reference members of the six coded models at the
+    other sizes (contexts cut at THAT segment size) decode on the host, and with the reference's own decoder"""
+    from minicom_amd import pipeline
+    import rans_reference as rr
+    syn = ec.synthetic_members()
+    inputs = {k: syn[k] for k in ("one_byte", "segment_plus_1", "three_segments_minus_1", "words_u32", "skewed_4_symbols")}
+    inputs["exact_segment"] = ec.exact_segment(seg_log2)
+    for name, raw in inputs.items():
+        for model, stride in ec.CODED_MODELS:
+            member = rr.ref_encode(raw, model, stride, seg_log2=seg_log2)
+            assert member[7] == seg_log2
+            assert pipeline.rans_decode(member) == raw, (name, model, stride)
+            assert rr.ref_decode(member) == raw, (name, model, stride)
+
+
+def test_one_crafted_member_per_refusal_rule():
+    """a valid three-segment member of the reference, then one member per rule of DESIGN 3.6 with that rule the first thing wrong: the
+    host twin and the reference's decoder accept the first and refuse every other one"""
+    from minicom_amd import pipeline
+    from minicom_amd.hip import McomError
+    import rans_reference as rr
+    raw, good, crafted = ec.crafted_refusals()
+    assert pipeline.rans_decode(good) == raw and rr.ref_decode(good) == raw
+    assert len(crafted) == 12
+    want_rule = {"length_moved_to_neighbour": ("exhausted", "end"), "run_of_length_3": ("run<4",), "state_2^23-1": ("state",), "state_2^31": ("state",),
+                 "byte_appended_to_run": ("end",), "table_row_emptied": ("slot",), "table_row_sums_to_4095": ("tables",), "wrong_crc": ("crc",)}
+    for label, bad in crafted.items():
+        with pytest.raises(rr.RansRefused) as e:
+            rr.ref_decode(bad)
+        assert e.value.rule in want_rule.get(label, ("header",)), (label, e.value.rule)         # refused for the reason it was made for
+        if not label.startswith("header"):
+            rr.parse_header(bad)
+        with pytest.raises(McomError):
+            pipeline.rans_decode(bad, cap=len(raw))
+
+
+def test_worst_case_run_room():
+    """a segment made only of symbols of frequency 1 (12 bits each) costs the longest run a 2048-byte segment can have: it stays within
+    the room the encoders give a run, run_cap(2048) = 3080 bytes less the 4 the state takes at the end, and the member decodes"""
+    from minicom_amd import pipeline
+    import rans_reference as rr
+    raw = ec.worst_case_raw()
+    member = pipeline.rans_encode(raw, model=1, stride=1)
+    h, freq = ec.parse_member(member)
+    assert (h["model"], h["stride"], h["n_seg"]) == (1, 1, 104)
+    assert (freq[0, 0, 1:] == 1).all() and freq[0, 0, 0] == 4096 - 255
+    _, _, runs = ec.split_member(member)
+    longest = max(len(r) for r in runs)
+    assert longest == len(runs[100]) and longest > 2048 * 12 // 8, longest          # the rare segment, and it does cost 12 bits a symbol
+    assert longest <= rr.run_cap(2048) - 4 and rr.run_cap(2048) == 3080, longest
+    assert pipeline.rans_decode(member) == raw
+    assert rr.ref_decode(member) == raw

@@ -1,5 +1,8 @@
 """The built-in entropy stage on the GPU (csrc/entropy.hip) against its host twin: identical bytes, cross
-decoding, the same hostile members refused, and the command line end to end with -G."""
+decoding, the same hostile members refused, and the command line end to end with -G.  Then against the independent reference of
+tests/rans_reference.py: the exact histogram counts and per-segment CRCs (test hooks of include/mcom_test.h), the encoder's bytes, the
+decoder at the segment sizes no encoder writes, pointers that are not 16-byte aligned, the longest possible run and one crafted member
+per refusal rule."""
 import gzip
 import os
 import subprocess
@@ -132,3 +135,145 @@ def test_minicom_G_end_to_end(golden_dir, tmp_path, mode, tag, suffix):
         else:
             got = (tmp_path / (base + "_dec.reads")).read_bytes().split(b"\n")[:-1]
             assert (got == rows if mode == "p" else sorted(got) == sorted(rows)), flags
+
+
+# ---- the device against the independent reference (tests/rans_reference.py) --------------------------------------------------------------
+SMALL_LENGTHS = (1, 15, 16, 17, 2047, 2048, 2049, 2063, 2064, 2065, 3 * 2048 - 1)
+
+
+def _dev_at(b, off):
+    """the bytes on the device, `off` bytes behind a 16-byte aligned address: a slice of a larger tensor, as the container passes"""
+    import torch
+    a = b if isinstance(b, np.ndarray) else np.frombuffer(b, dtype=np.uint8)
+    buf = torch.empty(off + a.size + 32, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    t = buf[off:off + a.size]
+    t.copy_(torch.from_numpy(a.copy()))
+    assert t.data_ptr() % 16 == off % 16 and t.is_contiguous()
+    return t
+
+
+def _room_at(n, off):
+    import torch
+    buf = torch.empty(off + n + 32, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    return buf[off:off + n]
+
+
+def _seven(n, seed=5):
+    return np.random.default_rng(seed).integers(0, 7, size=n, dtype=np.uint8)
+
+
+def _check_hist(ctx, raw, offsets, label):
+    import torch
+    import rans_reference as rr
+    o0, o1 = (torch.from_numpy(a).cuda() for a in rr.ref_hist(raw))
+    for off in offsets:
+        g0, g1 = ctx.rans_test_hist(_dev_at(raw, off))
+        assert torch.equal(g0, o0), (label, off, "order-0", int((g0 != o0).sum()))
+        assert torch.equal(g1, o1), (label, off, "order-1", int((g1 != o1).sum()))
+
+
+def test_histogram_counts_equal_the_reference(ctx):
+    """k_rans_hist, launched as the encoder launches it, against numpy: every one of the 4 x 256 + 7 x 65536 counts, at lengths around a
+    16-byte chunk and a segment, bytes of 7 symbols (contexts collide) and 32-bit words, the member 0, 1, 4 and 15 bytes behind an
+    aligned address.  (A count above 2^32 -- the reason the counters are 64-bit -- takes a member of more than 4 GB of one
+    (context, symbol): out of reach of a test of seconds.)"""
+    for n in SMALL_LENGTHS:
+        for label, raw in (("seven", _seven(n)), ("words", np.frombuffer(ec.words_bytes(n), dtype=np.uint8))):
+            _check_hist(ctx, raw, (0, 1, 4, 15), (label, n))
+
+
+@pytest.mark.parametrize("content", ["seven", "words", "one_value"])
+def test_histogram_counts_beyond_the_grid_cap(ctx, content):
+    """more 16-byte chunks than 8 workgroups per CU hold at once, so that the grid-stride loop goes round more than once (~9 MB); also
+    all one value: one cell per plane takes every increment"""
+    import torch
+    n = torch.cuda.get_device_properties(0).multi_processor_count * 8 * 4096 + 4096 + 5
+    raw = _seven(n) if content == "seven" else np.frombuffer(ec.words_bytes(n), dtype=np.uint8) if content == "words" else np.full(n, 0xA5, dtype=np.uint8)
+    _check_hist(ctx, raw, (0, 1), (content, n))
+
+
+@pytest.mark.parametrize("seg_log2", [8, 11, 15])
+def test_segment_crcs_equal_zlib(ctx, seg_log2):
+    """k_rans_crc, launched as the codec launches it: the CRC-32 of every segment (the last one short) is zlib's"""
+    import zlib
+    for n in SMALL_LENGTHS + ((257 << 8) + 3,):
+        raw = ec.words_bytes(n, seed=n)
+        want = [zlib.crc32(raw[a:a + (1 << seg_log2)]) for a in range(0, n, 1 << seg_log2)]
+        for off in (0, 1):
+            got = ctx.rans_test_seg_crc(_dev_at(raw, off), seg_log2).cpu().tolist()
+            assert got == want, (n, off)
+
+
+def test_device_encode_equals_reference_encode(ctx):
+    """every synthetic member x the six coded models: the device's bytes are the reference's -- the first comparison of the device with
+    something that is not its twin.  Then with the input 1 and 15 bytes behind an aligned address and the member written 1 byte behind
+    one (the byte-wise loads of the histogram, the CRC and the coder)"""
+    syn = ec.synthetic_members()
+    for name, raw in syn.items():
+        d_raw = _dev(raw)
+        for model, stride in ec.CODED_MODELS:
+            assert _host(ctx.rans_encode(d_raw, model=model, stride=stride)) == ec.ref_member(raw, model, stride), (name, model, stride)
+    bound = ctx.lib.mcom_rans_bound
+    for name in ("skewed_4_symbols", "three_segments_minus_1", "words_u32"):
+        raw = syn[name]
+        for off in (1, 15):
+            d_raw = _dev_at(raw, off)
+            for model, stride in ec.CODED_MODELS:
+                got = ctx.rans_encode(d_raw, model=model, stride=stride, out=_room_at(int(bound(len(raw))), 1))
+                assert _host(got) == ec.ref_member(raw, model, stride), (name, off, model, stride)
+
+
+OTHER_SEG_LENGTHS = {8: [(s << 8) + d for s in (63, 64, 65, 256, 257) for d in (-1, 0, 1)],          # a wave and a workgroup of segments, +- a byte
+                     9: [(64 << 9) - 1, 64 << 9, (64 << 9) + 1, (65 << 9) + 17],
+                     12: [1 << 12, (2 << 12) - 1, (5 << 12) + 33],
+                     15: [1 << 15, (2 << 15) - 1]}
+
+
+def _decode_both_ways(ctx, member, raw, label):
+    assert _host(ctx.rans_decode(_dev(member))) == raw, (label, "aligned")
+    got = ctx.rans_decode(_dev_at(member, 3), out=_room_at(len(raw), 5))
+    assert got.data_ptr() % 16 == 5 and _host(got) == raw, (label, "member + 3, output + 5")
+
+
+@pytest.mark.parametrize("model,stride", ec.CODED_MODELS)
+@pytest.mark.parametrize("seg_log2", [8, 9, 12, 15])
+def test_device_decodes_reference_members_at_other_segment_sizes(ctx, seg_log2, model, stride):
+    """no encoder writes segments other than 2^11 bytes, so the decoder's rounds, lengths and store offsets for 2^8 .. 2^15 are only
+    reached by members of the reference: lengths that cross a wave (64) and a workgroup (256) of segments, each decoded with member and
+    output aligned and with the member 3, the output 5 bytes behind an aligned address (the byte-wise stores)"""
+    for n in OTHER_SEG_LENGTHS[seg_log2]:
+        raw = ec.words_bytes(n, seed=seg_log2)
+        _decode_both_ways(ctx, ec.ref_member(raw, model, stride, seg_log2), raw, (seg_log2, model, stride, n))
+
+
+def test_device_decodes_the_longest_run_a_u16_length_holds(ctx):
+    """one segment of 2^15 symbols of frequency 1: a run of 49156 bytes, close to the top of the u16 length"""
+    raw, member = ec.all_frequency_1_member(15)
+    _, _, runs = ec.split_member(member)
+    assert len(runs) == 1 and len(runs[0]) == 49156
+    _decode_both_ways(ctx, member, raw, "frequency 1")
+
+
+def test_worst_case_run_room_on_the_device(ctx):
+    """the member of test_entropy.test_worst_case_run_room: the encoder's scratch run is filled to 3076 of 3080 bytes without raising its
+    flag, the bytes are the host twin's, and the member decodes on the device"""
+    from minicom_amd import pipeline
+    raw = ec.worst_case_raw()
+    host = pipeline.rans_encode(raw, model=1, stride=1)
+    dev = ctx.rans_encode(_dev(raw), model=1, stride=1)
+    assert _host(dev) == host
+    assert _host(ctx.rans_decode(dev)) == raw
+
+
+def test_crafted_refusals_on_the_device(ctx):
+    """one member per refusal rule (entropy_cases.crafted_refusals; the host twin and the reference refuse them in test_entropy.py): the
+    device raises for each and decodes the member they were made from"""
+    from minicom_amd.hip import McomError
+    raw, good, crafted = ec.crafted_refusals()
+    assert _host(ctx.rans_decode(_dev(good))) == raw
+    for label, bad in crafted.items():
+        with pytest.raises(McomError):
+            ctx.rans_decode(_dev(bad), cap=len(raw))
+            pytest.fail("accepted: " + label)
