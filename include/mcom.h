@@ -695,6 +695,32 @@ typedef struct {
 int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
                       uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag);
 
+/* ---- verification: are two tables of reads in HBM the same reads?  (csrc/verify.hip) ----------
+ * A table: n rows (below 2^32) of L characters (1 .. 256), `pitch` >= L bytes apart, at ANY address -- the ingested reads have
+ * pitch L, the decoder's file image pitch L + 1.  A record is row i, or, when d_mates is given (on both sides), row i followed by
+ * row i of d_mates (same pitch): compared as one string of 2 L bytes.  n = 0 is legal on either side.  The kernels read nothing
+ * outside [d_rows, d_rows + (n - 1) pitch + L) (and the same range of d_mates).  Both calls are synchronous.
+ *   mcom_verify_ordered   record i against record i: differing = positions below min(n_a, n_b) whose records differ, first_diff =
+ *                         the smallest of them (~0: none); identical = equal counts and no differing position
+ *   mcom_verify_multiset  exact equality of the two multisets of records, with multiplicities: missing = records of a that b does
+ *                         not give back, extra = the converse, each with up to 8 example record indices (the smallest ones,
+ *                         ascending; two calls on the same inputs give the same report); exact_runs = runs of equal hashes whose
+ *                         records had to be settled in full on the host (hash collisions: 0 on real data).  Never "equal up to a
+ *                         collision".  Device memory taken besides the tables: at most mcom_verify_room(n_a, n_b) bytes.        */
+typedef struct { const uint8_t *d_rows; const uint8_t *d_mates; uint64_t pitch; uint64_t n; } mcom_verify_table;
+typedef struct {
+	uint64_t n_a, n_b;
+	uint64_t missing, extra;                     /* multiset */
+	uint64_t differing, first_diff;              /* ordered */
+	uint64_t exact_runs;
+	uint64_t missing_ex[8], extra_ex[8];         /* unused entries ~0 */
+	uint32_t n_missing_ex, n_extra_ex;
+	int identical;
+} mcom_verify_report;
+uint64_t mcom_verify_room(uint64_t n_a, uint64_t n_b);
+int mcom_verify_ordered(mcom_ctx *ctx, const mcom_verify_table *a, const mcom_verify_table *b, int L, mcom_verify_report *rep);
+int mcom_verify_multiset(mcom_ctx *ctx, const mcom_verify_table *a, const mcom_verify_table *b, int L, mcom_verify_report *rep);
+
 /* ---- the built-in entropy stage: `.rans` members (csrc/entropy.hip; format and host twin: DESIGN.md section 3.6, include/mcom_host.h) ----
  * A static rANS coder, 12-bit frequencies, one model per member: stored, order-0 or order-1 (context = the previous byte of the same
  * plane), each over byte planes of stride 1, 2 or 4 (byte i belongs to plane i mod stride).  The member is cut into segments of 2 KiB,

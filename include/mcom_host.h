@@ -135,6 +135,30 @@ int mcomh_decompress_pe_gpu(const char *folder, const char *out_path1, const cha
 /* Where the last of those calls spent its time, in ms: [0] reading the files, [1] upload + indices + destinations, [2] decode (wall),
  * [3] decode kernels (device events), [4] download + write, [5] of that inside fwrite, [6] the whole call, [7] unused.              */
 void mcomh_decompress_gpu_times(double *ms8);
+/* Does the archive in `folder` give back exactly the reads of the FASTQ file(s)?  Answered on GPU `device` without writing a read
+ * (DESIGN.md section 3.7): the file(s) go up as mcomh_fastq_to_device / mcomh_fastq_pair_to_device put them, the archive's rows are
+ * rebuilt as by mcomh_decompress*_gpu (the same code up to the rows in HBM: the same archives are refused, by the same checks, before
+ * anything is compared) and the two tables are compared there (mcom_verify_multiset / mcom_verify_ordered of include/mcom.h).
+ * mode 0: the default archive, the reads as a multiset (the decoder returns them in another order); 1: -p, line i against line i;
+ * 2: paired end (fastq2 = the mates' file, NULL in the other modes), the pairs as a multiset.
+ * 0: the comparison was made, *rep says how it went (a different read COUNT is a verdict, not an error).  -1 with a message on stderr:
+ * bad arguments, an archive the decoders refuse, a FASTQ that cannot be read or whose reads are not the archive's length, no such GPU
+ * (there is no host route), or no room on the card for the two tables, the records and their sort.
+ * What it proves: pipeline, stream writer, entropy stage and decoder -- against the reads as this project's FASTQ reader delivers them;
+ * it does not prove the parser.                                                                                                      */
+typedef struct {
+	int identical, mode;
+	uint64_t n_input, n_archive;                /* reads; mode 2: pairs */
+	uint64_t missing, extra;                    /* modes 0, 2: reads (pairs) of the input that the archive does not give back, and the converse */
+	uint64_t differing, first_diff;             /* mode 1: lines below min(n_input, n_archive) that differ, the first of them (~0: none) */
+	uint64_t exact_runs;                        /* runs of equal hashes settled as multisets of full records (hash collisions) */
+	uint64_t missing_ex[8], extra_ex[8];        /* up to 8 examples each: the smallest read (pair) numbers, ascending, from 0 */
+	uint32_t n_missing_ex, n_extra_ex;
+	double times_ms[8];                         /* [0] FASTQ ingest, [1] upload + indices, [2] decode, [3] compare, [4] the whole call,
+	                                               [5] reading the stream files, [6] compare by device events, [7] decode kernels by device events */
+} mcomh_verify_report;
+int mcomh_verify_gpu(const char *folder, int mode /* 0 default, 1 order, 2 paired */, const char *fastq1, const char *fastq2 /* paired only, else NULL */,
+                     int device, mcomh_verify_report *rep);
 /* both files of a pair into one device matrix, second file behind the first; MCOM_E_ARG when the counts differ      */
 int mcomh_fastq_pair_to_device(const char *path1, const char *path2, int device, int *L, size_t chunk_reads, uint8_t **d_reads, size_t *n,
                                char *err, size_t err_cap);

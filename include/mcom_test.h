@@ -53,6 +53,10 @@ int mcom_set_lookup_route(mcom_ctx *ctx, int route);
  * mcom_test_rans_seg_crc: d_crc gets one CRC-32 per segment of 2^seg_log2 bytes (8 .. 15), the last one of what is left.                */
 int mcom_test_rans_hist(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_counts);
 int mcom_test_rans_seg_crc(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t seg_log2, uint32_t *d_crc);
+/* mcom_verify_multiset keeps only the low `bits` bits of every record's hash (0 .. 63; 64 or negative = default, all of them), through
+ * the same launches: with 2 or 0 bits nearly every run of equal hashes holds unequal records, so that a thousand rows walk the path
+ * real data reaches once in 2^64 -- the run settled in full on the host.  Same verdict and counts at any width.                    */
+int mcom_set_verify_hash_bits(mcom_ctx *ctx, int bits);
 
 
 /* ---- libmcom_host.so ---- */

@@ -229,3 +229,19 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
                 raise ValueError("a paired-end archive decodes into two files")
             return decompress_pe(td, out_path, out_path2, device=device)
         return decompress(td, out_path, order=kinds["order"], device=device)
+
+
+def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int = 8, device: int = 0) -> dict:
+    """`.minicom` against the FASTQ it was made from, on GPU `device`, without writing a read: pipeline.verify's report.  The mode comes
+    from the members, as in decompress_file: a paired-end archive needs `fastq2`, a -p archive is held line against line, any other
+    one as a multiset of reads."""
+    import tempfile
+    from .hip import McomError
+    from .pipeline import verify
+    if not os.path.isfile(path):
+        raise McomError("no such archive: %s" % path)
+    with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(path)) or ".") as td:
+        kinds = unpack(path, td, threads=threads, device=device)
+        if kinds["paired"] != (fastq2 is not None):
+            raise McomError("a paired-end archive is verified against two FASTQ files, any other against one")
+        return verify(td, fastq, fastq2, order=kinds["order"], device=device)

@@ -26,6 +26,18 @@ class DecodeSrc(C.Structure):
 DECODE_F_BOUNDS, DECODE_F_LINE, DECODE_F_DUP, DECODE_F_DEST = 1, 2, 4, 8
 
 
+class VerifyTable(C.Structure):
+    """mcom_verify_table of include/mcom.h"""
+    _fields_ = [("d_rows", C.c_void_p), ("d_mates", C.c_void_p), ("pitch", C.c_uint64), ("n", C.c_uint64)]
+
+
+class VerifyReport(C.Structure):
+    """mcom_verify_report of include/mcom.h"""
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("missing", C.c_uint64), ("extra", C.c_uint64), ("differing", C.c_uint64),
+                ("first_diff", C.c_uint64), ("exact_runs", C.c_uint64), ("missing_ex", C.c_uint64 * 8), ("extra_ex", C.c_uint64 * 8),
+                ("n_missing_ex", C.c_uint32), ("n_extra_ex", C.c_uint32), ("identical", C.c_int)]
+
+
 def rans_hint(model: int, stride: int = 1) -> int:
     """MCOM_RANS_HINT of include/mcom.h"""
     return 0x100 | (model << 4) | stride
@@ -151,6 +163,10 @@ def load_library():
     L.mcom_decode_pe_dest.restype = i32; L.mcom_decode_pe_dest.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, u64, vp, C.POINTER(u64), vp]
     L.mcom_decode_check_lines.restype = i32; L.mcom_decode_check_lines.argtypes = [vp, vp, u64, vp, u64, i32, i32, vp]
     L.mcom_decode_reads.restype = i32; L.mcom_decode_reads.argtypes = [vp, C.POINTER(DecodeSrc), u64, i32, vp, u64, vp, u64, vp, vp]
+    L.mcom_verify_room.restype = u64; L.mcom_verify_room.argtypes = [u64, u64]
+    L.mcom_verify_ordered.restype = i32; L.mcom_verify_ordered.argtypes = [vp, C.POINTER(VerifyTable), C.POINTER(VerifyTable), i32, C.POINTER(VerifyReport)]
+    L.mcom_verify_multiset.restype = i32; L.mcom_verify_multiset.argtypes = [vp, C.POINTER(VerifyTable), C.POINTER(VerifyTable), i32, C.POINTER(VerifyReport)]
+    L.mcom_set_verify_hash_bits.restype = i32; L.mcom_set_verify_hash_bits.argtypes = [vp, i32]
     L.mcom_rans_bound.restype = u64; L.mcom_rans_bound.argtypes = [u64]
     L.mcom_rans_encode.restype = i32; L.mcom_rans_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
     L.mcom_rans_decode.restype = i32; L.mcom_rans_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -920,6 +936,41 @@ class Context:
         got = C.c_uint64()
         self._check(self.lib.mcom_rans_decode(self._h, self._p(member, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
         return out[:got.value]
+
+    # -- verification (csrc/verify.hip)
+    def _verify_table(self, t, L: int):
+        """(rows, pitch, n) or (rows, pitch, n, mates): uint8 device tensors whose first byte is row 0 (a slice at any offset of a
+        larger buffer will do), rows `pitch` bytes apart; a tensor may be None when n == 0."""
+        torch = _torch()
+        rows, pitch, n = t[0], int(t[1]), int(t[2])
+        mates = t[3] if len(t) > 3 else None
+        for x in (rows, mates):
+            if x is not None and n and (x.dtype != torch.uint8 or x.numel() < (n - 1) * pitch + L):
+                raise McomError("a table must be a uint8 tensor that holds (n - 1) * pitch + L bytes from row 0 on")
+        return VerifyTable(self._p(rows).value if n else None, self._p(mates).value if (mates is not None and n) else None, pitch, n)
+
+    @staticmethod
+    def _verify_dict(r: VerifyReport) -> dict:
+        return {"identical": bool(r.identical), "n_a": int(r.n_a), "n_b": int(r.n_b), "missing": int(r.missing), "extra": int(r.extra),
+                "differing": int(r.differing), "first_diff": None if r.first_diff == 2 ** 64 - 1 else int(r.first_diff),
+                "exact_runs": int(r.exact_runs), "missing_examples": [int(v) for v in r.missing_ex[: r.n_missing_ex]],
+                "extra_examples": [int(v) for v in r.extra_ex[: r.n_extra_ex]]}
+
+    def verify_multiset(self, a, b, L: int) -> dict:
+        """mcom_verify_multiset: are the records of table a and table b the same multiset?  a, b: see _verify_table."""
+        ta, tb, r = self._verify_table(a, L), self._verify_table(b, L), VerifyReport()
+        self._check(self.lib.mcom_verify_multiset(self._h, C.byref(ta), C.byref(tb), L, C.byref(r)))
+        return self._verify_dict(r)
+
+    def verify_ordered(self, a, b, L: int) -> dict:
+        """mcom_verify_ordered: record i of table a against record i of table b."""
+        ta, tb, r = self._verify_table(a, L), self._verify_table(b, L), VerifyReport()
+        self._check(self.lib.mcom_verify_ordered(self._h, C.byref(ta), C.byref(tb), L, C.byref(r)))
+        return self._verify_dict(r)
+
+    def set_verify_hash_bits(self, bits: int):
+        """Test hook (mcom_set_verify_hash_bits): mcom_verify_multiset keeps the low `bits` bits of its hashes (64 or negative: all)."""
+        self._check(self.lib.mcom_set_verify_hash_bits(self._h, int(bits)))
 
     def rans_test_hist(self, raw):
         """Test hook (mcom_test_rans_hist): the counts of k_rans_hist for the uint8 device tensor `raw` (at least one byte), launched as

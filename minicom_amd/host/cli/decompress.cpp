@@ -4,15 +4,53 @@
 // concatenate (minicom:385-399), this one writes the final file(s) itself.
 // decompress --gpu DIR OUT pe order nthr [OUT2]: the same with the reads rebuilt on GPU 0 (mcomh_decompress*_gpu): the same
 // output files; an error, not the host decoder, when there is no GPU.
+// decompress --verify DIR IN.fastq pe order nthr [IN_2.fastq]: no output file; the archive's reads are rebuilt on GPU 0 and compared there
+// with the reads of the FASTQ file(s) (mcomh_verify_gpu).  Exit status 0 identical, 2 different, 1 refused or error.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
 
+static void examples(const char *what, const uint64_t *ex, uint32_t n)
+{
+	if (!n) return;
+	printf("  %s, for example", what);
+	for (uint32_t q = 0; q < n; ++q) printf(" %llu", (unsigned long long)ex[q]);
+	printf("\n");
+}
+
+static int verify(int argc, char **argv)
+{
+	if (argc < 6) { fprintf(stderr, "usage: decompress --verify DIR IN.fastq pe(true|false) order(true|false) nthr [IN_2.fastq]\n"); return 1; }
+	const bool pe = !strcmp(argv[3], "true") || !strcmp(argv[3], "1"), order = !strcmp(argv[4], "true") || !strcmp(argv[4], "1");
+	if (pe && argc < 7) { fprintf(stderr, "decompress: paired-end archives need IN_2.fastq\n"); return 1; }
+	mcomh_verify_report r;
+	if (mcomh_verify_gpu(argv[1], pe ? 2 : order ? 1 : 0, argv[2], pe ? argv[6] : nullptr, 0, &r)) {
+		fprintf(stderr, "decompress: %s could not be verified against %s\n", argv[1], argv[2]);
+		return 1;
+	}
+	const char *unit = pe ? "pairs" : "reads";
+	if (r.identical) { printf("verified: %llu %s identical\n", (unsigned long long)r.n_input, unit); return 0; }
+	printf("DIFFERENT: the FASTQ holds %llu %s, the archive %llu\n", (unsigned long long)r.n_input, unit, (unsigned long long)r.n_archive);
+	if (r.mode == 1) {
+		printf("  %llu lines differ", (unsigned long long)r.differing);
+		if (r.differing) printf(", the first one is line %llu (from 0)", (unsigned long long)r.first_diff);
+		printf("\n");
+	} else {
+		printf("  %llu %s of the FASTQ are missing from the archive, %llu %s of the archive are not in the FASTQ\n",
+		       (unsigned long long)r.missing, unit, (unsigned long long)r.extra, unit);
+		examples("missing (numbered from 0 in the FASTQ)", r.missing_ex, r.n_missing_ex);
+		examples("extra (numbered from 0 in the archive's output)", r.extra_ex, r.n_extra_ex);
+		if (r.exact_runs) printf("  %llu runs of equal hashes were settled record by record\n", (unsigned long long)r.exact_runs);
+	}
+	return 2;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc > 1 && !strcmp(argv[1], "--verify")) return verify(argc - 1, argv + 1);
 	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
 	if (gpu) { --argc; ++argv; }
-	if (argc < 6) { fprintf(stderr, "usage: decompress [--gpu] DIR OUT pe(true|false) order(true|false) nthr [OUT2]\n"); return 1; }
+	if (argc < 6) { fprintf(stderr, "usage: decompress [--gpu] DIR OUT pe(true|false) order(true|false) nthr [OUT2]\n       decompress --verify DIR IN.fastq pe order nthr [IN_2.fastq]\n"); return 1; }
 	const bool pe = !strcmp(argv[3], "true") || !strcmp(argv[3], "1"), order = !strcmp(argv[4], "true") || !strcmp(argv[4], "1");
 	uint64_t n = 0;
 	int rc;

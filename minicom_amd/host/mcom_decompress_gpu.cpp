@@ -7,6 +7,8 @@
 //      word the kernels raise are compared on the host.  An archive that fails here is refused before anything is decoded.
 //   B. one mcom_decode_reads per list / stream set writes its reads into a table of rows in HBM (L characters and a newline each:
 //      the file image); the table comes back through two page-locked buffers, the copy of piece i + 1 under the write of piece i.
+//   C. what becomes of the rows is the caller's tail: the three decoders write the file(s) (write_files); mcomh_verify_gpu compares the table,
+//      still in HBM, with the reads of the FASTQ file(s) (compare_rows over csrc/verify.hip) and writes nothing.
 // The only serial step is the chain of contig headers in beg_pos.bin (mcom_decode_walk_headers: four bytes read per contig).
 // No output file is left behind by a refused archive; there is no fall back to the host decoder.
 #include "../../include/mcom_host.h"
@@ -16,6 +18,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -102,7 +105,10 @@ uint32_t read_flag(Arena &A, const uint32_t *d_flag)
 	return f;
 }
 
-int run(Mode mode, const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_out, int device)
+// Phases A and B for the three decoders and for the verifier alike; `tail` gets the rows while they are still in HBM: 0 = done, else the call fails
+using Tail = std::function<int(Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L)>;
+
+int run(Mode mode, const char *folder, int device, const Tail &tail)
 {
 	const double t_begin = now_ms();
 	memset(g_times, 0, sizeof(g_times));
@@ -319,33 +325,8 @@ int run(Mode mode, const char *folder, const char *out_path1, const char *out_pa
 		g_times[2] = now_ms() - t0;
 		if (fl) throw Refuse{"a read cannot be decoded or placed"};
 
-		// ---- the file(s): copy of piece i + 1 under the write of piece i
-		t0 = now_ms();
-		uint8_t *pin[2] = {nullptr, nullptr};
-		for (int b = 0; b < 2; ++b) { void *p = nullptr; if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"}; A.pinned.push_back(p); pin[b] = (uint8_t*)p; }
-		const int n_files = mode == PE ? 2 : 1;
-		const char *paths[2] = {out_path1, out_path2};
-		bool wrote_ok = true;
-		for (int fi = 0; fi < n_files && wrote_ok; ++fi) {
-			const uint64_t first = mode == PE ? (uint64_t)fi * (uint64_t)half * row : 0, bytes = mode == PE ? (uint64_t)half * row : table_bytes;
-			FILE *out = fopen(paths[fi], "wb");
-			if (!out) { wrote_ok = false; break; }
-			const uint64_t pieces = (bytes + PIECE_BYTES - 1) / PIECE_BYTES;
-			auto piece_bytes = [&](uint64_t i) { const uint64_t at = i * PIECE_BYTES; return (size_t)(bytes - at < PIECE_BYTES ? bytes - at : PIECE_BYTES); };
-			if (pieces && hipMemcpyAsync(pin[0], table + first, piece_bytes(0), hipMemcpyDeviceToHost, nullptr) != hipSuccess) wrote_ok = false;
-			for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
-				if (hipStreamSynchronize(nullptr) != hipSuccess) { wrote_ok = false; break; }
-				if (i + 1 < pieces && hipMemcpyAsync(pin[(i + 1) & 1], table + first + (i + 1) * PIECE_BYTES, piece_bytes(i + 1), hipMemcpyDeviceToHost, nullptr) != hipSuccess) { wrote_ok = false; break; }
-				const double tw = now_ms();
-				if (fwrite(pin[i & 1], 1, piece_bytes(i), out) != piece_bytes(i)) wrote_ok = false;
-				g_times[5] += now_ms() - tw;
-			}
-			(void)hipStreamSynchronize(nullptr);
-			if (fclose(out) != 0) wrote_ok = false;
-		}
-		if (!wrote_ok) { for (int fi = 0; fi < n_files; ++fi) remove(paths[fi]); return -1; }
-		g_times[4] = now_ms() - t0;
-		if (n_out) *n_out = mode == PE ? (uint64_t)half : n_rows;
+		// ---- C. what becomes of the rows: the file(s), or the comparison of mcomh_verify_gpu
+		if (tail(A, table, n_rows, (uint64_t)half, L)) return -1;
 	} catch (const Refuse &r) {
 		fprintf(stderr, "minicom gpu decoder: %s refused: %s\n", folder, r.why);
 		return -1;
@@ -354,10 +335,104 @@ int run(Mode mode, const char *folder, const char *out_path1, const char *out_pa
 	return 0;
 }
 
+// the file(s): copy of piece i + 1 under the write of piece i
+int write_files(Mode mode, Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L, const char *out_path1, const char *out_path2, uint64_t *n_out)
+{
+	const uint64_t row = (uint64_t)L + 1, table_bytes = n_rows * row;
+	const double t0 = now_ms();
+	uint8_t *pin[2] = {nullptr, nullptr};
+	for (int b = 0; b < 2; ++b) { void *p = nullptr; if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"}; A.pinned.push_back(p); pin[b] = (uint8_t*)p; }
+	const int n_files = mode == PE ? 2 : 1;
+	const char *paths[2] = {out_path1, out_path2};
+	bool wrote_ok = true;
+	for (int fi = 0; fi < n_files && wrote_ok; ++fi) {
+		const uint64_t first = mode == PE ? (uint64_t)fi * (uint64_t)half * row : 0, bytes = mode == PE ? (uint64_t)half * row : table_bytes;
+		FILE *out = fopen(paths[fi], "wb");
+		if (!out) { wrote_ok = false; break; }
+		const uint64_t pieces = (bytes + PIECE_BYTES - 1) / PIECE_BYTES;
+		auto piece_bytes = [&](uint64_t i) { const uint64_t at = i * PIECE_BYTES; return (size_t)(bytes - at < PIECE_BYTES ? bytes - at : PIECE_BYTES); };
+		if (pieces && hipMemcpyAsync(pin[0], table + first, piece_bytes(0), hipMemcpyDeviceToHost, nullptr) != hipSuccess) wrote_ok = false;
+		for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
+			if (hipStreamSynchronize(nullptr) != hipSuccess) { wrote_ok = false; break; }
+			if (i + 1 < pieces && hipMemcpyAsync(pin[(i + 1) & 1], table + first + (i + 1) * PIECE_BYTES, piece_bytes(i + 1), hipMemcpyDeviceToHost, nullptr) != hipSuccess) { wrote_ok = false; break; }
+			const double tw = now_ms();
+			if (fwrite(pin[i & 1], 1, piece_bytes(i), out) != piece_bytes(i)) wrote_ok = false;
+			g_times[5] += now_ms() - tw;
+		}
+		(void)hipStreamSynchronize(nullptr);
+		if (fclose(out) != 0) wrote_ok = false;
+	}
+	if (!wrote_ok) { for (int fi = 0; fi < n_files; ++fi) remove(paths[fi]); return -1; }
+	g_times[4] = now_ms() - t0;
+	if (n_out) *n_out = mode == PE ? (uint64_t)half : n_rows;
+	return 0;
+}
+
 int guarded(Mode mode, const char *folder, const char *o1, const char *o2, uint64_t *n, int device)
 {
 	if (!folder || !o1 || (mode == PE && !o2)) return -1;
-	try { return run(mode, folder, o1, o2, n, device); } catch (...) { return -1; }   // no C++ exception crosses the C boundary
+	try {
+		return run(mode, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L) { return write_files(mode, A, table, n_rows, half, L, o1, o2, n); });
+	} catch (...) { return -1; }   // no C++ exception crosses the C boundary
+}
+
+// ---- verification: the rows of phase B against the reads of the FASTQ file(s), both in HBM (csrc/verify.hip) ----
+// Side a is the input, side b the archive: `missing` are reads of the input that the archive does not give back.
+int compare_rows(Mode mode, Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L, const uint8_t *d_in, uint64_t n_in, int L_in, mcomh_verify_report *rep)
+{
+	if (n_in && L_in != L) { fprintf(stderr, "minicom verify: the reads of the FASTQ are %d long, those of the archive %d\n", L_in, L); return -1; }
+	mcom_verify_table a, b;
+	a.d_rows = d_in; a.pitch = (uint64_t)L; a.n = mode == PE ? n_in / 2 : n_in; a.d_mates = mode == PE ? d_in + a.n * (uint64_t)L : nullptr;
+	b.d_rows = table; b.pitch = (uint64_t)L + 1; b.n = mode == PE ? half : n_rows; b.d_mates = mode == PE ? table + half * ((uint64_t)L + 1) : nullptr;
+	if (mode != ORDER) {
+		const uint64_t room = mcom_verify_room(a.n, b.n);
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess || room > fr) {
+			fprintf(stderr, "minicom verify: the card has no room: %llu bytes for the reads of the FASTQ, %llu for the archive's rows and %llu for the records and their sort are needed, %zu of the last are free\n",
+			        (unsigned long long)(n_in * (uint64_t)L), (unsigned long long)(n_rows * ((uint64_t)L + 1)), (unsigned long long)room, fr);
+			return -1;
+		}
+	}
+	const double t0 = now_ms();
+	mcom_verify_report r;
+	(void)hipEventRecord(A.ev[0], nullptr);
+	ok(A.ctx, mode == ORDER ? mcom_verify_ordered(A.ctx, &a, &b, L, &r) : mcom_verify_multiset(A.ctx, &a, &b, L, &r));
+	(void)hipEventRecord(A.ev[1], nullptr);
+	(void)hipEventSynchronize(A.ev[1]);
+	{ float ms = 0; if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) rep->times_ms[6] = ms; }
+	rep->times_ms[3] = now_ms() - t0;
+	rep->identical = r.identical; rep->n_input = r.n_a; rep->n_archive = r.n_b;
+	rep->missing = r.missing; rep->extra = r.extra; rep->differing = r.differing; rep->first_diff = r.first_diff; rep->exact_runs = r.exact_runs;
+	rep->n_missing_ex = r.n_missing_ex; rep->n_extra_ex = r.n_extra_ex;
+	memcpy(rep->missing_ex, r.missing_ex, sizeof(r.missing_ex)); memcpy(rep->extra_ex, r.extra_ex, sizeof(r.extra_ex));
+	return 0;
+}
+
+int verify(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
+{
+	const double t_begin = now_ms();
+	{
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
+			fprintf(stderr, "minicom verify: no GPU %d (%d visible); there is no host route\n", device, n_dev);
+			return -1;
+		}
+	}
+	struct Reads { uint8_t *d = nullptr; ~Reads() { mcomh_device_free(d); } } in;
+	size_t n_in = 0; int L_in = 0;
+	char err[256] = "";
+	const int rc = mode == PE ? mcomh_fastq_pair_to_device(fastq1, fastq2, device, &L_in, 0, &in.d, &n_in, err, sizeof(err))
+	                          : mcomh_fastq_to_device(fastq1, device, &L_in, 0, &in.d, &n_in, err, sizeof(err));
+	if (rc) { fprintf(stderr, "minicom verify: cannot read %s%s%s: %s\n", fastq1, mode == PE ? " and " : "", mode == PE ? fastq2 : "", err[0] ? err : "not a FASTQ / FASTA file of reads of one length"); return -1; }
+	const double ingest = now_ms() - t_begin;
+	const int rr = run((Mode)mode, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L) {
+		return compare_rows((Mode)mode, A, table, n_rows, half, L, in.d, (uint64_t)n_in, L_in, rep);
+	});
+	if (rr) return -1;
+	rep->mode = mode;
+	rep->times_ms[0] = ingest; rep->times_ms[1] = g_times[1]; rep->times_ms[2] = g_times[2]; rep->times_ms[5] = g_times[0]; rep->times_ms[7] = g_times[3];
+	rep->times_ms[4] = now_ms() - t_begin;
+	return 0;
 }
 
 } // namespace
@@ -366,3 +441,12 @@ extern "C" int mcomh_decompress_gpu(const char *folder, const char *out_path, ui
 extern "C" int mcomh_decompress_order_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(ORDER, folder, out_path, nullptr, n_reads, device); }
 extern "C" int mcomh_decompress_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device) { return guarded(PE, folder, out_path1, out_path2, n_pairs, device); }
 extern "C" void mcomh_decompress_gpu_times(double *ms8) { if (ms8) memcpy(ms8, g_times, sizeof(g_times)); }
+extern "C" int mcomh_verify_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
+{
+	if (!folder || !fastq1 || !rep || mode < 0 || mode > 2 || (mode == PE) != (fastq2 != nullptr)) {
+		fprintf(stderr, "minicom verify: bad arguments (a folder, mode 0 default | 1 -p | 2 paired end, one FASTQ file, and the mates' file with mode 2 only)\n");
+		return -1;
+	}
+	memset(rep, 0, sizeof(*rep));
+	try { return verify(folder, mode, fastq1, fastq2, device, rep); } catch (...) { return -1; }
+}

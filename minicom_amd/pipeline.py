@@ -11,6 +11,14 @@ from .hip import McomError, load_library
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+class VerifyReport(C.Structure):
+    """mcomh_verify_report of include/mcom_host.h"""
+    _fields_ = [("identical", C.c_int), ("mode", C.c_int), ("n_input", C.c_uint64), ("n_archive", C.c_uint64), ("missing", C.c_uint64),
+                ("extra", C.c_uint64), ("differing", C.c_uint64), ("first_diff", C.c_uint64), ("exact_runs", C.c_uint64),
+                ("missing_ex", C.c_uint64 * 8), ("extra_ex", C.c_uint64 * 8), ("n_missing_ex", C.c_uint32), ("n_extra_ex", C.c_uint32),
+                ("times_ms", C.c_double * 8)]
+
+
 class Params(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("k", "e", "m", "w", "cbthr", "max_rounds", "step", "maxthr", "numdict", "host_threads", "maxsearch", "window_scan",
                                          "full_consensus", "full_sketch", "overlap_screen", "host_dump", "stream_sets", "stage2_join", "read_batches")]
@@ -56,6 +64,7 @@ def load_host_library():
     L.mcomh_decompress_order_gpu.restype = i32; L.mcomh_decompress_order_gpu.argtypes = [cp, cp, C.POINTER(C.c_uint64), i32]
     L.mcomh_decompress_pe_gpu.restype = i32; L.mcomh_decompress_pe_gpu.argtypes = [cp, cp, cp, C.POINTER(C.c_uint64), i32]
     L.mcomh_decompress_gpu_times.restype = None; L.mcomh_decompress_gpu_times.argtypes = [C.POINTER(C.c_double)]
+    L.mcomh_verify_gpu.restype = i32; L.mcomh_verify_gpu.argtypes = [cp, i32, cp, cp, i32, C.POINTER(VerifyReport)]
     L.mcomh_fastq_pair_to_device.restype = i32
     L.mcomh_fastq_pair_to_device.argtypes = [cp, cp, i32, C.POINTER(i32), sz, C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
     L.mcomh_n_contigs.restype = sz; L.mcomh_n_contigs.argtypes = [vp]
@@ -93,7 +102,7 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_list", "mcomh_stat", "mcomh_prof_enable", "mcomh_prof_read", "mcomh_prof_kernels", "mcomh_fastq_read", "mcomh_fastq_to_device",
                     "mcomh_device_free", "mcomh_cluster_dump_order", "mcomh_decompress_order",
                     "mcomh_cluster_dump_pe", "mcomh_decompress_pe", "mcomh_fastq_pair_to_device",
-                    "mcomh_decompress_gpu", "mcomh_decompress_order_gpu", "mcomh_decompress_pe_gpu", "mcomh_decompress_gpu_times",
+                    "mcomh_decompress_gpu", "mcomh_decompress_order_gpu", "mcomh_decompress_pe_gpu", "mcomh_decompress_gpu_times", "mcomh_verify_gpu",
                     "mcomh_contig_set", "mcomh_result_digest",
                     # the built-in entropy stage (host/mcom_entropy.cpp)
                     "mcomh_rans_bound", "mcomh_rans_estimate", "mcomh_rans_encode", "mcomh_rans_decode", "mcomh_entropy_pack_file",
@@ -117,6 +126,30 @@ def decompress(folder: str, out_path: str, order: bool = False, device: int | No
     if rc:
         raise McomError(f"cannot decode the stream files in {folder}" + ("" if device is None else f" on GPU {device}"))
     return int(n.value)
+
+
+def verify(folder: str, fastq: str, fastq2: str | None = None, order: bool = False, device: int = 0) -> dict:
+    """mcomh_verify_gpu: do the stream files in `folder` give back exactly the reads of `fastq` (and, for a paired-end archive, the
+    mates of `fastq2`)?  Decided on GPU `device`, nothing is written.  order=True: a -p archive, line against line; otherwise the
+    reads (pairs) as a multiset.  Returns the report; McomError when no comparison could be made (an archive the decoders refuse, an
+    unreadable FASTQ or one of another read length, no such GPU, no room on the card) -- a difference is a verdict, not an error."""
+    if fastq is None or folder is None:
+        raise McomError("verify needs a folder and a FASTQ file")
+    if order and fastq2 is not None:
+        raise McomError("-p is a single-end option: no second FASTQ file")
+    mode = 2 if fastq2 is not None else 1 if order else 0
+    r = VerifyReport()
+    rc = load_host_library().mcomh_verify_gpu(os.fsencode(folder), mode, os.fsencode(fastq), os.fsencode(fastq2) if fastq2 is not None else None,
+                                              int(device), C.byref(r))
+    if rc:
+        raise McomError(f"cannot verify the stream files in {folder} against {fastq} on GPU {device}")
+    t = r.times_ms
+    return {"identical": bool(r.identical), "mode": ("default", "order", "paired")[r.mode], "n_input": int(r.n_input), "n_archive": int(r.n_archive),
+            "missing": int(r.missing), "extra": int(r.extra), "differing": int(r.differing),
+            "first_diff": None if r.first_diff == 2 ** 64 - 1 else int(r.first_diff), "exact_runs": int(r.exact_runs),
+            "missing_examples": [int(v) for v in r.missing_ex[: r.n_missing_ex]], "extra_examples": [int(v) for v in r.extra_ex[: r.n_extra_ex]],
+            "times_ms": {"ingest": t[0], "upload_index": t[1], "decode": t[2], "compare": t[3], "total": t[4], "read_files": t[5],
+                         "compare_device": t[6], "decode_kernels": t[7]}}
 
 
 def decompress_gpu_times() -> dict:
