@@ -738,6 +738,19 @@ uint64_t mcom_rans_bound(uint64_t n);
 int mcom_rans_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, int model_hint);
 int mcom_rans_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 
+/* ---- the block-sorting coder: `.bwt` members (csrc/bwt.hip; format and host twin: DESIGN.md section 3.8, include/mcom_host.h) ----
+ * Blocks of 1 MiB: suffix ranks of all blocks at once by prefix doubling over the radix sort, the Burrows-Wheeler transform with one
+ * anchor row per 4 KiB of text, move-to-front evaluated in parallel stretches, the ranks through mcom_rans_encode; the plain `.rans`
+ * coding of the bytes is made as well and the smaller one is written.  Device pointers at any address, work on the context's stream,
+ * both calls synchronous, members below 4 GiB.  The bytes equal those of mcomh_bwt_encode; errors as for the rANS calls, and
+ * MCOM_E_OVERFLOW with a message when the card has no room for the sort records.
+ *   mcom_bwt_bound   room that is enough for n raw bytes
+ *   mcom_bwt_decode  MCOM_E_ARG for every member section 3.8 refuses -- d_out then holds nothing valid.  Untrusted input never makes a
+ *                    kernel leave its buffers (it raises a flag word and skips the access).                                         */
+uint64_t mcom_bwt_bound(uint64_t n);
+int mcom_bwt_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
+int mcom_bwt_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
+
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,
                      uint64_t first, uint64_t count, uint8_t *d_ascii, size_t pitch);

@@ -249,6 +249,23 @@ int mcomh_entropy_pack_file(const char *in_path, const char *out_path, int devic
 int mcomh_entropy_unpack_file(const char *in_path, const char *out_path, int device);
 void mcomh_entropy_times(double *ms8);
 
+/* ---- the block-sorting coder: `.bwt` members (host/mcom_bwt.cpp) ----
+ * The host twin of mcom_bwt_encode / mcom_bwt_decode (include/mcom.h): blocks of 1 MiB, Burrows-Wheeler transform with anchors every
+ * 4 KiB, move-to-front, the ranks as one embedded `.rans` member -- or the plain `.rans` coding of the bytes where that is not larger.
+ * Same bytes out as the device route, the same members refused.  Return values as for the rANS calls.
+ *   mcomh_bwt_bound    room that is enough for n raw bytes
+ *   mcomh_bwt_raw_len  the raw length a member's header states (-1: not a `.bwt` header that describes in_len bytes)
+ *   mcomh_bwt_stages   the stages of the encoder for tests and tools, any of the outputs NULL: the transformed bytes (n), the index as
+ *                      the member stores it (4 bytes per anchor) and the move-to-front ranks (n; needs bwt as well)
+ * File forms as mcomh_entropy_pack_file / _unpack_file (mcomh_entropy_times reports them too).                                      */
+uint64_t mcomh_bwt_bound(uint64_t n);
+int mcomh_bwt_encode(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int mcomh_bwt_decode(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int mcomh_bwt_raw_len(const uint8_t *in, uint64_t in_len, uint64_t *raw_len);
+int mcomh_bwt_stages(const uint8_t *in, uint64_t n, uint8_t *bwt, uint8_t *index, uint8_t *ranks);
+int mcomh_bwt_pack_file(const char *in_path, const char *out_path, int device);
+int mcomh_bwt_unpack_file(const char *in_path, const char *out_path, int device);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

@@ -53,6 +53,14 @@ int mcom_set_lookup_route(mcom_ctx *ctx, int route);
  * mcom_test_rans_seg_crc: d_crc gets one CRC-32 per segment of 2^seg_log2 bytes (8 .. 15), the last one of what is left.                */
 int mcom_test_rans_hist(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_counts);
 int mcom_test_rans_seg_crc(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t seg_log2, uint32_t *d_crc);
+/* The block-sorting coder (csrc/bwt.hip) hands its stages out the same way, through the launch functions mcom_bwt_encode / _decode use,
+ * with the block and anchor sizes the encoder writes (2^20, 2^12).  d_in: n > 0 bytes on the device, at any address.
+ * mcom_test_bwt_forward: d_bwt gets the n transformed bytes, d_idx (4-byte aligned) one u32 row per anchor in the member's order,
+ * *h_rounds (may be NULL) the rounds of prefix doubling it took.
+ * mcom_test_bwt_mtf: d_dst gets the move-to-front ranks of d_src's n bytes (decode != 0: the bytes of n ranks), the list starting
+ * as 0 .. 255 at every block; both pointers 4-byte aligned.                                                                           */
+int mcom_test_bwt_forward(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_bwt, uint32_t *d_idx, int *h_rounds);
+int mcom_test_bwt_mtf(mcom_ctx *ctx, const uint8_t *d_src, uint64_t n, uint8_t *d_dst, int decode);
 /* mcom_verify_multiset keeps only the low `bits` bits of every record's hash (0 .. 63; 64 or negative = default, all of them), through
  * the same launches: with 2 or 0 bits nearly every run of equal hashes holds unequal records, so that a thousand rows walk the path
  * real data reaches once in 2^64 -- the run settled in full on the host.  Same verdict and counts at any width.                    */

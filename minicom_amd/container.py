@@ -14,6 +14,9 @@ what the reference's script unpacks.
 same bytes.  With `device=None` the members are coded by the host twin, with an integer by that GPU (libmcom_hip.so through
 libmcom_host.so); every other codec is packaging on the host.  The stream files themselves are the parity boundary
 (tests/test_streams.py compares them byte for byte with the reference's).
+
+`codec="bwt"` is the block-sorting coder on top of it (Burrows-Wheeler transform per 1 MiB block, move-to-front,
+the ranks as a `.rans` member), with the same two routes and the same meaning of `device`.
 """
 import bz2
 import glob
@@ -37,7 +40,7 @@ GROUPS = (
     ("filebin", ("file.bin.*",)),                    # :259-262, paired end only
 )
 SINGLES = ("single_N.seq", "single.seq", "AA.txt", "TT.txt", "NN.txt")      # :136-137, :144-146
-CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans")
+CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
 
 def _encode(data: bytes, codec: str) -> bytes:
@@ -78,16 +81,18 @@ def _bsc(args, src: bytes, tmpdir: str, tag: str) -> bytes:
     return out
 
 
-def _rans(data: bytes, pack_it: bool, device, tmpdir: str, tag: str) -> bytes:
+def _rans(data: bytes, pack_it: bool, device, tmpdir: str, tag: str, codec: str = "rans") -> bytes:
     """One member through the built-in entropy stage: the host twin on the bytes, or -- device given -- the file route on that GPU."""
     from . import pipeline
+    if device is None and codec == "bwt":
+        return pipeline.bwt_encode(data) if pack_it else pipeline.bwt_decode(data)
     if device is None:
         return pipeline.rans_encode(data) if pack_it else pipeline.rans_decode(data)
     a, b = os.path.join(tmpdir, tag + ".rin"), os.path.join(tmpdir, tag + ".rout")
     with open(a, "wb") as f:
         f.write(data)
     try:
-        pipeline.entropy_file(a, b, pack_it, device)
+        pipeline.entropy_file(a, b, pack_it, device, codec=codec)
         with open(b, "rb") as f:
             return f.read()
     finally:
@@ -111,7 +116,7 @@ def _inner_tar(folder: str, names) -> bytes:
 
 def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device: int | None = None) -> dict:
     """Stream files in `folder` (as cluster_dump left them) -> one `.minicom` file.  Returns the member sizes.
-    device (codec "rans" only): None = the host twin, an integer = that GPU, one member at a time."""
+    device (codecs "rans" and "bwt" only): None = the host twin, an integer = that GPU, one member at a time."""
     if codec not in CODECS:
         raise ValueError("codec must be one of %s" % (CODECS,))
     if not os.path.isfile(os.path.join(folder, "info.txt")):
@@ -134,6 +139,8 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
             return name + ".bsc", _bsc(("e", "-b64p", "-t%d" % threads, "-e2"), data, folder, name)
         if codec == "rans":
             return name + ".rans", _rans(data, True, device, folder, name)
+        if codec == "bwt":
+            return name + ".bwt", _rans(data, True, device, folder, name, codec="bwt")
         return name + "." + ext, _encode(data, codec)
 
     with ThreadPoolExecutor(max(1, threads) if device is None else 1) as ex:
@@ -154,7 +161,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
 def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) -> dict:
     """`.minicom` file -> the stream files in `folder` (created if absent).  Returns what the archive says about itself:
     {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334).
-    device: where `.rans` members are decoded -- None = the host twin, an integer = that GPU."""
+    device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
         items = [(m.name.lstrip("./"), t.extractfile(m).read()) for m in t.getmembers() if m.isfile()]
@@ -171,6 +178,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             raise RuntimeError("member %s needs 7z; archives written here use one codec for every member" % name)
         if ext == "rans":
             return base, _rans(data, False, device, folder, base)
+        if ext == "bwt":
+            return base, _rans(data, False, device, folder, base, codec="bwt")
         return base, _decode(data, ext)
 
     with ThreadPoolExecutor(max(1, threads) if device is None else 1) as ex:
@@ -197,7 +206,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
-    fallback), the stream writer and the packaging on the host -- except codec "rans", whose members are coded on `device` too.
+    fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     Returns pack()'s member sizes plus the read count."""
     import tempfile
     from .pipeline import Pipeline
@@ -208,7 +217,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.pre_process()
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
             p.cluster_dump(td, order=order, paired=path2 is not None)
-            sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec == "rans" else None)
+            sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         return sizes
     finally:
@@ -218,7 +227,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
 def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None) -> int:
     """`.minicom` -> reads, one per line: the original order for an archive written with -p, two files (line i of both a
     pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
-    integer: `.rans` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
+    integer: `.rans` and `.bwt` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
     are host code either way."""
     import tempfile
     from .pipeline import decompress, decompress_pe

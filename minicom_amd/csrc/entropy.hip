@@ -340,6 +340,13 @@ int device_crc(mcom_ctx *ctx, Blocks &B, const uint8_t *d, uint64_t n, uint32_t 
 }
 }  // namespace
 
+// the CRC-32 of n bytes on the device, for the other coders of the library (bwt.hip): segment CRCs joined on the host, as the codec's own
+int mcom_device_crc32(mcom_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t *crc_out)
+{
+	Blocks B(ctx);
+	return device_crc(ctx, B, d, n, SEG_LOG2, crc_out);
+}
+
 template <int O1, int STRIDE>
 static void launch_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t n_seg, const uint16_t *d_cum, uint8_t *scratch, uint64_t *lens, uint32_t *flag, int vec)
 {

@@ -151,6 +151,8 @@ int mcom_merge_consensus_units(mcom_ctx *ctx, const uint64_t *d_packed, const ui
 // 64-bit exclusive scan (merge.hip): scratch of mcom_scan64_scratch_elems(n) uint64
 size_t mcom_scan64_scratch_elems(size_t n);
 int mcom_scan64(mcom_ctx *ctx, const uint64_t *in, uint64_t *out, size_t n, uint64_t *scratch);
+// CRC-32 of n bytes at any device address: per-segment CRCs joined on the host (entropy.hip); synchronises the stream
+int mcom_device_crc32(mcom_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t *crc_out);
 
 #define MCOM_HIP(ctx, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) \
 	return mcom_fail(ctx, MCOM_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); } while (0)

@@ -170,6 +170,9 @@ def load_library():
     L.mcom_rans_bound.restype = u64; L.mcom_rans_bound.argtypes = [u64]
     L.mcom_rans_encode.restype = i32; L.mcom_rans_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
     L.mcom_rans_decode.restype = i32; L.mcom_rans_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcom_bwt_bound.restype = u64; L.mcom_bwt_bound.argtypes = [u64]
+    L.mcom_bwt_encode.restype = i32; L.mcom_bwt_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcom_bwt_decode.restype = i32; L.mcom_bwt_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.mcom_synth_reads.restype = i32
     L.mcom_synth_reads.argtypes = [vp, u64, u64, i32, i32, C.c_double, u64, u64, vp, sz]
     L.mcom_synth_reads_genome.restype = i32
@@ -936,6 +939,65 @@ class Context:
         got = C.c_uint64()
         self._check(self.lib.mcom_rans_decode(self._h, self._p(member, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
         return out[:got.value]
+
+    # ---- the block-sorting coder (csrc/bwt.hip) ----
+    def bwt_encode(self, raw, out=None):
+        """mcom_bwt_encode.  raw: uint8 device tensor.  Returns the `.bwt` member as a uint8 device tensor.
+        out: a uint8 device tensor to write the member into (its length is the room offered) instead of a fresh one."""
+        torch = _torch()
+        n = int(raw.shape[0])
+        cap = int(out.shape[0]) if out is not None else int(self.lib.mcom_bwt_bound(n))
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        got = C.c_uint64()
+        self._check(self.lib.mcom_bwt_encode(self._h, self._p(raw, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
+        return out[:got.value]
+
+    def bwt_decode(self, member, out=None):
+        """mcom_bwt_decode.  member: uint8 device tensor.  Returns the raw bytes as a uint8 device tensor; McomError for every member
+        section 3.8 refuses.  out: a uint8 device tensor to decode into (its length is the room offered) instead of a fresh one of
+        the length the header states (below 4 GiB)."""
+        torch = _torch()
+        n = int(member.shape[0])
+        if out is not None:
+            cap = int(out.shape[0])
+        else:
+            # the room comes from the header only once the header describes this member to the byte (the host twin's own check)
+            from .pipeline import load_host_library
+            head = bytes(member[:40].cpu().numpy()) if n >= 40 else b""
+            raw_len = C.c_uint64()
+            if len(head) != 40 or load_host_library().mcomh_bwt_raw_len(head, n, C.byref(raw_len)):
+                raise McomError("bwt_decode: the header does not describe this member")
+            cap = int(raw_len.value)
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
+        got = C.c_uint64()
+        self._check(self.lib.mcom_bwt_decode(self._h, self._p(member, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
+        return out[:got.value]
+
+    def bwt_test_forward(self, raw):
+        """Test hook (mcom_test_bwt_forward): (transformed bytes uint8 [n], index rows int64 [anchors], rounds of prefix doubling) for
+        the uint8 device tensor `raw` (at least one byte), through the launches of mcom_bwt_encode."""
+        torch = _torch()
+        self.lib.mcom_test_bwt_forward.restype = C.c_int
+        self.lib.mcom_test_bwt_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        n = int(raw.shape[0])
+        n_anc = sum(-(-min(1 << 20, n - a) // 4096) for a in range(0, n, 1 << 20))
+        tr = torch.empty(n, dtype=torch.uint8, device=self.device)
+        idx = torch.zeros(max(n_anc, 1), dtype=torch.int32, device=self.device)
+        rounds = C.c_int()
+        self._check(self.lib.mcom_test_bwt_forward(self._h, self._p(raw, torch.uint8), n, self._p(tr), self._p(idx), C.byref(rounds)))
+        return tr, idx[:n_anc].to(torch.int64) & 0xFFFFFFFF, int(rounds.value)
+
+    def bwt_test_mtf(self, src, decode: bool = False):
+        """Test hook (mcom_test_bwt_mtf): the move-to-front ranks of the uint8 device tensor `src` (decode: the bytes of ranks), the
+        list starting as 0 .. 255 every 2^20 bytes, through the launches of the codec."""
+        torch = _torch()
+        self.lib.mcom_test_bwt_mtf.restype = C.c_int
+        self.lib.mcom_test_bwt_mtf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+        src = src.contiguous().clone()                      # (a fresh allocation: 4-byte aligned)
+        dst = torch.empty_like(src)
+        self._check(self.lib.mcom_test_bwt_mtf(self._h, self._p(src, torch.uint8), int(src.shape[0]), self._p(dst), 1 if decode else 0))
+        return dst
 
     # -- verification (csrc/verify.hip)
     def _verify_table(self, t, L: int):

@@ -4,15 +4,18 @@
 // mcomh_rans_encode / mcomh_rans_decode are plain C++ on host buffers -- no GPU, no HIP call: the same histograms, the same shared
 // normalisation, choice and serialisation (csrc/rans_model.hpp), the same coder step, so the bytes equal the device's and the same
 // members are refused.  This half builds alone with -DMCOM_ENTROPY_HOST_ONLY (tests/fuzz_entropy.cpp runs it under the sanitizers).
+// (mcomh_bwt_pack_file / _unpack_file are the same file forms around the `.bwt` coder of host/mcom_bwt.cpp and csrc/bwt.hip.)
 // mcomh_entropy_pack_file / _unpack_file with device >= 0 run mcom_rans_encode / _decode on that GPU: the file is read into two
 // page-locked pieces that alternate between fread and the copy engine, the result comes back the same way, the copy of piece i + 1
 // under the write of piece i.  device = -1 is the host twin.  A refused or failed member leaves no output file.
 #include "../../include/mcom_host.h"
 #include "../csrc/rans_model.hpp"
+#include "../csrc/bwt_model.hpp"
 #include "mcom_inflate.hpp"
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 #ifndef MCOM_ENTROPY_HOST_ONLY
@@ -184,7 +187,8 @@ bool write_all(const char *path, const uint8_t *p, uint64_t n)
 	return true;
 }
 
-int host_file(const char *in_path, const char *out_path, bool pack)
+// bwt: the `.bwt` coder (section 3.8) instead of the `.rans` one
+int host_file(const char *in_path, const char *out_path, bool pack, bool bwt)
 {
 	const double t0 = now_ms();
 	FILE *f = fopen(in_path, "rb");
@@ -198,8 +202,14 @@ int host_file(const char *in_path, const char *out_path, bool pack)
 	std::vector<uint8_t> out;
 	uint64_t out_len = 0;
 	int rc;
-	if (pack) { out.resize(mcomh_rans_bound(n)); rc = mcomh_rans_encode(in.data(), n, out.data(), out.size(), &out_len, 0); }
-	else {
+	if (pack && bwt) { out.resize(mcomh_bwt_bound(n)); rc = mcomh_bwt_encode(in.data(), n, out.data(), out.size(), &out_len); }
+	else if (pack) { out.resize(mcomh_rans_bound(n)); rc = mcomh_rans_encode(in.data(), n, out.data(), out.size(), &out_len, 0); }
+	else if (bwt) {
+		mcom_bwt::Header bh;
+		if (!mcom_bwt::read_header(in.data(), n, bh)) return -1;
+		out.resize(bh.raw_len);
+		rc = mcomh_bwt_decode(in.data(), n, out.data(), out.size(), &out_len);
+	} else {
 		Header hd;
 		if (!read_header(in.data(), n, hd) || hd.raw_len > ((uint64_t)1 << 40)) return -1;
 		out.resize(hd.raw_len);
@@ -235,7 +245,7 @@ struct DeviceJob {                                           // what one file ca
 	}
 };
 
-int device_file(const char *in_path, const char *out_path, bool pack, int device)
+int device_file(const char *in_path, const char *out_path, bool pack, int device, bool bwt)
 {
 	const double t0 = now_ms();
 	int n_dev = 0;
@@ -251,23 +261,25 @@ int device_file(const char *in_path, const char *out_path, bool pack, int device
 	if (hipMalloc((void**)&J.d_in, n + 16) != hipSuccess) return -1;
 	// the file up: fread of piece i + 1 beside the copy of piece i
 	Header hd;
+	mcom_bwt::Header bh;
 	bool header_ok = pack;
 	for (uint64_t at = 0, i = 0; at < n; at += PIECE_BYTES, ++i) {
 		const int k = (int)(i & 1);
 		const size_t piece = n - at < PIECE_BYTES ? (size_t)(n - at) : PIECE_BYTES;
 		if (i >= 2 && hipEventSynchronize(J.ev[k]) != hipSuccess) return -1;
 		if (fread(J.pin[k], 1, piece, J.fin) != piece) return -1;
-		if (!pack && at == 0) header_ok = read_header(J.pin[k], n, hd);             // sizes are judged before anything is launched
+		if (!pack && at == 0) header_ok = bwt ? mcom_bwt::read_header(J.pin[k], n, bh) : read_header(J.pin[k], n, hd);             // sizes are judged before anything is launched
 		if (!header_ok) return -1;
 		if (hipMemcpyAsync(J.d_in + at, J.pin[k], piece, hipMemcpyHostToDevice, J.stream) != hipSuccess || hipEventRecord(J.ev[k], J.stream) != hipSuccess) return -1;
 	}
 	if (!header_ok || hipStreamSynchronize(J.stream) != hipSuccess) return -1;
 	const double t1 = now_ms();
-	const uint64_t cap = pack ? HEADER_BYTES + n : hd.raw_len;                      // (the chosen model never needs more than stored)
+	const uint64_t cap = pack ? (bwt ? mcom_bwt::HEADER_BYTES : 0) + HEADER_BYTES + n : bwt ? bh.raw_len : hd.raw_len;                      // (the chosen model never needs more than stored)
 	if (!pack && cap > ((uint64_t)1 << 40)) return -1;
 	if (hipMalloc((void**)&J.d_out, cap + 16) != hipSuccess) return -1;
 	uint64_t out_len = 0;
-	const int rc = pack ? mcom_rans_encode(J.ctx, J.d_in, n, J.d_out, cap, &out_len, 0) : mcom_rans_decode(J.ctx, J.d_in, n, J.d_out, cap, &out_len);
+	const int rc = bwt ? (pack ? mcom_bwt_encode(J.ctx, J.d_in, n, J.d_out, cap, &out_len) : mcom_bwt_decode(J.ctx, J.d_in, n, J.d_out, cap, &out_len))
+	                   : (pack ? mcom_rans_encode(J.ctx, J.d_in, n, J.d_out, cap, &out_len, 0) : mcom_rans_decode(J.ctx, J.d_in, n, J.d_out, cap, &out_len));
 	if (rc) { fprintf(stderr, "mcom entropy stage: %s\n", mcom_last_error(J.ctx)); return -1; }
 	const double t2 = now_ms();
 	// the result down: the copy of piece i + 1 under the write of piece i
@@ -293,13 +305,15 @@ int device_file(const char *in_path, const char *out_path, bool pack, int device
 }
 #endif
 
-int file_call(const char *in_path, const char *out_path, int device, bool pack)
+int file_call(const char *in_path, const char *out_path, int device, bool pack, bool bwt = false)
 {
 	if (!in_path || !out_path) return -1;
 	memset(g_times, 0, sizeof g_times);
-	if (device < 0) return host_file(in_path, out_path, pack);
+	if (device < 0) {
+		try { return host_file(in_path, out_path, pack, bwt); } catch (const std::bad_alloc &) { return -1; }      // (a header that asks for more than there is)
+	}
 #ifndef MCOM_ENTROPY_HOST_ONLY
-	return device_file(in_path, out_path, pack, device);
+	return device_file(in_path, out_path, pack, device, bwt);
 #else
 	return -1;
 #endif
@@ -310,3 +324,5 @@ int file_call(const char *in_path, const char *out_path, int device, bool pack)
 extern "C" int mcomh_entropy_pack_file(const char *in_path, const char *out_path, int device) { return file_call(in_path, out_path, device, true); }
 extern "C" int mcomh_entropy_unpack_file(const char *in_path, const char *out_path, int device) { return file_call(in_path, out_path, device, false); }
 extern "C" void mcomh_entropy_times(double *ms8) { memcpy(ms8, g_times, sizeof g_times); }
+extern "C" int mcomh_bwt_pack_file(const char *in_path, const char *out_path, int device) { return file_call(in_path, out_path, device, true, true); }
+extern "C" int mcomh_bwt_unpack_file(const char *in_path, const char *out_path, int device) { return file_call(in_path, out_path, device, false, true); }

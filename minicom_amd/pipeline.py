@@ -92,6 +92,13 @@ def load_host_library():
     L.mcomh_entropy_pack_file.restype = i32; L.mcomh_entropy_pack_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_unpack_file.restype = i32; L.mcomh_entropy_unpack_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_times.restype = None; L.mcomh_entropy_times.argtypes = [C.POINTER(C.c_double)]
+    L.mcomh_bwt_bound.restype = u64; L.mcomh_bwt_bound.argtypes = [u64]
+    L.mcomh_bwt_encode.restype = i32; L.mcomh_bwt_encode.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcomh_bwt_decode.restype = i32; L.mcomh_bwt_decode.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcomh_bwt_raw_len.restype = i32; L.mcomh_bwt_raw_len.argtypes = [vp, u64, C.POINTER(u64)]
+    L.mcomh_bwt_stages.restype = i32; L.mcomh_bwt_stages.argtypes = [vp, u64, vp, vp, vp]
+    L.mcomh_bwt_pack_file.restype = i32; L.mcomh_bwt_pack_file.argtypes = [cp, cp, i32]
+    L.mcomh_bwt_unpack_file.restype = i32; L.mcomh_bwt_unpack_file.argtypes = [cp, cp, i32]
     _lib = L
     return L
 
@@ -107,6 +114,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     # the built-in entropy stage (host/mcom_entropy.cpp)
                     "mcomh_rans_bound", "mcomh_rans_estimate", "mcomh_rans_encode", "mcomh_rans_decode", "mcomh_entropy_pack_file",
                     "mcomh_entropy_unpack_file", "mcomh_entropy_times",
+                    # the block-sorting coder (host/mcom_bwt.cpp)
+                    "mcomh_bwt_bound", "mcomh_bwt_encode", "mcomh_bwt_decode", "mcomh_bwt_raw_len", "mcomh_bwt_stages", "mcomh_bwt_pack_file",
+                    "mcomh_bwt_unpack_file",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -203,13 +213,75 @@ def rans_estimate(data: bytes) -> list[int]:
     return [int(v) for v in est]
 
 
-def entropy_file(in_path: str, out_path: str, pack: bool, device: int | None = None) -> dict:
-    """mcomh_entropy_pack_file / _unpack_file: a file -> a `.rans` member file or back.  device None: the host twin; an integer:
-    that GPU (an error, never the host twin, when there is none).  Returns mcomh_entropy_times as a dict."""
+def _device_context(device: int):
+    from .hip import Context
+    return Context(int(device))
+
+
+def bwt_encode(data: bytes, device: int | None = None) -> bytes:
+    """raw bytes -> a `.bwt` member.  device None: mcomh_bwt_encode, the host twin; an integer: mcom_bwt_encode
+    on that GPU (the same bytes; an error, never the host twin, when there is none)."""
+    if device is not None:
+        import torch
+        ctx = _device_context(device)
+        raw = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(f"cuda:{int(device)}") if data else torch.empty(0, dtype=torch.uint8, device=f"cuda:{int(device)}")
+        return ctx.bwt_encode(raw).cpu().numpy().tobytes()
     lib = load_host_library()
-    fn = lib.mcomh_entropy_pack_file if pack else lib.mcomh_entropy_unpack_file
+    n = len(data)
+    cap = int(lib.mcomh_bwt_bound(n))
+    out = C.create_string_buffer(cap)
+    got = C.c_uint64()
+    rc = lib.mcomh_bwt_encode((C.c_char * n).from_buffer_copy(data) if n else None, n, out, cap, C.byref(got))
+    if rc:
+        raise McomError(f"bwt_encode: error {rc}")
+    return out.raw[:got.value]
+
+
+def bwt_decode(member: bytes, device: int | None = None) -> bytes:
+    """a `.bwt` member -> the raw bytes, on the host twin or on that GPU; McomError for every member section 3.8 refuses."""
+    lib = load_host_library()
+    n = len(member)
+    src = (C.c_char * n).from_buffer_copy(member) if n else None
+    raw_len = C.c_uint64()
+    if lib.mcomh_bwt_raw_len(src, n, C.byref(raw_len)):
+        raise McomError("bwt_decode: not a complete .bwt member")
+    if device is not None:
+        import torch
+        ctx = _device_context(device)
+        return ctx.bwt_decode(torch.frombuffer(bytearray(member), dtype=torch.uint8).to(f"cuda:{int(device)}")).cpu().numpy().tobytes()
+    cap = int(raw_len.value)
+    out = C.create_string_buffer(max(cap, 1))
+    got = C.c_uint64()
+    rc = lib.mcomh_bwt_decode(src, n, out, cap, C.byref(got))
+    if rc:
+        raise McomError(f"bwt_decode: error {rc}: not a complete, intact .bwt member")
+    return out.raw[:got.value]
+
+
+def bwt_stages(data: bytes):
+    """mcomh_bwt_stages: (transformed bytes, index rows as a list, move-to-front ranks) of the host twin's encoder"""
+    lib = load_host_library()
+    n = len(data)
+    n_anc = sum(-(-min(1 << 20, n - a) // 4096) for a in range(0, n, 1 << 20))
+    tr, ix, rk = C.create_string_buffer(max(n, 1)), C.create_string_buffer(max(4 * n_anc, 1)), C.create_string_buffer(max(n, 1))
+    if lib.mcomh_bwt_stages((C.c_char * n).from_buffer_copy(data) if n else None, n, tr, ix, rk):
+        raise McomError("bwt_stages: error")
+    return tr.raw[:n], [int.from_bytes(ix.raw[4 * k:4 * k + 4], "little") for k in range(n_anc)], rk.raw[:n]
+
+
+def entropy_file(in_path: str, out_path: str, pack: bool, device: int | None = None, codec: str = "rans") -> dict:
+    """mcomh_entropy_pack_file / _unpack_file (codec "bwt": mcomh_bwt_pack_file / _unpack_file): a file -> a member file or back.
+    device None: the host twin; an integer: that GPU (an error, never the host twin, when there is none).  Returns mcomh_entropy_times
+    as a dict."""
+    lib = load_host_library()
+    if codec not in ("rans", "bwt"):
+        raise McomError("entropy_file: codec rans or bwt")
+    if codec == "bwt":
+        fn = lib.mcomh_bwt_pack_file if pack else lib.mcomh_bwt_unpack_file
+    else:
+        fn = lib.mcomh_entropy_pack_file if pack else lib.mcomh_entropy_unpack_file
     if fn(in_path.encode(), out_path.encode(), -1 if device is None else int(device)):
-        raise McomError(("cannot pack %s" if pack else "%s is not a complete, intact .rans member") % in_path + ("" if device is None else f" (GPU {device})"))
+        raise McomError(("cannot pack %s" if pack else "%s is not a complete, intact ." + codec + " member") % in_path + ("" if device is None else f" (GPU {device})"))
     t = (C.c_double * 8)()
     lib.mcomh_entropy_times(t)
     return {"read_upload_ms": t[0], "codec_ms": t[1], "download_write_ms": t[2], "total_ms": t[3], "raw_bytes": int(t[4]), "coded_bytes": int(t[5])}
