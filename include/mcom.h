@@ -751,6 +751,50 @@ uint64_t mcom_bwt_bound(uint64_t n);
 int mcom_bwt_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 int mcom_bwt_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 
+/* ---- quality values: `.mcq` members (csrc/qual.hip; format and host twin: DESIGN.md section 3.9, include/mcom_host.h) ----
+ * A matrix of n_rows x L bytes (1 <= L <= 256, n_rows < 2^32, n_rows * L <= 2^34) under a static context model: the byte values that
+ * occur become dense symbols, the context of a column is row-local (the previous symbol, the larger of the two before it in a few bins,
+ * the eighth of the row the column lies in), the coder step and the 12-bit tables are the `.rans` coder's.  A segment is a group of
+ * consecutive rows with one rANS state and one run, one lane per segment.  The `.rans` member of the flat bytes is made as well and
+ * embedded where it is smaller.  Device pointers at any address, rows `pitch` >= L bytes apart, work on the context's stream, both
+ * calls synchronous.  The bytes equal those of mcomh_qual_encode for the same input and hint.
+ *   mcom_qual_bound   room that is enough for n_rows x L under any hint (0: L outside 1 .. 256)
+ *   mcom_qual_encode  model_hint 0: the model id 0 .. 4 with the smallest estimate (ties: the earlier id), then the smaller of that
+ *                     member and the embedded `.rans` one; MCOM_QUAL_HINT(id) forces a model, MCOM_QUAL_HINT_RANS the embedding (tests).
+ *                     MCOM_E_OVERFLOW when cap is too small (nothing valid in d_out)
+ *   mcom_qual_info    plain host code: n_rows and L from the first 64 bytes of a member that the host holds (-1: not a `.mcq` header)
+ *   mcom_qual_decode  *n_rows, *L = the member's.  MCOM_E_OVERFLOW (with both set) when cap_rows is too small; MCOM_E_ARG for every
+ *                     member section 3.9 refuses -- d_rows then holds nothing valid.  Untrusted input never makes a kernel leave its
+ *                     buffers (it raises a flag word and skips the access).                                                          */
+#define MCOM_QUAL_HINT(id) (0x100 | (id))
+#define MCOM_QUAL_HINT_RANS 0x180
+uint64_t mcom_qual_bound(uint64_t n_rows, uint32_t L);
+int mcom_qual_encode(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_rows, uint32_t L, uint64_t pitch, uint8_t *d_out, uint64_t cap,
+                     uint64_t *out_len, int model_hint);
+int mcom_qual_info(const uint8_t *h_member_prefix, uint64_t len, uint64_t *n_rows, uint32_t *L);
+int mcom_qual_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_rows, uint64_t pitch, uint64_t cap_rows,
+                     uint64_t *n_rows, uint32_t *L);
+
+/* ---- FASTQ text <-> rows on the device (csrc/qual.hip): the two ends of `minicom -Q` ----
+ * mcom_fastq_quality_rows: record r of this call is lines 4r .. 4r + 3 of a line index made by mcom_decode_line_index over d_text
+ * (so d_line_start holds at least 4 n_records + 1 entries); its quality line goes to row first_record + r of d_rows (`pitch` >= L
+ * apart).  A record is flagged rather than guessed at: d_flag points at TWO words that the caller clears to 0 and 0xFFFFFFFF -- the
+ * first collects the bits below, the second the lowest flagged record number (first_record + r).  A flagged record's row holds
+ * nothing valid.  A '\r' in front of the newline makes the line one byte too long, which is a wrong length.
+ * mcom_fastq_emit: `count` records `@<i+1>\n<read>\n+\n<qualities>\n` for i = first .. first + count - 1 back to back into d_out;
+ * d_reads / d_quals point at the rows of record `first`.  *bytes = their length, count * (2 L + 6) + the digits of the names, also
+ * when d_out is NULL (nothing is launched then: the way to size d_out).  Both calls are synchronous; below 2^32 records.            */
+enum mcom_fastq_flag {
+	MCOM_FASTQ_F_NAME = 1,      /* line 4r is empty or does not start with '@'                                          */
+	MCOM_FASTQ_F_PLUS = 2,      /* line 4r + 2 is empty or does not start with '+'                                      */
+	MCOM_FASTQ_F_LENGTH = 4,    /* line 4r + 1 or line 4r + 3 is not exactly L bytes long                               */
+	MCOM_FASTQ_F_CHAR = 8       /* a quality byte outside 33 .. 126                                                     */
+};
+int mcom_fastq_quality_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
+                            uint64_t n_records, uint32_t L, uint8_t *d_rows, uint64_t pitch, uint32_t *d_flag);
+int mcom_fastq_emit(mcom_ctx *ctx, const uint8_t *d_reads, uint64_t read_pitch, const uint8_t *d_quals, uint64_t qual_pitch, uint64_t first,
+                    uint64_t count, uint32_t L, uint8_t *d_out, uint64_t *bytes);
+
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,
                      uint64_t first, uint64_t count, uint8_t *d_ascii, size_t pitch);

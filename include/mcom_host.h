@@ -266,6 +266,56 @@ int mcomh_bwt_stages(const uint8_t *in, uint64_t n, uint8_t *bwt, uint8_t *index
 int mcomh_bwt_pack_file(const char *in_path, const char *out_path, int device);
 int mcomh_bwt_unpack_file(const char *in_path, const char *out_path, int device);
 
+/* ---- quality values: `.mcq` members (host/mcom_qual.cpp) ----
+ * The host twin of mcom_qual_encode / mcom_qual_decode (include/mcom.h): a matrix of n_rows x L bytes, rows `pitch` >= L bytes apart,
+ * under a static context model, or as an embedded `.rans` member where that is smaller.  Plain C++, no GPU; the same bytes out for the
+ * same input and hint (0, 0x100 | model id 0 .. 4, 0x180 for the embedding), the same members accepted and refused.  Return values as
+ * for the rANS calls; decode sets *n_rows and *L also when it returns -4 (more than cap_rows rows).
+ *   mcomh_qual_bound     room that is enough under any hint (0: L outside 1 .. 256)
+ *   mcomh_qual_info      n_rows and L from the first 64 bytes of a member (-1: not a `.mcq` header)
+ *   mcomh_qual_estimate  the estimated sizes the choice compares, by model id 0 .. 4 (as mcomh_rans_estimate: what the tests of the
+ *                        model choice and tools read)
+ * mcomh_qual_estimate and the two file forms below are additions beyond the four coder calls, made on purpose on the pattern of the
+ * `.rans` and `.bwt` sections above: the estimate lets a test hold the choice to the specification, the file forms are what bin/mcomz runs.
+ *                                                 */
+uint64_t mcomh_qual_bound(uint64_t n_rows, uint32_t L);
+int mcomh_qual_info(const uint8_t *prefix, uint64_t len, uint64_t *n_rows, uint32_t *L);
+int mcomh_qual_estimate(const uint8_t *rows, uint64_t n_rows, uint32_t L, uint64_t pitch, uint64_t est5[5]);
+int mcomh_qual_encode(const uint8_t *rows, uint64_t n_rows, uint32_t L, uint64_t pitch, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                      int model_hint);
+int mcomh_qual_decode(const uint8_t *in, uint64_t in_len, uint8_t *rows, uint64_t pitch, uint64_t cap_rows, uint64_t *n_rows, uint32_t *L);
+/* File forms (bin/mcomz e --qual L, d): a file of n * L raw bytes <-> a `.mcq` member; device = -1 the host twin, otherwise that GPU (an
+ * error, never the host twin, when there is no such GPU).  No output file is left by a call that fails.                              */
+int mcomh_qual_pack_file(const char *in_path, const char *out_path, int L, int device);
+int mcomh_qual_unpack_file(const char *in_path, const char *out_path, int device);
+
+/* ---- `minicom -Q`: a -p archive that also carries the quality values, as the member qual.mcq in input order ----
+ * Read names and the text of the third line are not kept: the decoders name record i `@<i+1>` and write a bare `+`.
+ *   mcomh_fastq_qualities_to_device  the quality lines of a four-line FASTQ file (plain or .gz) as rows of L bytes in HBM (*d_rows,
+ *                                    release with mcomh_device_free; *n records).  The text goes up through two page-locked pieces of
+ *                                    piece_bytes (0 = 32 MiB; at least 4 * (2 L + 64) bytes, a smaller request is raised to that, so that a
+ *                                    piece holds a few records), the unfinished record at a piece's end in front of the next piece; lines
+ *                                    are found by mcom_decode_line_index, rows gathered by mcom_fastq_quality_rows.  A missing last
+ *                                    newline is accepted; a record the kernel flags is an error whose message names the first one.
+ *   mcomh_fastq_quality_member       FASTQ file -> the `.mcq` member file in one call (what `minicom -Q` runs, bin/mcomz e --fastq-qual L):
+ *                                    on GPU `device` the two calls above and mcom_qual_encode; device = -1 the host twin of both, which
+ *                                    applies the same record rules, refuses the same files and names the same first bad record.  The
+ *                                    same member either way; *n = the records; no output file is left by a call that fails.
+ *   mcomh_device_copy                `bytes` from one device pointer to another (for callers that hold device memory of their own, such
+ *                                    as the Python mirror, and must not bind the HIP runtime a second time); 0 on success.
+ *   mcomh_decompress_fastq           the host route: reads by the -p decoder, qualities by mcomh_qual_decode, four-line records.
+ *   mcomh_decompress_fastq_gpu       the same bytes with reads and qualities rebuilt and the records laid out on GPU `device`.
+ *   mcomh_verify_quality_gpu         qual.mcq decoded on the device against the quality lines of `fastq`, line against line
+ *                                    (mcom_verify_ordered); the report's mode is 1.  Returns 0 when a comparison was made.
+ * All refuse an archive that is not a -p one, that has no qual.mcq, or whose qual.mcq states another n or L than the reads; a
+ * refused archive leaves no output file.                                                                                              */
+int mcomh_fastq_qualities_to_device(const char *path, int device, int L, size_t piece_bytes, uint8_t **d_rows, size_t *n, char *err, size_t err_cap);
+int mcomh_fastq_quality_member(const char *fastq, int L, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap);
+int mcomh_device_copy(void *d_dst, const void *d_src, size_t bytes);
+int mcomh_decompress_fastq(const char *folder, const char *out_path, uint64_t *n_reads);
+int mcomh_decompress_fastq_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device);
+int mcomh_verify_quality_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

@@ -61,6 +61,13 @@ int mcom_test_rans_seg_crc(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint3
  * as 0 .. 255 at every block; both pointers 4-byte aligned.                                                                           */
 int mcom_test_bwt_forward(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_bwt, uint32_t *d_idx, int *h_rounds);
 int mcom_test_bwt_mtf(mcom_ctx *ctx, const uint8_t *d_src, uint64_t n, uint8_t *d_dst, int decode);
+/* The quality coder (csrc/qual.hip) counts once, for its richest model; the counts are only seen through the tables of the chosen model.
+ * mcom_test_qual_hist runs the very launches of mcom_qual_encode (alphabet pass, then the counting kernel: counters in LDS for an
+ * alphabet of at most 8 values, in a global table otherwise) on n_rows > 0 rows of L bytes, `pitch` apart, at any address.  h_map gets
+ * the 32 bytes of the alphabet map, *h_A the alphabet size A; d_counts (room for A * min(A, 8) * 8 * A u64; pass NULL to learn A first)
+ * gets the counts [previous symbol][bin of max(s[j-2], s[j-3])][floor(8 j / L)][symbol] over dense symbols.                             */
+int mcom_test_qual_hist(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_rows, uint32_t L, uint64_t pitch, uint8_t *h_map, uint32_t *h_A,
+                        uint64_t *d_counts);
 /* mcom_verify_multiset keeps only the low `bits` bits of every record's hash (0 .. 63; 64 or negative = default, all of them), through
  * the same launches: with 2 or 0 bits nearly every run of equal hashes holds unequal records, so that a thousand rows walk the path
  * real data reaches once in 2^64 -- the run settled in full on the host.  Same verdict and counts at any width.                    */

@@ -40,6 +40,7 @@ GROUPS = (
     ("filebin", ("file.bin.*",)),                    # :259-262, paired end only
 )
 SINGLES = ("single_N.seq", "single.seq", "AA.txt", "TT.txt", "NN.txt")      # :136-137, :144-146
+QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
 
@@ -145,6 +146,9 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
 
     with ThreadPoolExecutor(max(1, threads) if device is None else 1) as ex:
         packed = list(ex.map(enc, members))
+    if os.path.isfile(os.path.join(folder, QUALITY_MEMBER)):     # coded already: stored as it is, no codec on top
+        with open(os.path.join(folder, QUALITY_MEMBER), "rb") as f:
+            packed.append((QUALITY_MEMBER, f.read()))
     sizes = {}
     with tarfile.open(out_path, mode="w", format=tarfile.GNU_FORMAT) as t:
         with open(os.path.join(folder, "info.txt"), "rb") as f:
@@ -160,7 +164,8 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
 
 def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) -> dict:
     """`.minicom` file -> the stream files in `folder` (created if absent).  Returns what the archive says about itself:
-    {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334).
+    {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334), and "quality": True for an archive
+    that carries quality values (the member qual.mcq, left in the folder as it is).
     device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
@@ -169,7 +174,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt":
+        if name == "info.txt" or name == QUALITY_MEMBER:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -185,6 +190,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
     with ThreadPoolExecutor(max(1, threads) if device is None else 1) as ex:
         plain = list(ex.map(dec, items))
     for name, data in plain:
+        if name == QUALITY_MEMBER:
+            kinds["quality"] = True
         if name.startswith("idsbin.tar"):
             kinds["order"] = True
         if name.startswith("filebin.tar"):
@@ -204,19 +211,25 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
-                   device: int = 0, threads: int = 8, **params) -> dict:
+                   device: int = 0, threads: int = 8, quality: bool = False, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
-    Returns pack()'s member sizes plus the read count."""
+    quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
+    belongs to which read): the quality lines are gathered and coded on `device` and travel as the member qual.mcq.  Read names and the
+    text of the `+` line are not kept.  Returns pack()'s member sizes plus the read count."""
     import tempfile
     from .pipeline import Pipeline
     if order and path2 is not None:
         raise ValueError("-p is a single-end option (reference minicom:439-476)")
+    if quality and (not order or path2 is not None):
+        raise ValueError("quality values are kept by the order-preserving single-end mode only (order=True, no path2)")
     p = Pipeline.from_fastq(path, device=device, path2=path2, host_threads=threads, **params)
     try:
         p.pre_process()
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
             p.cluster_dump(td, order=order, paired=path2 is not None)
+            if quality:
+                _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER))
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         return sizes
@@ -224,15 +237,30 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.close()
 
 
+def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str) -> None:
+    """the quality lines of `fastq` -> rows on the device -> a `.mcq` member in out_path"""
+    from .hip import Context, McomError
+    from .pipeline import fastq_qualities
+    rows = fastq_qualities(fastq, L, device=device)
+    if int(rows.shape[0]) != n:
+        raise McomError("%s: %d quality lines for %d reads" % (fastq, int(rows.shape[0]), n))
+    member = Context(device).qual_encode(rows)
+    with open(out_path, "wb") as f:
+        f.write(member.cpu().numpy().tobytes())
+
+
 def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None) -> int:
     """`.minicom` -> reads, one per line: the original order for an archive written with -p, two files (line i of both a
     pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
     integer: `.rans` and `.bwt` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
-    are host code either way."""
+    are host code either way.  An archive with quality values (compress_fastq(quality=True)) gives FASTQ instead: four-line records
+    `@<i+1>`, read, `+`, qualities."""
     import tempfile
-    from .pipeline import decompress, decompress_pe
+    from .pipeline import decompress, decompress_fastq, decompress_pe
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        if kinds.get("quality"):
+            return decompress_fastq(td, out_path, device=device)
         if kinds["paired"]:
             if out_path2 is None:
                 raise ValueError("a paired-end archive decodes into two files")
@@ -243,14 +271,19 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
 def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int = 8, device: int = 0) -> dict:
     """`.minicom` against the FASTQ it was made from, on GPU `device`, without writing a read: pipeline.verify's report.  The mode comes
     from the members, as in decompress_file: a paired-end archive needs `fastq2`, a -p archive is held line against line, any other
-    one as a multiset of reads."""
+    one as a multiset of reads.  An archive with quality values is held against the quality lines as well: the report gets
+    "quality" (pipeline.verify_quality's) and "identical" is true only when both checks say so."""
     import tempfile
     from .hip import McomError
-    from .pipeline import verify
+    from .pipeline import verify, verify_quality
     if not os.path.isfile(path):
         raise McomError("no such archive: %s" % path)
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
         if kinds["paired"] != (fastq2 is not None):
             raise McomError("a paired-end archive is verified against two FASTQ files, any other against one")
-        return verify(td, fastq, fastq2, order=kinds["order"], device=device)
+        rep = verify(td, fastq, fastq2, order=kinds["order"], device=device)
+        if kinds.get("quality"):
+            rep["quality"] = verify_quality(td, fastq, device=device)
+            rep["identical"] = rep["identical"] and rep["quality"]["identical"]
+        return rep

@@ -170,6 +170,12 @@ def load_library():
     L.mcom_rans_bound.restype = u64; L.mcom_rans_bound.argtypes = [u64]
     L.mcom_rans_encode.restype = i32; L.mcom_rans_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
     L.mcom_rans_decode.restype = i32; L.mcom_rans_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcom_fastq_quality_rows.restype = i32; L.mcom_fastq_quality_rows.argtypes = [vp, vp, u64, vp, u64, u64, C.c_uint32, vp, u64, vp]
+    L.mcom_fastq_emit.restype = i32; L.mcom_fastq_emit.argtypes = [vp, vp, u64, vp, u64, u64, u64, C.c_uint32, vp, C.POINTER(u64)]
+    L.mcom_qual_bound.restype = u64; L.mcom_qual_bound.argtypes = [u64, C.c_uint32]
+    L.mcom_qual_encode.restype = i32; L.mcom_qual_encode.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_bwt_bound.restype = u64; L.mcom_bwt_bound.argtypes = [u64]
     L.mcom_bwt_encode.restype = i32; L.mcom_bwt_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.mcom_bwt_decode.restype = i32; L.mcom_bwt_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -939,6 +945,94 @@ class Context:
         got = C.c_uint64()
         self._check(self.lib.mcom_rans_decode(self._h, self._p(member, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got)))
         return out[:got.value]
+
+    # ---- quality values (csrc/qual.hip) ----
+    def qual_encode(self, rows, model=None, out=None):
+        """mcom_qual_encode.  rows: uint8 device tensor [n, L] whose rows are contiguous (any row stride >= L, any address).  model
+        None: chosen by estimated size, and the embedded `.rans` member where that is smaller; 0 .. 4 or "rans" force one.  Returns the
+        `.mcq` member as a uint8 device tensor.  out: a uint8 device tensor to write the member into."""
+        torch = _torch()
+        if rows.dim() != 2 or rows.dtype != torch.uint8 or (rows.shape[0] and rows.stride(1) != 1):
+            raise McomError("qual_encode: a uint8 matrix with contiguous rows")
+        n, L = int(rows.shape[0]), int(rows.shape[1])
+        pitch = int(rows.stride(0)) if n > 1 else L
+        cap = int(out.shape[0]) if out is not None else int(self.lib.mcom_qual_bound(n, L))
+        if not cap or pitch < L:
+            raise McomError("qual_encode: rows of %d bytes" % L)
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        hint = 0 if model is None else 0x180 if model == "rans" else 0x100 | int(model)
+        got = C.c_uint64()
+        self._check(self.lib.mcom_qual_encode(self._h, rows.data_ptr() if n else None, n, L, pitch, self._p(out), cap, C.byref(got), hint))
+        return out[:got.value]
+
+    def qual_decode(self, member, out=None):
+        """mcom_qual_decode.  member: uint8 device tensor.  Returns the quality matrix as a uint8 device tensor [n, L]; McomError for a
+        member that is truncated, malformed or fails its CRC-32.  out: a uint8 device tensor [rows, >= L] with contiguous rows to decode
+        into (its first dimension is the room offered); the result is then a view of it."""
+        torch = _torch()
+        n_in = int(member.shape[0])
+        head = bytes(member[:64].cpu().numpy())
+        n, L = C.c_uint64(), C.c_uint32()
+        if self.lib.mcom_qual_info(head if head else None, n_in, C.byref(n), C.byref(L)):
+            raise McomError("qual_decode: not a .mcq member")
+        n, L = int(n.value), int(L.value)
+        if out is None:
+            out = torch.empty((max(n, 1), L), dtype=torch.uint8, device=self.device)
+        if out.dim() != 2 or out.dtype != torch.uint8 or out.stride(1) != 1 or int(out.shape[1]) < L:
+            raise McomError("qual_decode: out must be a uint8 matrix with contiguous rows of at least %d bytes" % L)
+        pitch = int(out.stride(0)) if int(out.shape[0]) > 1 else max(L, int(out.shape[1]))
+        gn, gL = C.c_uint64(), C.c_uint32()
+        self._check(self.lib.mcom_qual_decode(self._h, self._p(member, torch.uint8), n_in, out.data_ptr(), pitch, int(out.shape[0]), C.byref(gn), C.byref(gL)))
+        return out[:n, :L]
+
+    def fastq_qualities(self, text, L: int, first_record: int = 0, out=None):
+        """mcom_decode_line_index + mcom_fastq_quality_rows.  text: uint8 device tensor holding whole four-line records (every line ends
+        with a newline).  Returns (rows uint8 [first_record + n_records, L], flag bits of MCOM_FASTQ_F_*, the first flagged record or
+        None); rows of flagged records hold nothing valid.  out: a uint8 device matrix with contiguous rows to gather into."""
+        torch = _torch()
+        start, _ = self.decode_line_index(text)
+        n_rec = (int(start.shape[0]) - 1) // 4
+        if out is None:
+            out = torch.zeros((max(first_record + n_rec, 1), L), dtype=torch.uint8, device=self.device)
+        pitch = int(out.stride(0)) if int(out.shape[0]) > 1 else max(L, int(out.shape[1]))
+        if out.dtype != torch.uint8 or out.stride(1) != 1 or int(out.shape[0]) < first_record + n_rec or int(out.shape[1]) < L:
+            raise McomError("fastq_qualities: out must hold %d rows of %d bytes" % (first_record + n_rec, L))
+        flag = torch.tensor([0, -1], dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_fastq_quality_rows(self._h, self._p(text, torch.uint8) if n_rec else None, int(text.shape[0]), self._p(start), first_record, n_rec, L,
+                                                     out.data_ptr(), pitch, self._p(flag)))
+        f = flag.cpu().numpy().view(np.uint32)
+        return out[:first_record + n_rec, :L], int(f[0]), (None if f[1] == 0xFFFFFFFF else int(f[1]))
+
+    def fastq_emit(self, reads, quals, first: int = 0):
+        """mcom_fastq_emit.  reads, quals: uint8 device matrices [count, >= L] with contiguous rows (row strides at will): the rows of
+        records first .. first + count - 1.  Returns the records `@<i+1>`, read, `+`, qualities as one uint8 device tensor."""
+        torch = _torch()
+        count, L = int(quals.shape[0]), int(quals.shape[1])
+        if int(reads.shape[0]) != count or int(reads.shape[1]) != L or (count and (reads.stride(1) != 1 or quals.stride(1) != 1)):
+            raise McomError("fastq_emit: reads and qualities of one shape, rows contiguous")
+        rp = int(reads.stride(0)) if count > 1 else L
+        qp = int(quals.stride(0)) if count > 1 else L
+        nb = C.c_uint64()
+        self._check(self.lib.mcom_fastq_emit(self._h, None, rp, None, qp, first, count, L, None, C.byref(nb)))
+        out = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.mcom_fastq_emit(self._h, reads.data_ptr() if count else None, rp, quals.data_ptr() if count else None, qp, first, count, L, self._p(out), C.byref(nb)))
+        return out[:nb.value]
+
+    def qual_test_hist(self, rows):
+        """Test hook (mcom_test_qual_hist): (alphabet map as 32 bytes, A, counts int64 [A, min(A, 8), 8, A] on the device) of the uint8
+        device matrix `rows` (at least one row), through the launches of mcom_qual_encode."""
+        torch = _torch()
+        self.lib.mcom_test_qual_hist.restype = C.c_int
+        self.lib.mcom_test_qual_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+        n, L = int(rows.shape[0]), int(rows.shape[1])
+        pitch = int(rows.stride(0)) if n > 1 else L
+        hmap = C.create_string_buffer(32); A = C.c_uint32()
+        self._check(self.lib.mcom_test_qual_hist(self._h, rows.data_ptr(), n, L, pitch, hmap, C.byref(A), None))
+        a = int(A.value); q = min(a, 8)
+        counts = torch.empty(a * q * 8 * a, dtype=torch.int64, device=self.device)
+        self._check(self.lib.mcom_test_qual_hist(self._h, rows.data_ptr(), n, L, pitch, hmap, C.byref(A), self._p(counts)))
+        return hmap.raw, a, counts.view(a, q, 8, a)
 
     # ---- the block-sorting coder (csrc/bwt.hip) ----
     def bwt_encode(self, raw, out=None):

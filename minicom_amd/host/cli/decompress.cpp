@@ -6,6 +6,8 @@
 // output files; an error, not the host decoder, when there is no GPU.
 // decompress --verify DIR IN.fastq pe order nthr [IN_2.fastq]: no output file; the archive's reads are rebuilt on GPU 0 and compared there
 // with the reads of the FASTQ file(s) (mcomh_verify_gpu).  Exit status 0 identical, 2 different, 1 refused or error.
+// decompress --fastq [--gpu] DIR OUT.fastq: a -p -Q archive (DIR holds qual.mcq) back to four-line records `@<i+1>`, read, `+`, qualities.
+// decompress --verify-quality DIR IN.fastq: qual.mcq against the quality lines of the FASTQ on GPU 0; exit status as --verify.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
@@ -45,9 +47,37 @@ static int verify(int argc, char **argv)
 	return 2;
 }
 
+static int verify_quality(int argc, char **argv)
+{
+	if (argc < 3) { fprintf(stderr, "usage: decompress --verify-quality DIR IN.fastq\n"); return 1; }
+	mcomh_verify_report r;
+	if (mcomh_verify_quality_gpu(argv[1], argv[2], 0, &r)) { fprintf(stderr, "decompress: the qualities of %s could not be verified against %s\n", argv[1], argv[2]); return 1; }
+	if (r.identical) { printf("verified: %llu quality lines identical\n", (unsigned long long)r.n_input); return 0; }
+	printf("DIFFERENT: the FASTQ holds %llu quality lines, the archive %llu\n  %llu lines differ", (unsigned long long)r.n_input, (unsigned long long)r.n_archive, (unsigned long long)r.differing);
+	if (r.differing) printf(", the first one is line %llu (from 0)", (unsigned long long)r.first_diff);
+	printf("\n");
+	return 2;
+}
+
+static int fastq(int argc, char **argv)
+{
+	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+	if (gpu) { --argc; ++argv; }
+	if (argc < 3) { fprintf(stderr, "usage: decompress --fastq [--gpu] DIR OUT.fastq\n"); return 1; }
+	uint64_t n = 0;
+	if (gpu ? mcomh_decompress_fastq_gpu(argv[1], argv[2], &n, 0) : mcomh_decompress_fastq(argv[1], argv[2], &n)) {
+		fprintf(stderr, "decompress: %s is not a complete, consistent -p archive with quality values%s\n", argv[1], gpu ? ", or the GPU route is not available" : "");
+		return 1;
+	}
+	fprintf(stdout, "%llu records\n", (unsigned long long)n);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	if (argc > 1 && !strcmp(argv[1], "--verify")) return verify(argc - 1, argv + 1);
+	if (argc > 1 && !strcmp(argv[1], "--verify-quality")) return verify_quality(argc - 1, argv + 1);
+	if (argc > 1 && !strcmp(argv[1], "--fastq")) return fastq(argc - 1, argv + 1);
 	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
 	if (gpu) { --argc; ++argv; }
 	if (argc < 6) { fprintf(stderr, "usage: decompress [--gpu] DIR OUT pe(true|false) order(true|false) nthr [OUT2]\n       decompress --verify DIR IN.fastq pe order nthr [IN_2.fastq]\n"); return 1; }

@@ -3,36 +3,55 @@
 // section 3.8); d: the way back, the kind of member taken from its first four bytes.  Host twin by default, GPU 0 with --gpu (an error,
 // not the host twin, when there is none).  Exit status 1 and no output file when IN cannot be read, is not a complete, intact member, or
 // OUT cannot be written.
+// mcomz e --qual L [--gpu] IN OUT: IN is n * L raw quality bytes (row after row), OUT a `.mcq` member; d knows
+// such a member by its magic and writes the raw bytes back.
+// mcomz e --fastq-qual L [--gpu] IN.fastq OUT: the quality lines of a four-line FASTQ file (plain or .gz) of reads of L bases -> a `.mcq`
+// member; every record is checked ('@' line, '+' line, both lengths, quality bytes 33 .. 126) and the first bad one is named -- on the
+// GPU by the kernels behind mcomh_fastq_qualities_to_device, without --gpu by their host twin.  Prints the number of records.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
-static bool is_bwt_member(const char *path)
+static bool has_magic(const char *path, const char *magic4)
 {
 	char magic[4] = {0, 0, 0, 0};
 	FILE *f = fopen(path, "rb");
 	if (!f) return false;
 	const bool got = fread(magic, 1, 4, f) == 4;
 	fclose(f);
-	return got && !memcmp(magic, "MCBW", 4);
+	return got && !memcmp(magic, magic4, 4);
 }
 
 int main(int argc, char **argv)
 {
 	bool gpu = false, bwt = false;
-	int at = 2;
+	int at = 2, qual_L = 0, fastq_L = 0;
 	for (; at < argc; ++at) {
 		if (!strcmp(argv[at], "--gpu") && !gpu) gpu = true;
+		else if (!strcmp(argv[at], "--qual") && !qual_L && at + 1 < argc) { qual_L = atoi(argv[++at]); if (qual_L < 1 || qual_L > 256) { fprintf(stderr, "mcomz: --qual takes the row length, 1 .. 256\n"); return 1; } }
+		else if (!strcmp(argv[at], "--fastq-qual") && !fastq_L && at + 1 < argc) { fastq_L = atoi(argv[++at]); if (fastq_L < 1 || fastq_L > 256) { fprintf(stderr, "mcomz: --fastq-qual takes the read length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--bwt") && !bwt) bwt = true;
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && bwt)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--gpu] IN.fastq OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;
+	if (fastq_L) {
+		char err[320] = ""; uint64_t n = 0;
+		if (mcomh_fastq_quality_member(in, fastq_L, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
+		printf("%llu\n", (unsigned long long)n);
+		return 0;
+	}
+	if (qual_L || (dec && has_magic(in, "MCQV"))) {
+		rc = enc ? mcomh_qual_pack_file(in, out, qual_L, device) : mcomh_qual_unpack_file(in, out, device);
+		if (rc) fprintf(stderr, enc ? "mcomz: cannot pack %s into %s%s\n" : "mcomz: %s is not a complete, intact .mcq member, or %s cannot be written%s\n", in, out, gpu ? " (or the GPU route is not available)" : "");
+		return rc ? 1 : 0;
+	}
 	if (enc) rc = bwt ? mcomh_bwt_pack_file(in, out, device) : mcomh_entropy_pack_file(in, out, device);
-	const bool bwt_in = dec && is_bwt_member(in);
+	const bool bwt_in = dec && has_magic(in, "MCBW");
 	if (dec) rc = bwt_in ? mcomh_bwt_unpack_file(in, out, device) : mcomh_entropy_unpack_file(in, out, device);
 	if (rc) {
 		fprintf(stderr, enc ? "mcomz: cannot pack %s into %s%s\n" : bwt_in ? "mcomz: %s is not a complete, intact .bwt member, or %s cannot be written%s\n"

@@ -156,9 +156,10 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 // the reads are rebuilt into a table indexed by their original position and written out in that order.  Id streams
 // are uint32, delta coded inside a list (lists are sorted by id); in ids.bin.T a member carries its id when it is the
 // first of its contig or starts at a new position, else the difference to the previous member's id (:164-167).
-static int decompress_order_impl(const char *folder, const char *out_path, uint64_t *n_reads)
+// keep: the table of n_seq x L characters is handed out instead of being written (mcomh_decompress_fastq)
+static int decompress_order_impl(const char *folder, const char *out_path, uint64_t *n_reads, std::vector<char> *keep = nullptr, int *L_out = nullptr)
 {
-	if (!folder || !out_path) return -1;
+	if (!folder || (!out_path && !keep)) return -1;
 	const std::string dir(folder);
 	FILE *fi = fopen((dir + "/info.txt").c_str(), "r");
 	if (!fi) return -1;
@@ -261,6 +262,7 @@ static int decompress_order_impl(const char *folder, const char *out_path, uint6
 	}
 	if (bad) return -1;
 	for (uint8_t s : seen) if (!s) return -1;                              // every position filled exactly once
+	if (keep) { keep->swap(table); if (L_out) *L_out = L; if (n_reads) *n_reads = n_seq; return 0; }
 	FILE *out = fopen(out_path, "w");
 	if (!out) return -1;
 	for (size_t i = 0; i < n_seq; ++i) { fwrite(table.data() + i * (size_t)L, 1, (size_t)L, out); fputc('\n', out); }
@@ -388,4 +390,35 @@ extern "C" int mcomh_decompress_order(const char *folder, const char *out_path, 
 extern "C" int mcomh_decompress_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
 {
 	try { return decompress_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
+}
+
+// ---- a -p -Q archive back to FASTQ on the host: the reads of decompress_order_impl in memory, the quality
+// rows of folder/qual.mcq by the host twin, then records `@<i+1>`, read, `+`, qualities.  The cross-check of mcomh_decompress_fastq_gpu:
+// the same bytes, the same archives refused (one that is not a -p archive, no qual.mcq, another n or L than the reads).
+static int decompress_fastq_impl(const char *folder, const char *out_path, uint64_t *n_reads)
+{
+	if (!folder || !out_path) return -1;
+	std::vector<char> reads; int L = 0; uint64_t n = 0;
+	if (decompress_order_impl(folder, nullptr, &n, &reads, &L)) return -1;
+	std::vector<uint8_t> member;
+	if (!slurp(std::string(folder) + "/qual.mcq", member)) return -1;
+	uint64_t qn = 0; uint32_t qL = 0;
+	if (mcomh_qual_info(member.data(), member.size(), &qn, &qL) || qn != n || (int)qL != L) return -1;
+	std::vector<uint8_t> quals((size_t)n * (size_t)L + 1);
+	if (mcomh_qual_decode(member.data(), member.size(), quals.data(), (uint64_t)L, n, &qn, &qL) || qn != n || (int)qL != L) return -1;
+	FILE *out = fopen(out_path, "wb");
+	if (!out) return -1;
+	bool ok = true;
+	for (uint64_t i = 0; i < n && ok; ++i) {
+		ok = fprintf(out, "@%llu\n", (unsigned long long)(i + 1)) > 0 && fwrite(reads.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0 &&
+		     fwrite(quals.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
+	}
+	if (fclose(out) != 0 || !ok) { remove(out_path); return -1; }
+	if (n_reads) *n_reads = n;
+	return 0;
+}
+
+extern "C" int mcomh_decompress_fastq(const char *folder, const char *out_path, uint64_t *n_reads)
+{
+	try { return decompress_fastq_impl(folder, out_path, n_reads); } catch (...) { return -1; }
 }

@@ -376,6 +376,55 @@ int guarded(Mode mode, const char *folder, const char *o1, const char *o2, uint6
 	} catch (...) { return -1; }   // no C++ exception crosses the C boundary
 }
 
+// ---- a -p -Q archive back to FASTQ: the third tail.  folder/qual.mcq is decoded on the device (mcom_qual_decode), the records
+// `@<i+1>`, read, `+`, qualities are laid out by mcom_fastq_emit a piece at a time, the copy of piece i under the write of piece i - 1.
+int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out)
+{
+	std::vector<uint8_t> member;
+	if (!slurp(std::string(folder) + "/qual.mcq", member)) throw Refuse{"no qual.mcq: not a -Q archive"};
+	uint64_t qn = 0; uint32_t qL = 0;
+	if (mcom_qual_info(member.data(), member.size(), &qn, &qL) || qn != n_rows || (int)qL != L) throw Refuse{"qual.mcq does not state the reads' number and length"};
+	const uint8_t *d_member = A.upload(member.data(), member.size());
+	uint8_t *quals = A.alloc<uint8_t>(n_rows * (uint64_t)L);
+	if (mcom_qual_decode(A.ctx, d_member, member.size(), quals, (uint64_t)L, n_rows, &qn, &qL)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"qual.mcq is refused"}; }
+	const double t0 = now_ms();
+	const uint64_t rec_max = 2 * (uint64_t)L + 17, per_piece = PIECE_BYTES / rec_max, pieces = (n_rows + per_piece - 1) / per_piece;
+	uint8_t *pin[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+	for (int b = 0; b < 2; ++b) {
+		void *p = nullptr;
+		if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"};
+		A.pinned.push_back(p); pin[b] = (uint8_t*)p;
+		d_out[b] = A.alloc<uint8_t>(pieces ? PIECE_BYTES : 1);
+	}
+	struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } arrived;   // piece i is in pin[i & 1]
+	for (int b = 0; b < 2; ++b) if (hipEventCreateWithFlags(&arrived.e[b], hipEventDisableTiming) != hipSuccess) throw Refuse{"no events"};
+	FILE *out = fopen(out_path, "wb");
+	if (!out) return -1;
+	bool wrote_ok = true;
+	uint64_t bytes[2] = {0, 0};
+	for (uint64_t i = 0; i <= pieces && wrote_ok; ++i) {
+		if (i < pieces) {
+			const uint64_t first = i * per_piece, count = n_rows - first < per_piece ? n_rows - first : per_piece;
+			if (mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, first, count, (uint32_t)L, d_out[i & 1], &bytes[i & 1]) ||
+			    bytes[i & 1] > PIECE_BYTES) { wrote_ok = false; break; }       // (synchronous on the context's stream: d_out[i & 1] is complete)
+			if (hipMemcpyAsync(pin[i & 1], d_out[i & 1], bytes[i & 1], hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
+			    hipEventRecord(arrived.e[i & 1], nullptr) != hipSuccess) { wrote_ok = false; break; }
+		}
+		if (i > 0) {
+			if (hipEventSynchronize(arrived.e[(i - 1) & 1]) != hipSuccess) { wrote_ok = false; break; }   // piece i - 1 has arrived, whatever stream the context works on
+			const double tw = now_ms();
+			if (fwrite(pin[(i - 1) & 1], 1, bytes[(i - 1) & 1], out) != bytes[(i - 1) & 1]) wrote_ok = false;
+			g_times[5] += now_ms() - tw;
+		}
+	}
+	(void)hipStreamSynchronize(nullptr);
+	if (fclose(out) != 0) wrote_ok = false;
+	if (!wrote_ok) { remove(out_path); return -1; }
+	g_times[4] = now_ms() - t0;
+	if (n_out) *n_out = n_rows;
+	return 0;
+}
+
 // ---- verification: the rows of phase B against the reads of the FASTQ file(s), both in HBM (csrc/verify.hip) ----
 // Side a is the input, side b the archive: `missing` are reads of the input that the archive does not give back.
 int compare_rows(Mode mode, Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L, const uint8_t *d_in, uint64_t n_in, int L_in, mcomh_verify_report *rep)
@@ -440,6 +489,13 @@ int verify(const char *folder, int mode, const char *fastq1, const char *fastq2,
 extern "C" int mcomh_decompress_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(DEFAULT, folder, out_path, nullptr, n_reads, device); }
 extern "C" int mcomh_decompress_order_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(ORDER, folder, out_path, nullptr, n_reads, device); }
 extern "C" int mcomh_decompress_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device) { return guarded(PE, folder, out_path1, out_path2, n_pairs, device); }
+extern "C" int mcomh_decompress_fastq_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device)
+{
+	if (!folder || !out_path) return -1;
+	try {
+		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) { return write_fastq(A, folder, table, n_rows, L, out_path, n_reads); });
+	} catch (...) { return -1; }
+}
 extern "C" void mcomh_decompress_gpu_times(double *ms8) { if (ms8) memcpy(ms8, g_times, sizeof(g_times)); }
 extern "C" int mcomh_verify_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
 {

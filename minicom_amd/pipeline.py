@@ -99,6 +99,19 @@ def load_host_library():
     L.mcomh_bwt_stages.restype = i32; L.mcomh_bwt_stages.argtypes = [vp, u64, vp, vp, vp]
     L.mcomh_bwt_pack_file.restype = i32; L.mcomh_bwt_pack_file.argtypes = [cp, cp, i32]
     L.mcomh_bwt_unpack_file.restype = i32; L.mcomh_bwt_unpack_file.argtypes = [cp, cp, i32]
+    u32 = C.c_uint32
+    L.mcomh_qual_bound.restype = u64; L.mcomh_qual_bound.argtypes = [u64, u32]
+    L.mcomh_qual_info.restype = i32; L.mcomh_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u32)]
+    L.mcomh_qual_estimate.restype = i32; L.mcomh_qual_estimate.argtypes = [vp, u64, u32, u64, C.POINTER(u64)]
+    L.mcomh_qual_encode.restype = i32; L.mcomh_qual_encode.argtypes = [vp, u64, u32, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcomh_qual_decode.restype = i32; L.mcomh_qual_decode.argtypes = [vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(u32)]
+    L.mcomh_fastq_qualities_to_device.restype = i32
+    L.mcomh_fastq_qualities_to_device.argtypes = [cp, i32, i32, sz, C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
+    L.mcomh_fastq_quality_member.restype = i32; L.mcomh_fastq_quality_member.argtypes = [cp, i32, i32, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_device_copy.restype = i32; L.mcomh_device_copy.argtypes = [vp, vp, sz]
+    L.mcomh_decompress_fastq.restype = i32; L.mcomh_decompress_fastq.argtypes = [cp, cp, C.POINTER(u64)]
+    L.mcomh_decompress_fastq_gpu.restype = i32; L.mcomh_decompress_fastq_gpu.argtypes = [cp, cp, C.POINTER(u64), i32]
+    L.mcomh_verify_quality_gpu.restype = i32; L.mcomh_verify_quality_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport)]
     _lib = L
     return L
 
@@ -117,6 +130,10 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     # the block-sorting coder (host/mcom_bwt.cpp)
                     "mcomh_bwt_bound", "mcomh_bwt_encode", "mcomh_bwt_decode", "mcomh_bwt_raw_len", "mcomh_bwt_stages", "mcomh_bwt_pack_file",
                     "mcomh_bwt_unpack_file",
+                    # quality values (host/mcom_qual.cpp)
+                    "mcomh_qual_bound", "mcomh_qual_info", "mcomh_qual_estimate", "mcomh_qual_encode", "mcomh_qual_decode",
+                    "mcomh_qual_pack_file", "mcomh_qual_unpack_file", "mcomh_fastq_quality_member", "mcomh_device_copy",
+                    "mcomh_fastq_qualities_to_device", "mcomh_decompress_fastq", "mcomh_decompress_fastq_gpu", "mcomh_verify_quality_gpu",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -203,6 +220,127 @@ def rans_decode(member: bytes, cap: int | None = None) -> bytes:
     if rc:
         raise McomError(f"rans_decode: error {rc}: not a complete, intact .rans member")
     return out.raw[:got.value]
+
+
+def fastq_qualities(path: str, L: int, device: int = 0, piece_bytes: int = 0):
+    """mcomh_fastq_qualities_to_device: the quality lines of a four-line FASTQ file (plain or .gz) as a uint8 device tensor [n, L].
+    piece_bytes: the size of the two page-locked pieces the text goes up through (0 = 32 MiB; a request below 4 * (2 L + 64) bytes is
+    raised to that -- 552 bytes at L = 37 -- so that a piece holds a few records; tests pass small sizes so that records straddle pieces).  McomError, naming the first bad record, for a file the kernel flags."""
+    import torch
+    lib = load_host_library()
+    err = C.create_string_buffer(320)
+    d, n = C.c_void_p(), C.c_size_t()
+    if lib.mcomh_fastq_qualities_to_device(os.fsencode(path), int(device), int(L), int(piece_bytes), C.byref(d), C.byref(n), err, 320):
+        raise McomError(f"{path}: {err.value.decode() or 'cannot read the qualities'}")
+    try:
+        out = torch.empty((int(n.value), int(L)), dtype=torch.uint8, device=f"cuda:{int(device)}")
+        if n.value:
+            if lib.mcomh_device_copy(out.data_ptr(), d, int(n.value) * int(L)):
+                raise McomError("fastq_qualities: copy failed")
+    finally:
+        lib.mcomh_device_free(d)
+    return out
+
+
+def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None = None) -> int:
+    """mcomh_fastq_quality_member: the quality lines of a four-line FASTQ file -> the `.mcq` member file out_path; returns the number of
+    records.  device=None: the host twin (same record rules, same member); an integer: gathered and coded on that GPU."""
+    err = C.create_string_buffer(320)
+    n = C.c_uint64()
+    if load_host_library().mcomh_fastq_quality_member(os.fsencode(fastq), int(L), -1 if device is None else int(device), os.fsencode(out_path), C.byref(n), err, 320):
+        raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
+    return int(n.value)
+
+
+def decompress_fastq(folder: str, out_path: str, device: int | None = None) -> int:
+    """mcomh_decompress_fastq(_gpu): the stream files of a -p -Q archive and its qual.mcq -> records `@<i+1>`, read, `+`, qualities.
+    Returns the number of records.  device=None: the host route; an integer: reads and qualities rebuilt and the records laid out on
+    that GPU (the same bytes; an error, never the host route, when there is no such GPU)."""
+    n = C.c_uint64()
+    lib = load_host_library()
+    rc = lib.mcomh_decompress_fastq(os.fsencode(folder), os.fsencode(out_path), C.byref(n)) if device is None else \
+        lib.mcomh_decompress_fastq_gpu(os.fsencode(folder), os.fsencode(out_path), C.byref(n), int(device))
+    if rc:
+        raise McomError(f"cannot decode {folder} to FASTQ" + ("" if device is None else f" on GPU {device}") + ": not a -p archive with qual.mcq, or a refused member")
+    return int(n.value)
+
+
+def verify_quality(folder: str, fastq: str, device: int = 0) -> dict:
+    """mcomh_verify_quality_gpu: does folder/qual.mcq give back exactly the quality lines of `fastq`, line against line?  Decided on GPU
+    `device`, nothing is written.  McomError when no comparison could be made; a difference is a verdict, not an error."""
+    r = VerifyReport()
+    if load_host_library().mcomh_verify_quality_gpu(os.fsencode(folder), os.fsencode(fastq), int(device), C.byref(r)):
+        raise McomError(f"cannot verify the qualities in {folder} against {fastq} on GPU {device}")
+    return {"identical": bool(r.identical), "n_input": int(r.n_input), "n_archive": int(r.n_archive), "differing": int(r.differing),
+            "first_diff": None if r.first_diff == 2 ** 64 - 1 else int(r.first_diff),
+            "times_ms": {"ingest": r.times_ms[0], "decode": r.times_ms[2], "compare": r.times_ms[3], "total": r.times_ms[4]}}
+
+
+QUAL_MODELS = ("stored", "order-0", "P", "PP", "PMP")     # the model ids of a `.mcq` member (DESIGN.md section 3.9)
+QUAL_HINT_RANS = 0x180
+
+
+def qual_hint(model) -> int:
+    """MCOM_QUAL_HINT of include/mcom.h: None = choose, 0 .. 4 = that model id, "rans" = the embedded `.rans` member"""
+    return 0 if model is None else QUAL_HINT_RANS if model == "rans" else 0x100 | int(model)
+
+
+def qual_encode(rows, model=None) -> bytes:
+    """mcomh_qual_encode, the host twin of the GPU coder: a uint8 matrix [n, L] (1 <= L <= 256; rows may be strided) -> a `.mcq`
+    member.  model None: chosen by estimated size, and the embedded `.rans` member where that is smaller; 0 .. 4 or "rans" force one."""
+    import numpy as np
+    lib = load_host_library()
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.dtype != np.uint8 or (rows.shape[0] and rows.strides[1] != 1):
+        raise McomError("qual_encode: a uint8 matrix with contiguous rows")
+    n, L = int(rows.shape[0]), int(rows.shape[1])
+    pitch = int(rows.strides[0]) if n > 1 else L
+    cap = int(lib.mcomh_qual_bound(n, L))
+    if not cap or pitch < L:
+        raise McomError("qual_encode: rows of %d bytes" % L)
+    out = C.create_string_buffer(cap)
+    got = C.c_uint64()
+    rc = lib.mcomh_qual_encode(rows.ctypes.data if n else None, n, L, pitch, out, cap, C.byref(got), qual_hint(model))
+    if rc:
+        raise McomError(f"qual_encode: error {rc}")
+    return out.raw[:got.value]
+
+
+def qual_info(member: bytes) -> tuple[int, int]:
+    """mcomh_qual_info: (n_rows, L) a `.mcq` member's header states; McomError when the first 64 bytes are not such a header"""
+    n, L = C.c_uint64(), C.c_uint32()
+    head = bytes(member[:64])
+    if load_host_library().mcomh_qual_info((C.c_char * len(head)).from_buffer_copy(head) if head else None, len(member), C.byref(n), C.byref(L)):
+        raise McomError("qual_info: not a .mcq member")
+    return int(n.value), int(L.value)
+
+
+def qual_decode(member: bytes, pitch: int | None = None):
+    """mcomh_qual_decode: a `.mcq` member -> the uint8 matrix [n, L] (a view of rows `pitch` apart when given); McomError for a member
+    that is truncated, malformed or fails its CRC-32."""
+    import numpy as np
+    lib = load_host_library()
+    member = bytes(member)
+    n, L = qual_info(member)
+    pitch = L if pitch is None else int(pitch)
+    if pitch < L or n * pitch > 1 << 40:
+        raise McomError("qual_decode: %d rows of %d bytes at pitch %d" % (n, L, pitch))
+    buf = np.zeros(max(n * pitch, 1), dtype=np.uint8)
+    gn, gL = C.c_uint64(), C.c_uint32()
+    rc = lib.mcomh_qual_decode((C.c_char * len(member)).from_buffer_copy(member), len(member), buf.ctypes.data, pitch, n, C.byref(gn), C.byref(gL))
+    if rc:
+        raise McomError(f"qual_decode: error {rc}: not a complete, intact .mcq member")
+    return buf[:n * pitch].reshape(n, pitch)[:, :L]
+
+
+def qual_estimate(rows) -> list[int]:
+    """mcomh_qual_estimate: the estimated coded size under every model id, in the order of QUAL_MODELS"""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    est = (C.c_uint64 * 5)()
+    if load_host_library().mcomh_qual_estimate(rows.ctypes.data if rows.size else None, rows.shape[0], rows.shape[1], rows.shape[1], est):
+        raise McomError("qual_estimate: rows of %d bytes" % rows.shape[1])
+    return [int(v) for v in est]
 
 
 def rans_estimate(data: bytes) -> list[int]:
