@@ -788,12 +788,56 @@ enum mcom_fastq_flag {
 	MCOM_FASTQ_F_NAME = 1,      /* line 4r is empty or does not start with '@'                                          */
 	MCOM_FASTQ_F_PLUS = 2,      /* line 4r + 2 is empty or does not start with '+'                                      */
 	MCOM_FASTQ_F_LENGTH = 4,    /* line 4r + 1 or line 4r + 3 is not exactly L bytes long                               */
-	MCOM_FASTQ_F_CHAR = 8       /* a quality byte outside 33 .. 126                                                     */
+	MCOM_FASTQ_F_CHAR = 8,      /* a quality byte outside 33 .. 126                                                     */
+	MCOM_FASTQ_F_LONG = 16      /* mcom_fastq_name_text: more than 255 bytes behind the '@' or the '+'                  */
 };
 int mcom_fastq_quality_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
                             uint64_t n_records, uint32_t L, uint8_t *d_rows, uint64_t pitch, uint32_t *d_flag);
 int mcom_fastq_emit(mcom_ctx *ctx, const uint8_t *d_reads, uint64_t read_pitch, const uint8_t *d_quals, uint64_t qual_pitch, uint64_t first,
                     uint64_t count, uint32_t L, uint8_t *d_out, uint64_t *bytes);
+
+/* ---- read names and '+' lines: `.mcn` members (csrc/names.hip; format and host twin: DESIGN.md section 3.10, include/mcom_host.h) ----
+ * The name text of n records is 2 n lines: line 1 of a record without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at
+ * most 255 bytes a line.  Names are cut into digit runs and other runs, every token coded against the same token of the record before
+ * (segments of 256 records decode alone), seven streams each through mcom_bwt_encode; the `.rans` member of the text is made as well and
+ * embedded where that is smaller.  Device pointers at any address, work on the context's stream, all calls synchronous.  The bytes
+ * equal those of mcomh_name_encode.
+ *   mcom_name_bound   room that is enough for a name text of text_len bytes
+ *   mcom_name_encode  MCOM_E_ARG for a text that is not 2 n complete lines, for a line above 255 bytes (*bad_record, may be NULL: the
+ *                     first such record, ~0 otherwise; the message names it), for more than 171 798 691 records and for a text or a stream
+ *                     of 4 GiB or more (they are refused, not split); MCOM_E_OVERFLOW when cap is too small (nothing valid in d_out)
+ *   mcom_name_info    plain host code: n_records and text_len from the first 96 bytes of a member that the host holds (-1: not a header)
+ *   mcom_name_decode  *text_len, *n_records = the member's.  d_rec_off (may be NULL; n_records + 1 entries): the offset of every record in
+ *                     the name text, the last one text_len.  MCOM_E_OVERFLOW (with both set) when cap is too small; MCOM_E_ARG for every
+ *                     member section 3.10 refuses -- d_text then holds nothing valid.  Untrusted input never makes a kernel leave its
+ *                     buffers (it raises a flag word and skips the access).
+ *   mcom_name_text_offsets  the record offsets (n + 1 entries, the last one text_len) of a name text that did not come out of
+ *                     mcom_name_decode; MCOM_E_ARG when it is not 2 n complete lines of at most 255 bytes
+ *   mcom_name_compare two name texts with their record offsets (n + 1 entries each), record against record: *differing = the records
+ *                     that are not byte for byte the same, *first_diff = the lowest of them (~0: none)                               */
+uint64_t mcom_name_bound(uint64_t text_len);
+int mcom_name_encode(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n_records, uint8_t *d_out, uint64_t cap,
+                     uint64_t *out_len, uint64_t *bad_record);
+int mcom_name_info(const uint8_t *h_member_prefix, uint64_t len, uint64_t *n_records, uint64_t *text_len);
+int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_text, uint64_t cap, uint64_t *text_len,
+                     uint64_t *n_records, uint64_t *d_rec_off);
+int mcom_name_text_offsets(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n_records, uint64_t *d_rec_off);
+int mcom_name_compare(mcom_ctx *ctx, const uint8_t *d_a, const uint64_t *d_off_a, uint64_t bytes_a, const uint8_t *d_b,
+                      const uint64_t *d_off_b, uint64_t bytes_b, uint64_t n, uint64_t *differing, uint64_t *first_diff);
+/* The FASTQ ends of the name coder, siblings of mcom_fastq_quality_rows / mcom_fastq_emit over the same line index.
+ * mcom_fastq_name_text: the name text of the n_records records of a piece of FASTQ text.  d_rec_off (n_records + 1 entries) gets the
+ * offset of every record in it, *bytes its length -- also when d_names is NULL (nothing is copied then: the way to size d_names);
+ * MCOM_E_OVERFLOW when cap is below *bytes.  d_flag: two words as for mcom_fastq_quality_rows; MCOM_FASTQ_F_NAME, _PLUS and _LONG
+ * are raised, a flagged record takes no room in the name text.
+ * mcom_fastq_emit_named: `count` records `@<name>\n<read>\n+<text>\n<qualities>\n` back to back into d_out.  d_reads / d_quals point
+ * at the rows of the first of them, d_rec_off (count + 1 entries) at its entry of the offsets of the name text d_names (names_bytes
+ * long; what mcom_name_decode gives).  Record r lies at (2 L + 4) r + d_rec_off[r] - d_rec_off[0].  *bytes = their length, also when
+ * d_out is NULL (nothing is launched then).  Offsets that do not describe two lines of at most 255 bytes are MCOM_E_ARG.              */
+int mcom_fastq_name_text(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
+                         uint64_t n_records, uint8_t *d_names, uint64_t cap, uint64_t *bytes, uint64_t *d_rec_off, uint32_t *d_flag);
+int mcom_fastq_emit_named(mcom_ctx *ctx, const uint8_t *d_reads, uint64_t read_pitch, const uint8_t *d_quals, uint64_t qual_pitch,
+                          const uint8_t *d_names, uint64_t names_bytes, const uint64_t *d_rec_off, uint64_t count, uint32_t L,
+                          uint8_t *d_out, uint64_t *bytes);
 
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,

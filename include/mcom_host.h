@@ -316,6 +316,43 @@ int mcomh_decompress_fastq(const char *folder, const char *out_path, uint64_t *n
 int mcomh_decompress_fastq_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device);
 int mcomh_verify_quality_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep);
 
+/* ---- read names and '+' lines: `.mcn` members (host/mcom_names.cpp) ----
+ * The host twin of mcom_name_encode / mcom_name_decode (include/mcom.h).  The name text of n records is 2 n lines: line 1 of a record
+ * without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at most 255 bytes a line.  Names are cut into tokens and coded
+ * against the record before; seven streams, each a `.bwt` member, or the `.rans` member of the text where that is smaller.  Plain C++,
+ * no GPU; the same bytes out as the device route, the same members accepted and refused.  Return values as for the rANS calls.
+ *   mcomh_name_bound    room that is enough for a name text of text_len bytes
+ *   mcomh_name_info     n_records and text_len from the first 96 bytes of a member (-1: not a `.mcn` header)
+ *   mcomh_name_encode   -1 for a text that is not 2 n complete lines or holds a line above 255 bytes: *bad_record (may be NULL) is then
+ *                       the first record with such a line, ~0 otherwise
+ *   mcomh_name_decode   *text_len and *n_records are set also when it returns -4 (text_len above cap)
+ * File forms (bin/mcomz e --names, d): a file of name text <-> a `.mcn` member; device = -1 the host twin, otherwise that GPU (an error,
+ * never the host twin, when there is no such GPU).  No output file is left by a call that fails.                                     */
+uint64_t mcomh_name_bound(uint64_t text_len);
+int mcomh_name_info(const uint8_t *prefix, uint64_t len, uint64_t *n_records, uint64_t *text_len);
+int mcomh_name_encode(const uint8_t *text, uint64_t text_len, uint64_t n_records, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                      uint64_t *bad_record);
+int mcomh_name_decode(const uint8_t *in, uint64_t in_len, uint8_t *text, uint64_t cap, uint64_t *text_len, uint64_t *n_records);
+int mcomh_name_pack_file(const char *in_path, const char *out_path, int device);
+int mcomh_name_unpack_file(const char *in_path, const char *out_path, int device);
+/* ---- `minicom -N`: a -p -Q archive that also carries read names and '+' texts, as the member name.mcn in input order ----
+ *   mcomh_fastq_names_to_device  the name text of a four-line FASTQ file (plain or .gz) in HBM (*d_names, *bytes long; release with
+ *                                mcomh_device_free; *n records), through two page-locked pieces of piece_bytes (0 = 32 MiB) with the
+ *                                unfinished record of a piece in front of the next, as mcomh_fastq_qualities_to_device; lines by
+ *                                mcom_decode_line_index, records checked and gathered by mcom_fastq_name_text.  A record without '@' or
+ *                                '+', or with more than 255 bytes behind either, is an error whose message names the first one.
+ *   mcomh_fastq_name_member      FASTQ file -> the `.mcn` member file (what `minicom -N` runs, bin/mcomz e --fastq-names): on GPU `device`
+ *                                the call above and mcom_name_encode; device = -1 a host twin of the record rules and mcomh_name_encode.
+ *                                The same member either way; *n = the records; no output file is left by a call that fails.  This is a
+ *                                pass over the file of its own, beside the one that makes qual.mcq.
+ *   mcomh_verify_names_gpu       name.mcn decoded on the device against the name text of `fastq`, record against record
+ *                                (mcom_name_compare); the report's mode is 1.  Returns 0 when a comparison was made.
+ * mcomh_decompress_fastq[_gpu] pick folder/name.mcn up by themselves: the records then carry its names and '+' texts.  They refuse a
+ * name.mcn that states another n than the reads, one without qual.mcq, and a refused member; no output file is left then.             */
+int mcomh_fastq_names_to_device(const char *path, int device, size_t piece_bytes, uint8_t **d_names, uint64_t *bytes, size_t *n, char *err, size_t err_cap);
+int mcomh_fastq_name_member(const char *fastq, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap);
+int mcomh_verify_names_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

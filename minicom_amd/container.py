@@ -40,6 +40,7 @@ GROUPS = (
     ("filebin", ("file.bin.*",)),                    # :259-262, paired end only
 )
 SINGLES = ("single_N.seq", "single.seq", "AA.txt", "TT.txt", "NN.txt")      # :136-137, :144-146
+NAME_MEMBER = "name.mcn"          # read names and '+' texts of a -p -Q archive: stored as it is
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -149,6 +150,9 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
     if os.path.isfile(os.path.join(folder, QUALITY_MEMBER)):     # coded already: stored as it is, no codec on top
         with open(os.path.join(folder, QUALITY_MEMBER), "rb") as f:
             packed.append((QUALITY_MEMBER, f.read()))
+    if os.path.isfile(os.path.join(folder, NAME_MEMBER)):        # likewise (section 3.10)
+        with open(os.path.join(folder, NAME_MEMBER), "rb") as f:
+            packed.append((NAME_MEMBER, f.read()))
     sizes = {}
     with tarfile.open(out_path, mode="w", format=tarfile.GNU_FORMAT) as t:
         with open(os.path.join(folder, "info.txt"), "rb") as f:
@@ -174,7 +178,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt" or name == QUALITY_MEMBER:
+        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -192,6 +196,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
     for name, data in plain:
         if name == QUALITY_MEMBER:
             kinds["quality"] = True
+        if name == NAME_MEMBER:
+            kinds["names"] = True
         if name.startswith("idsbin.tar"):
             kinds["order"] = True
         if name.startswith("filebin.tar"):
@@ -211,18 +217,21 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
-                   device: int = 0, threads: int = 8, quality: bool = False, **params) -> dict:
+                   device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
     belongs to which read): the quality lines are gathered and coded on `device` and travel as the member qual.mcq.  Read names and the
-    text of the `+` line are not kept.  Returns pack()'s member sizes plus the read count."""
+    text of the `+` line are not kept, unless names=True (`minicom -N`; needs order=True and quality=True): they travel as the member
+    name.mcn, coded on `device`, and decompress_file then gives the input file back byte for byte.  Returns pack()'s member sizes plus the read count."""
     import tempfile
     from .pipeline import Pipeline
     if order and path2 is not None:
         raise ValueError("-p is a single-end option (reference minicom:439-476)")
     if quality and (not order or path2 is not None):
         raise ValueError("quality values are kept by the order-preserving single-end mode only (order=True, no path2)")
+    if names and not (order and quality):
+        raise ValueError("names are kept beside the quality values of an order-preserving archive only (order=True, quality=True)")
     p = Pipeline.from_fastq(path, device=device, path2=path2, host_threads=threads, **params)
     try:
         p.pre_process()
@@ -230,6 +239,11 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
             p.cluster_dump(td, order=order, paired=path2 is not None)
             if quality:
                 _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER))
+            if names:
+                from .pipeline import fastq_name_member
+                n_names = fastq_name_member(path, os.path.join(td, NAME_MEMBER), device=device)
+                if n_names != p.n:
+                    raise McomError("%s: %d names for %d reads" % (path, n_names, p.n))
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         return sizes
@@ -254,7 +268,8 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
     pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
     integer: `.rans` and `.bwt` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
     are host code either way.  An archive with quality values (compress_fastq(quality=True)) gives FASTQ instead: four-line records
-    `@<i+1>`, read, `+`, qualities."""
+    `@<i+1>`, read, `+`, qualities -- or, for an archive that carries name.mcn (compress_fastq(names=True)), the records with their names
+    and `+` texts: the input file."""
     import tempfile
     from .pipeline import decompress, decompress_fastq, decompress_pe
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
@@ -272,7 +287,8 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
     """`.minicom` against the FASTQ it was made from, on GPU `device`, without writing a read: pipeline.verify's report.  The mode comes
     from the members, as in decompress_file: a paired-end archive needs `fastq2`, a -p archive is held line against line, any other
     one as a multiset of reads.  An archive with quality values is held against the quality lines as well: the report gets
-    "quality" (pipeline.verify_quality's) and "identical" is true only when both checks say so."""
+    "quality" (pipeline.verify_quality's) and "identical" is true only when both checks say so; one with names likewise gets "names"
+    (pipeline.verify_names's)."""
     import tempfile
     from .hip import McomError
     from .pipeline import verify, verify_quality
@@ -286,4 +302,8 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
         if kinds.get("quality"):
             rep["quality"] = verify_quality(td, fastq, device=device)
             rep["identical"] = rep["identical"] and rep["quality"]["identical"]
+        if kinds.get("names"):
+            from .pipeline import verify_names
+            rep["names"] = verify_names(td, fastq, device=device)
+            rep["identical"] = rep["identical"] and rep["names"]["identical"]
         return rep

@@ -176,6 +176,14 @@ def load_library():
     L.mcom_qual_encode.restype = i32; L.mcom_qual_encode.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, C.POINTER(u64), i32]
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.mcom_name_bound.restype = u64; L.mcom_name_bound.argtypes = [u64]
+    L.mcom_name_encode.restype = i32; L.mcom_name_encode.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_name_info.restype = i32; L.mcom_name_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_name_decode.restype = i32; L.mcom_name_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
+    L.mcom_name_text_offsets.restype = i32; L.mcom_name_text_offsets.argtypes = [vp, vp, u64, u64, vp]
+    L.mcom_name_compare.restype = i32; L.mcom_name_compare.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_fastq_name_text.restype = i32; L.mcom_fastq_name_text.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp]
+    L.mcom_fastq_emit_named.restype = i32; L.mcom_fastq_emit_named.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
     L.mcom_bwt_bound.restype = u64; L.mcom_bwt_bound.argtypes = [u64]
     L.mcom_bwt_encode.restype = i32; L.mcom_bwt_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.mcom_bwt_decode.restype = i32; L.mcom_bwt_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -1033,6 +1041,89 @@ class Context:
         counts = torch.empty(a * q * 8 * a, dtype=torch.int64, device=self.device)
         self._check(self.lib.mcom_test_qual_hist(self._h, rows.data_ptr(), n, L, pitch, hmap, C.byref(A), self._p(counts)))
         return hmap.raw, a, counts.view(a, q, 8, a)
+
+    # ---- read names and '+' lines (csrc/names.hip) ----
+    def name_encode(self, text, n_records: int, out=None):
+        """mcom_name_encode.  text: uint8 device tensor holding the name text of n_records records (two lines each, any address).
+        Returns the `.mcn` member as a uint8 device tensor; McomError names the first record with a line above
+        255 bytes.  out: a uint8 device tensor to write the member into."""
+        torch = _torch()
+        n = int(text.shape[0])
+        cap = int(out.shape[0]) if out is not None else int(self.lib.mcom_name_bound(n))
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        got, bad = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mcom_name_encode(self._h, self._p(text, torch.uint8) if n else None, n, int(n_records), self._p(out), cap, C.byref(got), C.byref(bad)))
+        return out[:got.value]
+
+    def name_decode(self, member, out=None):
+        """mcom_name_decode.  member: uint8 device tensor.  Returns (the name text as a uint8 device tensor, the offset of every record
+        in it as an int64 device tensor of n_records + 1 entries); McomError for every member section 3.10 refuses.  out: a uint8
+        device tensor to decode into (its length is the room offered)."""
+        torch = _torch()
+        n_in = int(member.shape[0])
+        head = bytes(member[:96].cpu().numpy())
+        n, t = C.c_uint64(), C.c_uint64()
+        if self.lib.mcom_name_info(head if head else None, n_in, C.byref(n), C.byref(t)):
+            raise McomError("name_decode: not a .mcn member")
+        n, t = int(n.value), int(t.value)
+        if out is None:
+            out = torch.empty(max(t, 1), dtype=torch.uint8, device=self.device)
+        off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        gt, gn = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mcom_name_decode(self._h, self._p(member, torch.uint8), n_in, self._p(out, torch.uint8), int(out.shape[0]), C.byref(gt), C.byref(gn), self._p(off)))
+        return out[:t], off
+
+    def name_compare(self, text_a, off_a, text_b, off_b):
+        """mcom_name_compare.  Two name texts (uint8 device tensors) with their record offsets (int64 device tensors of n + 1 entries).
+        Returns (the number of records that differ, the lowest of them or None)."""
+        torch = _torch()
+        n = int(off_a.shape[0]) - 1
+        if int(off_b.shape[0]) - 1 != n or off_a.dtype != torch.int64 or off_b.dtype != torch.int64:
+            raise McomError("name_compare: two int64 offset arrays of one length")
+        d, f = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mcom_name_compare(self._h, self._p(text_a, torch.uint8), self._p(off_a), int(text_a.shape[0]), self._p(text_b, torch.uint8), self._p(off_b),
+                                               int(text_b.shape[0]), n, C.byref(d), C.byref(f)))
+        return int(d.value), (None if f.value == 0xFFFFFFFFFFFFFFFF else int(f.value))
+
+    def fastq_names(self, text, first_record: int = 0):
+        """mcom_decode_line_index + mcom_fastq_name_text.  text: uint8 device tensor holding whole four-line records (every line ends
+        with a newline).  Returns (the name text uint8, record offsets int64 [n_records + 1], flag bits of MCOM_FASTQ_F_*, the first
+        flagged record or None); a flagged record takes no room in the name text."""
+        torch = _torch()
+        start, _ = self.decode_line_index(text)
+        n_rec = (int(start.shape[0]) - 1) // 4
+        off = torch.zeros(n_rec + 1, dtype=torch.int64, device=self.device)
+        flag = torch.tensor([0, -1], dtype=torch.int32, device=self.device)
+        nb = C.c_uint64()
+        self._check(self.lib.mcom_fastq_name_text(self._h, self._p(text, torch.uint8) if n_rec else None, int(text.shape[0]), self._p(start), first_record, n_rec, None, 0,
+                                                  C.byref(nb), self._p(off), self._p(flag)))
+        out = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=self.device)
+        flag = torch.tensor([0, -1], dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_fastq_name_text(self._h, self._p(text, torch.uint8) if n_rec else None, int(text.shape[0]), self._p(start), first_record, n_rec, self._p(out),
+                                                  int(out.shape[0]), C.byref(nb), self._p(off), self._p(flag)))
+        f = flag.cpu().numpy().view(np.uint32)
+        return out[:nb.value], off, int(f[0]), (None if f[1] == 0xFFFFFFFF else int(f[1]))
+
+    def fastq_emit_named(self, reads, quals, names, rec_off, first: int = 0):
+        """mcom_fastq_emit_named.  reads, quals: uint8 device matrices [count, >= L] with contiguous rows: the rows of records first ..
+        first + count - 1.  names, rec_off: a name text and the offsets of ALL its records (what name_decode returns).  Returns the
+        records `@<name>`, read, `+<text>`, qualities as one uint8 device tensor."""
+        torch = _torch()
+        count, L = int(quals.shape[0]), int(quals.shape[1])
+        if int(reads.shape[0]) != count or int(reads.shape[1]) != L or (count and (reads.stride(1) != 1 or quals.stride(1) != 1)):
+            raise McomError("fastq_emit_named: reads and qualities of one shape, rows contiguous")
+        if rec_off.dtype != torch.int64 or first < 0 or first + count + 1 > int(rec_off.shape[0]):
+            raise McomError("fastq_emit_named: %d records from %d need %d int64 offsets" % (count, first, first + count + 1))
+        rp = int(reads.stride(0)) if count > 1 else L
+        qp = int(quals.stride(0)) if count > 1 else L
+        off = rec_off[first:]
+        nb = C.c_uint64()
+        self._check(self.lib.mcom_fastq_emit_named(self._h, None, rp, None, qp, None, int(names.shape[0]), self._p(off), count, L, None, C.byref(nb)))
+        out = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.mcom_fastq_emit_named(self._h, reads.data_ptr() if count else None, rp, quals.data_ptr() if count else None, qp, self._p(names, torch.uint8),
+                                                   int(names.shape[0]), self._p(off), count, L, self._p(out), C.byref(nb)))
+        return out[:nb.value]
 
     # ---- the block-sorting coder (csrc/bwt.hip) ----
     def bwt_encode(self, raw, out=None):

@@ -8,6 +8,8 @@
 // with the reads of the FASTQ file(s) (mcomh_verify_gpu).  Exit status 0 identical, 2 different, 1 refused or error.
 // decompress --fastq [--gpu] DIR OUT.fastq: a -p -Q archive (DIR holds qual.mcq) back to four-line records `@<i+1>`, read, `+`, qualities.
 // decompress --verify-quality DIR IN.fastq: qual.mcq against the quality lines of the FASTQ on GPU 0; exit status as --verify.
+// decompress --verify-names DIR IN.fastq: name.mcn against the names and '+' texts of the FASTQ on GPU 0; exit status as --verify.
+// --fastq picks DIR/name.mcn up by itself (an archive made with -N): the records then carry the names and '+' texts.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
@@ -59,6 +61,18 @@ static int verify_quality(int argc, char **argv)
 	return 2;
 }
 
+static int verify_names(int argc, char **argv)
+{
+	if (argc < 3) { fprintf(stderr, "usage: decompress --verify-names DIR IN.fastq\n"); return 1; }
+	mcomh_verify_report r;
+	if (mcomh_verify_names_gpu(argv[1], argv[2], 0, &r)) { fprintf(stderr, "decompress: the names of %s could not be verified against %s\n", argv[1], argv[2]); return 1; }
+	if (r.identical) { printf("verified: the names and '+' lines of %llu records identical\n", (unsigned long long)r.n_input); return 0; }
+	printf("DIFFERENT: the FASTQ holds %llu records, the archive %llu\n  %llu records differ in their name or '+' line", (unsigned long long)r.n_input, (unsigned long long)r.n_archive, (unsigned long long)r.differing);
+	if (r.differing) printf(", the first one is record %llu (from 0)", (unsigned long long)r.first_diff);
+	printf("\n");
+	return 2;
+}
+
 static int fastq(int argc, char **argv)
 {
 	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
@@ -77,6 +91,7 @@ int main(int argc, char **argv)
 {
 	if (argc > 1 && !strcmp(argv[1], "--verify")) return verify(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify-quality")) return verify_quality(argc - 1, argv + 1);
+	if (argc > 1 && !strcmp(argv[1], "--verify-names")) return verify_names(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--fastq")) return fastq(argc - 1, argv + 1);
 	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
 	if (gpu) { --argc; ++argv; }

@@ -8,6 +8,10 @@
 // mcomz e --fastq-qual L [--gpu] IN.fastq OUT: the quality lines of a four-line FASTQ file (plain or .gz) of reads of L bases -> a `.mcq`
 // member; every record is checked ('@' line, '+' line, both lengths, quality bytes 33 .. 126) and the first bad one is named -- on the
 // GPU by the kernels behind mcomh_fastq_qualities_to_device, without --gpu by their host twin.  Prints the number of records.
+// mcomz e --names [--gpu] IN OUT: IN is a name text (per record its name and the text of its third line, a line each; DESIGN.md section
+// 3.10), OUT a `.mcn` member; a line above 255 bytes is refused and its record named.  d knows such a member by its magic.
+// mcomz e --fastq-names [--gpu] IN.fastq OUT: the names and '+' texts of a four-line FASTQ file (plain or .gz) -> a `.mcn` member; every
+// record is checked ('@' line, '+' line, at most 255 bytes behind either) and the first bad one is named.  Prints the number of records.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstdlib>
@@ -25,17 +29,19 @@ static bool has_magic(const char *path, const char *magic4)
 
 int main(int argc, char **argv)
 {
-	bool gpu = false, bwt = false;
+	bool gpu = false, bwt = false, names = false, fastq_names = false;
 	int at = 2, qual_L = 0, fastq_L = 0;
 	for (; at < argc; ++at) {
 		if (!strcmp(argv[at], "--gpu") && !gpu) gpu = true;
 		else if (!strcmp(argv[at], "--qual") && !qual_L && at + 1 < argc) { qual_L = atoi(argv[++at]); if (qual_L < 1 || qual_L > 256) { fprintf(stderr, "mcomz: --qual takes the row length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--fastq-qual") && !fastq_L && at + 1 < argc) { fastq_L = atoi(argv[++at]); if (fastq_L < 1 || fastq_L > 256) { fprintf(stderr, "mcomz: --fastq-qual takes the read length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--bwt") && !bwt) bwt = true;
+		else if (!strcmp(argv[at], "--names") && !names) names = true;
+		else if (!strcmp(argv[at], "--fastq-names") && !fastq_names) fastq_names = true;
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--gpu] IN.fastq OUT\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names))) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;
@@ -44,6 +50,17 @@ int main(int argc, char **argv)
 		if (mcomh_fastq_quality_member(in, fastq_L, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
 		printf("%llu\n", (unsigned long long)n);
 		return 0;
+	}
+	if (fastq_names) {
+		char err[320] = ""; uint64_t n = 0;
+		if (mcomh_fastq_name_member(in, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the names"); return 1; }
+		printf("%llu\n", (unsigned long long)n);
+		return 0;
+	}
+	if (names || (dec && has_magic(in, "MCNM"))) {
+		rc = enc ? mcomh_name_pack_file(in, out, device) : mcomh_name_unpack_file(in, out, device);
+		if (rc) fprintf(stderr, enc ? "mcomz: cannot pack %s into %s%s\n" : "mcomz: %s is not a complete, intact .mcn member, or %s cannot be written%s\n", in, out, gpu ? " (or the GPU route is not available)" : "");
+		return rc ? 1 : 0;
 	}
 	if (qual_L || (dec && has_magic(in, "MCQV"))) {
 		rc = enc ? mcomh_qual_pack_file(in, out, qual_L, device) : mcomh_qual_unpack_file(in, out, device);

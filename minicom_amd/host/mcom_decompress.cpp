@@ -394,7 +394,8 @@ extern "C" int mcomh_decompress_pe(const char *folder, const char *out_path1, co
 
 // ---- a -p -Q archive back to FASTQ on the host: the reads of decompress_order_impl in memory, the quality
 // rows of folder/qual.mcq by the host twin, then records `@<i+1>`, read, `+`, qualities.  The cross-check of mcomh_decompress_fastq_gpu:
-// the same bytes, the same archives refused (one that is not a -p archive, no qual.mcq, another n or L than the reads).
+// the same bytes, the same archives refused (one that is not a -p archive, no qual.mcq, another n or L than the reads).  With
+// folder/name.mcn (section 3.10) the records are `@<name>`, read, `+<text>`, qualities; a name.mcn of another n or a refused one is an error.
 static int decompress_fastq_impl(const char *folder, const char *out_path, uint64_t *n_reads)
 {
 	if (!folder || !out_path) return -1;
@@ -406,12 +407,30 @@ static int decompress_fastq_impl(const char *folder, const char *out_path, uint6
 	if (mcomh_qual_info(member.data(), member.size(), &qn, &qL) || qn != n || (int)qL != L) return -1;
 	std::vector<uint8_t> quals((size_t)n * (size_t)L + 1);
 	if (mcomh_qual_decode(member.data(), member.size(), quals.data(), (uint64_t)L, n, &qn, &qL) || qn != n || (int)qL != L) return -1;
+	// folder/name.mcn (`minicom -N`, section 3.10): the records carry its names and '+' texts; it must state the reads' number
+	std::vector<uint8_t> names; std::vector<uint64_t> name_at;
+	std::vector<uint8_t> nmember;
+	const bool named = slurp(std::string(folder) + "/name.mcn", nmember);
+	if (named) {
+		uint64_t nn = 0, tl = 0;
+		if (mcomh_name_info(nmember.data(), nmember.size(), &nn, &tl) || nn != n) return -1;
+		names.resize(tl + 1);
+		if (mcomh_name_decode(nmember.data(), nmember.size(), names.data(), tl, &tl, &nn) || nn != n) return -1;
+		name_at.reserve(2 * n + 1); name_at.push_back(0);
+		for (uint64_t i = 0; i < tl; ++i) if (names[i] == '\n') name_at.push_back(i + 1);
+		if (name_at.size() != 2 * n + 1) return -1;
+	}
 	FILE *out = fopen(out_path, "wb");
 	if (!out) return -1;
 	bool ok = true;
 	for (uint64_t i = 0; i < n && ok; ++i) {
-		ok = fprintf(out, "@%llu\n", (unsigned long long)(i + 1)) > 0 && fwrite(reads.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0 &&
-		     fwrite(quals.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
+		if (named) {
+			const uint64_t a = name_at[2 * i], b = name_at[2 * i + 1], c = name_at[2 * i + 2];
+			ok = fputc('@', out) != EOF && fwrite(names.data() + a, 1, b - a, out) == b - a && fwrite(reads.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+", out) >= 0 &&
+			     fwrite(names.data() + b, 1, c - b, out) == c - b;
+		} else
+			ok = fprintf(out, "@%llu\n", (unsigned long long)(i + 1)) > 0 && fwrite(reads.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0;
+		ok = ok && fwrite(quals.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
 	}
 	if (fclose(out) != 0 || !ok) { remove(out_path); return -1; }
 	if (n_reads) *n_reads = n;

@@ -378,6 +378,7 @@ int guarded(Mode mode, const char *folder, const char *o1, const char *o2, uint6
 
 // ---- a -p -Q archive back to FASTQ: the third tail.  folder/qual.mcq is decoded on the device (mcom_qual_decode), the records
 // `@<i+1>`, read, `+`, qualities are laid out by mcom_fastq_emit a piece at a time, the copy of piece i under the write of piece i - 1.
+// With folder/name.mcn the names and '+' texts are decoded on the device as well and mcom_fastq_emit_named lays the records out.
 int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out)
 {
 	std::vector<uint8_t> member;
@@ -387,8 +388,36 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	const uint8_t *d_member = A.upload(member.data(), member.size());
 	uint8_t *quals = A.alloc<uint8_t>(n_rows * (uint64_t)L);
 	if (mcom_qual_decode(A.ctx, d_member, member.size(), quals, (uint64_t)L, n_rows, &qn, &qL)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"qual.mcq is refused"}; }
+	// folder/name.mcn (`minicom -N`, section 3.10): decoded on the device too; the records then carry its names and '+' texts
+	std::vector<uint8_t> nmember;
+	const bool named = slurp(std::string(folder) + "/name.mcn", nmember);
+	uint8_t *d_names = nullptr; uint64_t *d_off = nullptr, names_bytes = 0;
+	std::vector<uint64_t> off;                                             // the record offsets of the name text, on the host: pieces are cut by them
+	if (named) {
+		uint64_t nn = 0;
+		if (mcom_name_info(nmember.data(), nmember.size(), &nn, &names_bytes) || nn != n_rows) throw Refuse{"name.mcn does not state the reads' number"};
+		const uint8_t *d_nm = A.upload(nmember.data(), nmember.size());
+		d_names = A.alloc<uint8_t>(names_bytes); d_off = A.alloc<uint64_t>(n_rows + 1);
+		if (mcom_name_decode(A.ctx, d_nm, nmember.size(), d_names, names_bytes, &names_bytes, &nn, d_off) || nn != n_rows) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"name.mcn is refused"}; }
+		off.resize(n_rows + 1);
+		if (hipMemcpy(off.data(), d_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+	}
 	const double t0 = now_ms();
-	const uint64_t rec_max = 2 * (uint64_t)L + 17, per_piece = PIECE_BYTES / rec_max, pieces = (n_rows + per_piece - 1) / per_piece;
+	const uint64_t rec_max = 2 * (uint64_t)L + 17, per_piece = PIECE_BYTES / rec_max;
+	// where every piece begins: a fixed number of records without names; with names the most records whose bytes fit a piece (bisection
+	// in the offset array: record r of a piece from `first` ends at (2 L + 4)(r + 1 - first) + off[r + 1] - off[first])
+	std::vector<uint64_t> piece_at(1, 0);
+	while (piece_at.back() < n_rows) {
+		const uint64_t first = piece_at.back();
+		uint64_t end = first + per_piece < n_rows ? first + per_piece : n_rows;
+		if (named) {
+			uint64_t lo = first + 1, hi = n_rows;                              // (one record always fits: at most 2 L + 4 + 512 bytes)
+			while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if ((2 * (uint64_t)L + 4) * (mid - first) + off[mid] - off[first] <= PIECE_BYTES) lo = mid; else hi = mid - 1; }
+			end = lo;
+		}
+		piece_at.push_back(end);
+	}
+	const uint64_t pieces = piece_at.size() - 1;
 	uint8_t *pin[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
 	for (int b = 0; b < 2; ++b) {
 		void *p = nullptr;
@@ -404,8 +433,11 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	uint64_t bytes[2] = {0, 0};
 	for (uint64_t i = 0; i <= pieces && wrote_ok; ++i) {
 		if (i < pieces) {
-			const uint64_t first = i * per_piece, count = n_rows - first < per_piece ? n_rows - first : per_piece;
-			if (mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, first, count, (uint32_t)L, d_out[i & 1], &bytes[i & 1]) ||
+			const uint64_t first = piece_at[i], count = piece_at[i + 1] - first;
+			const int rc = named ? mcom_fastq_emit_named(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, d_names, names_bytes, d_off + first, count,
+			                                             (uint32_t)L, d_out[i & 1], &bytes[i & 1])
+			                     : mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, first, count, (uint32_t)L, d_out[i & 1], &bytes[i & 1]);
+			if (rc ||
 			    bytes[i & 1] > PIECE_BYTES) { wrote_ok = false; break; }       // (synchronous on the context's stream: d_out[i & 1] is complete)
 			if (hipMemcpyAsync(pin[i & 1], d_out[i & 1], bytes[i & 1], hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
 			    hipEventRecord(arrived.e[i & 1], nullptr) != hipSuccess) { wrote_ok = false; break; }

@@ -112,6 +112,15 @@ def load_host_library():
     L.mcomh_decompress_fastq.restype = i32; L.mcomh_decompress_fastq.argtypes = [cp, cp, C.POINTER(u64)]
     L.mcomh_decompress_fastq_gpu.restype = i32; L.mcomh_decompress_fastq_gpu.argtypes = [cp, cp, C.POINTER(u64), i32]
     L.mcomh_verify_quality_gpu.restype = i32; L.mcomh_verify_quality_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_name_bound.restype = u64; L.mcomh_name_bound.argtypes = [u64]
+    L.mcomh_name_info.restype = i32; L.mcomh_name_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_name_encode.restype = i32; L.mcomh_name_encode.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_name_decode.restype = i32; L.mcomh_name_decode.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_fastq_names_to_device.restype = i32; L.mcomh_fastq_names_to_device.argtypes = [cp, i32, sz, C.POINTER(vp), C.POINTER(u64), C.POINTER(sz), C.c_char_p, sz]
+    L.mcomh_fastq_name_member.restype = i32; L.mcomh_fastq_name_member.argtypes = [cp, i32, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_verify_names_gpu.restype = i32; L.mcomh_verify_names_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_name_pack_file.restype = i32; L.mcomh_name_pack_file.argtypes = [cp, cp, i32]
+    L.mcomh_name_unpack_file.restype = i32; L.mcomh_name_unpack_file.argtypes = [cp, cp, i32]
     _lib = L
     return L
 
@@ -134,6 +143,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_qual_bound", "mcomh_qual_info", "mcomh_qual_estimate", "mcomh_qual_encode", "mcomh_qual_decode",
                     "mcomh_qual_pack_file", "mcomh_qual_unpack_file", "mcomh_fastq_quality_member", "mcomh_device_copy",
                     "mcomh_fastq_qualities_to_device", "mcomh_decompress_fastq", "mcomh_decompress_fastq_gpu", "mcomh_verify_quality_gpu",
+                    # read names and '+' lines (host/mcom_names.cpp)
+                    "mcomh_name_bound", "mcomh_name_info", "mcomh_name_encode", "mcomh_name_decode", "mcomh_name_pack_file",
+                    "mcomh_name_unpack_file", "mcomh_fastq_names_to_device", "mcomh_fastq_name_member", "mcomh_verify_names_gpu",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -341,6 +353,109 @@ def qual_estimate(rows) -> list[int]:
     if load_host_library().mcomh_qual_estimate(rows.ctypes.data if rows.size else None, rows.shape[0], rows.shape[1], rows.shape[1], est):
         raise McomError("qual_estimate: rows of %d bytes" % rows.shape[1])
     return [int(v) for v in est]
+
+
+def name_text(names, plus=None) -> bytes:
+    """The name text of records: per record its name (line 1 without '@'), a newline, the text of its third
+    line (without '+'; plus=None: bare everywhere), a newline."""
+    plus = [b""] * len(names) if plus is None else plus
+    return b"".join(bytes(a) + b"\n" + bytes(b) + b"\n" for a, b in zip(names, plus))
+
+
+def name_encode(text: bytes, n_records: int | None = None, device: int | None = None) -> bytes:
+    """A name text (name_text) -> a `.mcn` member.  device None: mcomh_name_encode, the host twin; an integer: mcom_name_encode on that
+    GPU (the same bytes; an error, never the host twin, when there is none).  n_records None: half the number of lines.  McomError
+    for a text that is not two complete lines per record; for a line above 255 bytes it names the record."""
+    text = bytes(text)
+    n = text.count(b"\n") // 2 if n_records is None else int(n_records)
+    if device is not None:
+        import torch
+        ctx = _device_context(device)
+        dev = f"cuda:{int(device)}"
+        raw = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(dev) if text else torch.empty(0, dtype=torch.uint8, device=dev)
+        return ctx.name_encode(raw, n).cpu().numpy().tobytes()
+    lib = load_host_library()
+    cap = int(lib.mcomh_name_bound(len(text)))
+    out = C.create_string_buffer(cap)
+    got, bad = C.c_uint64(), C.c_uint64()
+    rc = lib.mcomh_name_encode((C.c_char * len(text)).from_buffer_copy(text) if text else None, len(text), n, out, cap, C.byref(got), C.byref(bad))
+    if rc:
+        if bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise McomError(f"name_encode: record {bad.value + 1} has a name or a '+' text above 255 bytes")
+        raise McomError(f"name_encode: error {rc}: not the two lines of each of {n} records")
+    return out.raw[:got.value]
+
+
+def name_info(member: bytes) -> tuple[int, int]:
+    """mcomh_name_info: (n_records, text_len) a `.mcn` member's header states; McomError when the first 96 bytes are not such a header"""
+    n, t = C.c_uint64(), C.c_uint64()
+    head = bytes(member[:96])
+    if load_host_library().mcomh_name_info((C.c_char * len(head)).from_buffer_copy(head) if head else None, len(member), C.byref(n), C.byref(t)):
+        raise McomError("name_info: not a .mcn member")
+    return int(n.value), int(t.value)
+
+
+def name_decode(member: bytes, device: int | None = None) -> bytes:
+    """A `.mcn` member -> the name text, on the host twin or on that GPU; McomError for every member section 3.10 refuses."""
+    member = bytes(member)
+    n, t = name_info(member)
+    if device is not None:
+        import torch
+        ctx = _device_context(device)
+        text, _ = ctx.name_decode(torch.frombuffer(bytearray(member), dtype=torch.uint8).to(f"cuda:{int(device)}"))
+        return text.cpu().numpy().tobytes()
+    out = C.create_string_buffer(max(t, 1))
+    gt, gn = C.c_uint64(), C.c_uint64()
+    rc = load_host_library().mcomh_name_decode((C.c_char * len(member)).from_buffer_copy(member), len(member), out, t, C.byref(gt), C.byref(gn))
+    if rc:
+        raise McomError(f"name_decode: error {rc}: not a complete, intact .mcn member")
+    return out.raw[:t]
+
+
+def fastq_name_member(fastq: str, out_path: str, device: int | None = None) -> int:
+    """mcomh_fastq_name_member: the names and `+` texts of a four-line FASTQ file -> the `.mcn` member file out_path; returns the number
+    of records.  device None: the host twin of the record rules and of the coder; an integer: that GPU (an error when there is none).
+    McomError names the first record that has no `@` or `+` line or more than 255 bytes behind either; no file is left then."""
+    n = C.c_uint64(); err = C.create_string_buffer(320)
+    if load_host_library().mcomh_fastq_name_member(os.fsencode(fastq), -1 if device is None else int(device), os.fsencode(out_path), C.byref(n), err, 320):
+        raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the names'}")
+    return int(n.value)
+
+
+def fastq_names(path: str, device: int = 0, piece_bytes: int = 0) -> tuple[bytes, int]:
+    """mcomh_fastq_names_to_device: (the name text of a four-line FASTQ file, the number of records), gathered on GPU `device` through
+    pieces of piece_bytes (0 = 32 MiB) with the unfinished record of a piece carried in front of the next."""
+    lib = load_host_library()
+    d, nb, n = C.c_void_p(), C.c_uint64(), C.c_size_t()
+    err = C.create_string_buffer(320)
+    if lib.mcomh_fastq_names_to_device(os.fsencode(path), int(device), int(piece_bytes), C.byref(d), C.byref(nb), C.byref(n), err, 320):
+        raise McomError(f"{path}: {err.value.decode() or 'cannot read the names'}")
+    try:
+        import torch
+        out = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=f"cuda:{int(device)}")
+        if nb.value and lib.mcomh_device_copy(out.data_ptr(), d, int(nb.value)):
+            raise McomError("fastq_names: copy failed")
+        return out[:nb.value].cpu().numpy().tobytes(), int(n.value)
+    finally:
+        lib.mcomh_device_free(d)
+
+
+def verify_names(folder: str, fastq: str, device: int = 0) -> dict:
+    """mcomh_verify_names_gpu: does folder/name.mcn give back exactly the names and `+` texts of `fastq`, record against record?  Decided
+    on GPU `device`, nothing is written.  McomError when no comparison could be made; a difference is a verdict, not an error."""
+    r = VerifyReport()
+    if load_host_library().mcomh_verify_names_gpu(os.fsencode(folder), os.fsencode(fastq), int(device), C.byref(r)):
+        raise McomError(f"cannot verify the names in {folder} against {fastq} on GPU {device}")
+    return {"identical": bool(r.identical), "n_input": int(r.n_input), "n_archive": int(r.n_archive), "differing": int(r.differing),
+            "first_diff": None if r.first_diff == 2 ** 64 - 1 else int(r.first_diff)}
+
+
+def name_file(in_path: str, out_path: str, pack: bool, device: int | None = None) -> None:
+    """mcomh_name_pack_file / _unpack_file: a file of name text -> a `.mcn` member file or back; device None: the host twin."""
+    lib = load_host_library()
+    fn = lib.mcomh_name_pack_file if pack else lib.mcomh_name_unpack_file
+    if fn(os.fsencode(in_path), os.fsencode(out_path), -1 if device is None else int(device)):
+        raise McomError(f"cannot {'pack' if pack else 'unpack'} {in_path}" + ("" if device is None else f" on GPU {device}"))
 
 
 def rans_estimate(data: bytes) -> list[int]:
