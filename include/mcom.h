@@ -613,6 +613,13 @@ int mcom_dump_pairing_at(mcom_ctx *ctx, const uint32_t *d_lists, uint64_t n_list
                          uint32_t *d_ids_sp, uint8_t *d_file_sp, uint32_t *d_ids_0, uint8_t *d_file_0, uint64_t *h_counts,
                          const uint64_t *h_at_members, int n_at, uint64_t *h_second_at);
 int mcom_dump_member_bits(mcom_ctx *ctx, const uint64_t *d_mem, uint64_t n_members, int which, uint32_t half, uint8_t *d_out);
+/* The read order of an archive: d_lists and d_mem as for mcom_dump_pairing -- the ids of the eight lists in the
+ * decoder's order (allA, allT, allN, AA, TT, NN, single_N, single), then the members of all sets in dump order.  half == 0: d_order[j] =
+ * the read id of the j-th entry of that sequence, *h_rows = n_list + n_members.  half > 0 (paired end): d_order[j] = the id of the j-th
+ * entry that is a read of the first file (id < half); d_order holds `half` entries and *h_rows = the first-file reads found -- `half`
+ * unless the input names a read twice or not at all.  Whether d_order is a permutation is what mcom_qual_gather_rows decides.  Synchronous. */
+int mcom_dump_read_order(mcom_ctx *ctx, const uint32_t *d_lists, uint64_t n_list, const uint64_t *d_mem, uint64_t n_members, uint32_t half,
+                         uint32_t *d_order, uint64_t *h_rows);
 /* d_flag[i] = 1 when read d_rids[i] holds an N (such unclustered reads go to single_N.seq as text, kthread_dump.c:400-407)       */
 int mcom_rows_have_n(mcom_ctx *ctx, const uint64_t *d_nmask, const uint32_t *d_rids, size_t n, int L, uint8_t *d_flag);
 
@@ -720,6 +727,12 @@ typedef struct {
 uint64_t mcom_verify_room(uint64_t n_a, uint64_t n_b);
 int mcom_verify_ordered(mcom_ctx *ctx, const mcom_verify_table *a, const mcom_verify_table *b, int L, mcom_verify_report *rep);
 int mcom_verify_multiset(mcom_ctx *ctx, const mcom_verify_table *a, const mcom_verify_table *b, int L, mcom_verify_report *rep);
+/* Records of up to four parts: record i is row i of d_part[0], then row i of d_part[1], ... (each L bytes; all parts of a side `pitch`
+ * apart, at any address) -- a read and its quality line (2 parts), a pair of reads and their two quality lines (4).  The hash is taken
+ * over all parts and partners are compared byte for byte over all parts; the report and the exact_runs rule are mcom_verify_multiset's,
+ * which is this call with one part (two in its paired form).  Both sides must have the same number of parts.                        */
+typedef struct { const uint8_t *d_part[4]; int n_parts; uint64_t pitch; uint64_t n; } mcom_verify_parts;
+int mcom_verify_multiset_parts(mcom_ctx *ctx, const mcom_verify_parts *a, const mcom_verify_parts *b, int L, mcom_verify_report *rep);
 
 /* ---- the built-in entropy stage: `.rans` members (csrc/entropy.hip; format and host twin: DESIGN.md section 3.6, include/mcom_host.h) ----
  * A static rANS coder, 12-bit frequencies, one model per member: stored, order-0 or order-1 (context = the previous byte of the same
@@ -795,6 +808,19 @@ int mcom_fastq_quality_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_byt
                             uint64_t n_records, uint32_t L, uint8_t *d_rows, uint64_t pitch, uint32_t *d_flag);
 int mcom_fastq_emit(mcom_ctx *ctx, const uint8_t *d_reads, uint64_t read_pitch, const uint8_t *d_quals, uint64_t qual_pitch, uint64_t first,
                     uint64_t count, uint32_t L, uint8_t *d_out, uint64_t *bytes);
+
+/* ---- quality rows through an order (csrc/qual.hip) ----
+ * mcom_qual_gather_rows: row j of d_out (n_rows rows, `pitch_out` apart) = row d_order[j] of d_rows (n_src rows, `pitch_in` apart), L
+ * bytes each; any address, any pitch >= L, 1 <= L <= 256, both counts below 2^32; the two tables must not overlap.  The call is the
+ * order's validity check as well: d_flag points at ONE word that the caller clears and the kernel ORs the bits below into.  An index
+ * outside the table is not followed (its output row keeps what it held); a row named twice is copied both times.  With n_rows == n_src a
+ * clear word proves that d_order is a permutation.  Synchronous.                                                                      */
+enum mcom_gather_flag {
+	MCOM_GATHER_F_BOUNDS = 1,   /* an entry of d_order is >= n_src                                                      */
+	MCOM_GATHER_F_DUP = 2       /* two entries of d_order name the same source row                                     */
+};
+int mcom_qual_gather_rows(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_src, uint32_t L, uint64_t pitch_in, const uint32_t *d_order,
+                          uint64_t n_rows, uint8_t *d_out, uint64_t pitch_out, uint32_t *d_flag);
 
 /* ---- read names and '+' lines: `.mcn` members (csrc/names.hip; format and host twin: DESIGN.md section 3.10, include/mcom_host.h) ----
  * The name text of n records is 2 n lines: line 1 of a record without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at

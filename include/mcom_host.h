@@ -316,6 +316,40 @@ int mcomh_decompress_fastq(const char *folder, const char *out_path, uint64_t *n
 int mcomh_decompress_fastq_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device);
 int mcomh_verify_quality_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep);
 
+/* ---- `minicom -q`: a default or paired-end archive that also carries the quality values, in the archive's own order ----
+ * The default and the paired-end decoder return the reads in an order of their own.  The dump knows it: with mcomh_keep_read_order it also
+ * writes FOLDER/read_order.bin -- `rows` little-endian u32, the input read of the decoder's row j (paired end: of its pair j, a read of the
+ * first file; the mate is read half + order[j]).  The quality rows are put into that order before they are coded, so the member needs no
+ * ids beside it.  Names are not kept (the name coder codes a name against the one before it): record j is named `@<j+1>`.
+ *   mcomh_keep_read_order               on != 0: from now on mcomh_cluster_dump / mcomh_cluster_dump_pe of this pipeline also write read_order.bin (by
+ *                                       mcom_dump_read_order; the host_dump route writes the same bytes).  mcomh_cluster_dump_order then
+ *                                       fails, and so does this call on a pipeline with a communicator.
+ *   mcomh_qual_gather_rows              the host twin of mcom_qual_gather_rows (include/mcom.h): out row j = source row order[j]; *flag (cleared
+ *                                       by the caller) collects MCOMH_GATHER_F_*; -1 for the arguments the device call refuses.
+ *   mcomh_fastq_quality_member_ordered  mcomh_fastq_quality_member with the rows gathered through the order file first (bin/mcomz e --fastq-qual
+ *                                       L --order FILE): fails with a message, and writes no member, when the file's size is no multiple of 4,
+ *                                       its entry count is not the record count, or the gather raises a flag; device >= 0: also when the card
+ *                                       has no room to hold the rows twice.
+ *   mcomh_decompress_fastq_reordered    FOLDER with rqual.mcq -> records `@<j+1>`, read, `+`, qualities, row j the default decoder's j-th read
+ *   mcomh_decompress_fastq_pe           FOLDER with rqual_1.mcq and rqual_2.mcq -> two such files, record j of one the mate of record j of the other
+ *   ..._gpu                             the same bytes with reads and qualities rebuilt and the records laid out on GPU `device`
+ *   mcomh_verify_records_gpu            mode 0 / 2 as mcomh_verify_gpu: the archive's (read, quality) records -- paired end: (read 1, read 2,
+ *                                       quality 1, quality 2) -- against those of the FASTQ file(s) as multisets (mcom_verify_multiset_parts)
+ * The decoders and the verifier refuse a -p archive, an archive of the other kind, a missing member (paired end: either one), a member of
+ * another n or L than the reads and a refused member; a refused archive leaves no output file (of two, neither).                         */
+#define MCOMH_GATHER_F_BOUNDS 1
+#define MCOMH_GATHER_F_DUP 2
+int mcomh_keep_read_order(mcomh_pipeline *p, int on);
+int mcomh_qual_gather_rows(const uint8_t *rows, uint64_t n_src, uint32_t L, uint64_t pitch_in, const uint32_t *order, uint64_t n_rows, uint8_t *out,
+                           uint64_t pitch_out, uint32_t *flag);
+int mcomh_fastq_quality_member_ordered(const char *fastq, int L, int device, const char *order_path, const char *out_path, uint64_t *n, char *err,
+                                       size_t err_cap);
+int mcomh_decompress_fastq_reordered(const char *folder, const char *out_path, uint64_t *n_reads);
+int mcomh_decompress_fastq_reordered_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device);
+int mcomh_decompress_fastq_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs);
+int mcomh_decompress_fastq_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device);
+int mcomh_verify_records_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep);
+
 /* ---- read names and '+' lines: `.mcn` members (host/mcom_names.cpp) ----
  * The host twin of mcom_name_encode / mcom_name_decode (include/mcom.h).  The name text of n records is 2 n lines: line 1 of a record
  * without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at most 255 bytes a line.  Names are cut into tokens and coded

@@ -41,6 +41,8 @@ GROUPS = (
 )
 SINGLES = ("single_N.seq", "single.seq", "AA.txt", "TT.txt", "NN.txt")      # :136-137, :144-146
 NAME_MEMBER = "name.mcn"          # read names and '+' texts of a -p -Q archive: stored as it is
+REORDERED_MEMBERS = ("rqual.mcq", "rqual_1.mcq", "rqual_2.mcq")     # quality values in the archive's own order
+READ_ORDER = "read_order.bin"     # temporary of compress_fastq(quality_reordered=True): never a member
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -153,6 +155,10 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
     if os.path.isfile(os.path.join(folder, NAME_MEMBER)):        # likewise (section 3.10)
         with open(os.path.join(folder, NAME_MEMBER), "rb") as f:
             packed.append((NAME_MEMBER, f.read()))
+    for m in REORDERED_MEMBERS:                                  # likewise (section 3.11)
+        if os.path.isfile(os.path.join(folder, m)):
+            with open(os.path.join(folder, m), "rb") as f:
+                packed.append((m, f.read()))
     sizes = {}
     with tarfile.open(out_path, mode="w", format=tarfile.GNU_FORMAT) as t:
         with open(os.path.join(folder, "info.txt"), "rb") as f:
@@ -169,7 +175,8 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
 def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) -> dict:
     """`.minicom` file -> the stream files in `folder` (created if absent).  Returns what the archive says about itself:
     {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334), and "quality": True for an archive
-    that carries quality values (the member qual.mcq, left in the folder as it is).
+    that carries quality values (the member qual.mcq, left in the folder as it is), "quality_reordered": True for one that carries them
+    in its own order (rqual.mcq, or rqual_1.mcq and rqual_2.mcq).
     device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
@@ -178,7 +185,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER:
+        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -198,6 +205,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             kinds["quality"] = True
         if name == NAME_MEMBER:
             kinds["names"] = True
+        if name in REORDERED_MEMBERS:
+            kinds["quality_reordered"] = True
         if name.startswith("idsbin.tar"):
             kinds["order"] = True
         if name.startswith("filebin.tar"):
@@ -217,13 +226,17 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
-                   device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, **params) -> dict:
+                   device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, quality_reordered: bool = False,
+                   **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
     belongs to which read): the quality lines are gathered and coded on `device` and travel as the member qual.mcq.  Read names and the
     text of the `+` line are not kept, unless names=True (`minicom -N`; needs order=True and quality=True): they travel as the member
-    name.mcn, coded on `device`, and decompress_file then gives the input file back byte for byte.  Returns pack()'s member sizes plus the read count."""
+    name.mcn, coded on `device`, and decompress_file then gives the input file back byte for byte.
+    quality_reordered=True (`minicom -q`; not with order, quality or names; allowed with path2): the quality rows are put into the archive's
+    own order on `device` and travel as rqual.mcq (rqual_1.mcq and rqual_2.mcq for a pair); decompress_file gives four-line records in that
+    order, named by their row.  Returns pack()'s member sizes plus the read count."""
     import tempfile
     from .pipeline import Pipeline
     if order and path2 is not None:
@@ -232,11 +245,21 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         raise ValueError("quality values are kept by the order-preserving single-end mode only (order=True, no path2)")
     if names and not (order and quality):
         raise ValueError("names are kept beside the quality values of an order-preserving archive only (order=True, quality=True)")
+    if quality_reordered and (order or quality or names):
+        raise ValueError("quality_reordered keeps the quality values in the archive's own order: not with order, quality or names")
     p = Pipeline.from_fastq(path, device=device, path2=path2, host_threads=threads, **params)
     try:
         p.pre_process()
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
+            if quality_reordered:
+                p.keep_read_order(True)
             p.cluster_dump(td, order=order, paired=path2 is not None)
+            if quality_reordered:
+                from .pipeline import fastq_quality_member
+                order_path = os.path.join(td, READ_ORDER)
+                for fq, member in ((path, "rqual.mcq"),) if path2 is None else ((path, "rqual_1.mcq"), (path2, "rqual_2.mcq")):
+                    fastq_quality_member(fq, p.L, os.path.join(td, member), device=device, order_path=order_path)
+                os.remove(order_path)
             if quality:
                 _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER))
             if names:
@@ -274,6 +297,13 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
     from .pipeline import decompress, decompress_fastq, decompress_pe
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        if kinds.get("quality_reordered"):
+            from .pipeline import decompress_fastq_reordered, decompress_fastq_pe
+            if kinds["paired"]:
+                if out_path2 is None:
+                    raise ValueError("a paired-end archive decodes into two files")
+                return decompress_fastq_pe(td, out_path, out_path2, device=device)
+            return decompress_fastq_reordered(td, out_path, device=device)
         if kinds.get("quality"):
             return decompress_fastq(td, out_path, device=device)
         if kinds["paired"]:
@@ -298,6 +328,9 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
         kinds = unpack(path, td, threads=threads, device=device)
         if kinds["paired"] != (fastq2 is not None):
             raise McomError("a paired-end archive is verified against two FASTQ files, any other against one")
+        if kinds.get("quality_reordered"):
+            from .pipeline import verify_records
+            return verify_records(td, fastq, fastq2, device=device)
         rep = verify(td, fastq, fastq2, order=kinds["order"], device=device)
         if kinds.get("quality"):
             rep["quality"] = verify_quality(td, fastq, device=device)

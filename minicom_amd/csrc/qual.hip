@@ -16,6 +16,10 @@
 //                   context's row is bisected in global memory; either way the bisection takes at most 8 steps over the A + 1 entries
 //                   of a row.  64 decoded bytes per lane are staged in LDS, then every group of four lanes stores one segment's 64 bytes
 //                   as 16-byte pieces (vector stores where the address is aligned and the piece lies inside the segment).
+//   k_qual_gather   rows through an order: sixteen lanes per OUTPUT row j copy source row order[j], as the aligned 16-byte pieces of the
+//                   output they cover (vector stores; ragged byte pieces at both ends; the source is read unaligned).  The kernel is the
+//                   order's validity check as well: an index >= n_src raises a flag and is skipped, a source row named twice raises
+//                   another (one bit per source row, atomicOr).  DESIGN.md section 3.11.
 // The decoder always writes a flat image (row after row); rows that are `pitch` != L apart are spread by a 2-D copy afterwards.
 // The CRC-32 goes through the `.rans` coder's path (mcom_device_crc32).
 // Untrusted input (the rule of section 3.5): sizes, tables and run lengths are judged on the host before a kernel runs; every loop of
@@ -601,6 +605,58 @@ extern "C" int mcom_fastq_emit(mcom_ctx *ctx, const uint8_t *d_reads, uint64_t r
 	if (!d_out || !count) return MCOM_OK;
 	if (!d_reads || !d_quals) { *bytes = 0; return mcom_fail(ctx, MCOM_E_ARG, "fastq_emit: null pointer"); }
 	MCOM_LAUNCH(k_fastq_emit, dim3(blocks_for(count * 16)), dim3(QV_THREADS), 0, ctx->stream, d_reads, read_pitch, d_quals, qual_pitch, first, count, L, before, d_out);
+	MCOM_LAUNCH_CHECK(ctx);
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	return MCOM_OK;
+}
+
+// ---- rows through an order ------------------------------------------------------------------------------------
+// seen: one bit per source row, cleared by the caller.  A row named twice is still copied (it lies inside the table); an index outside
+// the table is not followed.
+__global__ __launch_bounds__(QV_THREADS) void k_qual_gather(const uint8_t *__restrict__ rows, uint64_t n_src, uint32_t L, uint64_t pitch_in, const uint32_t *__restrict__ order,
+                                                            uint64_t n_rows, uint8_t *__restrict__ out, uint64_t pitch_out, uint32_t *__restrict__ seen, uint32_t *__restrict__ flag)
+{
+	const uint64_t j = ((uint64_t)blockIdx.x * QV_THREADS + threadIdx.x) >> 4;
+	const int lane = threadIdx.x & 15;
+	if (j >= n_rows) return;                                                // (all sixteen lanes of a row together)
+	const uint64_t s = order[j];
+	if (s >= n_src) { if (lane == 0) atomicOr(flag, (uint32_t)MCOM_GATHER_F_BOUNDS); return; }
+	if (lane == 0) {
+		const uint32_t bit = 1u << (s & 31);
+		if (atomicOr(seen + (s >> 5), bit) & bit) atomicOr(flag, (uint32_t)MCOM_GATHER_F_DUP);
+	}
+	const uint8_t *src = rows + s * pitch_in;
+	uint8_t *dst = out + j * pitch_out;
+	const int lead = (int)(((uintptr_t)dst) & 15), iL = (int)L;
+	const int n_pieces = (lead + iL + 15) >> 4;                             // at most 17: L <= 256
+	for (int k = lane; k < n_pieces; k += 16) {
+		const int at = k * 16 - lead;
+		if (at >= 0 && at + 16 <= iL) {
+			uint4 v;
+			__builtin_memcpy(&v, src + at, 16);                             // (any address: the bytes [at, at + 16) of the source row, nothing else)
+			*(uint4*)(dst + at) = v;
+		} else {
+			const int b = at < 0 ? 0 : at, e = at + 16 < iL ? at + 16 : iL;
+			for (int i = b; i < e; ++i) dst[i] = src[i];
+		}
+	}
+}
+
+extern "C" int mcom_qual_gather_rows(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_src, uint32_t L, uint64_t pitch_in, const uint32_t *d_order, uint64_t n_rows,
+                                     uint8_t *d_out, uint64_t pitch_out, uint32_t *d_flag)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (!d_flag || (n_rows && (!d_order || !d_out)) || (n_src && !d_rows)) return mcom_fail(ctx, MCOM_E_ARG, "qual_gather_rows: null pointer");
+	if (L < 1 || L > L_MAX || pitch_in < L || pitch_out < L || n_src >= ((uint64_t)1 << 32) || n_rows >= ((uint64_t)1 << 32))
+		return mcom_fail(ctx, MCOM_E_ARG, "qual_gather_rows: L %u, pitches %llu and %llu, %llu rows out of %llu (L 1 .. 256, pitches >= L, below 2^32 rows)", L,
+		                 (unsigned long long)pitch_in, (unsigned long long)pitch_out, (unsigned long long)n_rows, (unsigned long long)n_src);
+	if (!n_rows) return MCOM_OK;
+	Blocks B(ctx);
+	uint32_t *d_seen = nullptr;
+	const size_t seen_bytes = (size_t)((n_src + 31) / 32) * 4;
+	MCOM_HIP(ctx, B.get(&d_seen, seen_bytes));
+	if (seen_bytes) MCOM_HIP(ctx, hipMemsetAsync(d_seen, 0, seen_bytes, ctx->stream));
+	MCOM_LAUNCH(k_qual_gather, dim3(blocks_for(n_rows * 16)), dim3(QV_THREADS), 0, ctx->stream, d_rows, n_src, L, pitch_in, d_order, n_rows, d_out, pitch_out, d_seen, d_flag);
 	MCOM_LAUNCH_CHECK(ctx);
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
 	return MCOM_OK;

@@ -527,6 +527,59 @@ extern "C" int mcom_dump_pairing_at(mcom_ctx *ctx, const uint32_t *d_lists, uint
 	return MCOM_OK;
 }
 
+// ---- the read order of an archive ----
+// seq = the reads in the order the decoder writes them: the eight lists, then the members of all sets in dump order (as for the pairing
+// streams above).  half == 0: order[i] = the read id of entry i.  half > 0 (paired end): order[j] = the id of the j-th entry that is a
+// read of the first file -- k_pe_rid's flag, one scan, and this scatter; an entry beyond `half` first-file reads (an input that names
+// a read twice) is not written.
+namespace {
+__global__ void k_ro_order(const uint32_t *__restrict__ lists, size_t n_list, const uint64_t *__restrict__ mem, size_t n_members, uint32_t half, const uint32_t *__restrict__ pre,
+                           uint32_t *__restrict__ order)
+{
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_list + n_members) return;
+	const uint32_t rid = i < n_list ? lists[i] : (uint32_t)(mem[i - n_list] >> 32);
+	if (!half) order[i] = rid;
+	else if (rid < half && pre[i] < half) order[pre[i]] = rid;
+}
+}
+extern "C" int mcom_dump_read_order(mcom_ctx *ctx, const uint32_t *d_lists, uint64_t n_list, const uint64_t *d_mem, uint64_t n_members, uint32_t half, uint32_t *d_order,
+                                    uint64_t *h_rows)
+{
+	if (!ctx || !h_rows) return MCOM_E_ARG;
+	*h_rows = 0;
+	const uint64_t N = n_list + n_members;
+	if (N == 0) return MCOM_OK;
+	if (N >= (1ull << 32) - 1) return mcom_fail(ctx, MCOM_E_ARG, "more than 2^32-2 reads");
+	if ((n_list && !d_lists) || (n_members && !d_mem) || !d_order) return mcom_fail(ctx, MCOM_E_ARG, "null device pointer");
+	const unsigned blocks = (unsigned)((N + 1 + 255) / 256);
+	if (!half) {
+		MCOM_LAUNCH(k_ro_order, dim3(blocks), dim3(256), 0, ctx->stream, d_lists, (size_t)n_list, d_mem, (size_t)n_members, 0u, (const uint32_t*)nullptr, d_order);
+		MCOM_LAUNCH_CHECK(ctx);
+		MCOM_HIP(ctx, mcom_stream_sync(ctx));
+		*h_rows = N;
+		return MCOM_OK;
+	}
+	uint32_t *first = nullptr, *pre = nullptr;
+	auto drop = [&]() { if (first) mcom_dfree(first); if (pre) mcom_dfree(pre); };
+	if (mcom_dmalloc(&first, (N + 1) * 4) != hipSuccess || mcom_dmalloc(&pre, (N + 1) * 4) != hipSuccess) { drop(); return mcom_fail(ctx, MCOM_E_NOMEM, "read order scratch"); }
+	MCOM_LAUNCH(k_pe_rid, dim3(blocks), dim3(256), 0, ctx->stream, d_lists, (size_t)n_list, d_mem, (size_t)n_members, half, first);
+	int rc = mcom_scan_u32(ctx, first, pre, N + 1, nullptr);
+	uint32_t cnt = 0;
+	hipError_t e = hipSuccess;
+	if (!rc) {
+		MCOM_LAUNCH(k_ro_order, dim3(blocks), dim3(256), 0, ctx->stream, d_lists, (size_t)n_list, d_mem, (size_t)n_members, half, (const uint32_t*)pre, d_order);
+		e = hipGetLastError();
+		if (e == hipSuccess) e = hipMemcpyAsync(&cnt, pre + N, 4, hipMemcpyDeviceToHost, ctx->stream);
+	}
+	if (e == hipSuccess) e = mcom_stream_sync(ctx);
+	drop();
+	if (rc) return rc;
+	if (e != hipSuccess) return mcom_fail(ctx, MCOM_E_HIP, "%s", hipGetErrorString(e));
+	*h_rows = cnt;
+	return MCOM_OK;
+}
+
 // dir.bin / file.bin of ONE stream set: the bits of members [0, n) of d_mem packed from bit 0 (the reference starts a fresh bit writer per
 // thread, kthread_dump.c:370-379; breads.h:241-248).  which = 0: the direction bit; 1: the file bit of the paired-end mode (read id >= half)
 namespace {

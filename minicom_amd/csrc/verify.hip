@@ -1,7 +1,8 @@
 // minicom_amd/csrc/verify.hip -- are two tables of reads in HBM the same reads?  
 //
 // A table is n rows of L characters, `pitch` bytes apart, at any address (the ingested reads: pitch L; the decoder's file image: pitch
-// L + 1, rows aligned to nothing).  A record is a row, or -- paired form -- a row and the row of the same number of a second table.
+// L + 1, rows aligned to nothing).  A record is a row, or -- paired form -- a row and the row of the same number of a second table, or
+// in general the rows of the same number of up to four parts (mcom_verify_multiset_parts: a read with its quality line, a pair with both).
 //   ordered    record i against record i: how many differ below min(n_a, n_b), and the first one                      (k_vf_ordered)
 //   multiset   a 64-bit hash per record (k_vf_hash), {hash, record} sorted by hash on both sides (mcom_radix_sort_128x: stable, so the
 //              records of a run of equal hashes stay in index order), then every sorted position finds its run on the other side by
@@ -22,7 +23,7 @@
 #define VF_RPB (VF_THREADS / VF_G)
 #define VF_GOLD 0x9E3779B97F4A7C15ull
 
-struct VfTable { const uint8_t *rows, *mates; uint64_t pitch, n; };
+struct VfTable { const uint8_t *part[4]; int np; uint64_t pitch, n; };      // a record: row i of part[0 .. np)
 
 // ---- sixteen bytes of a row -------------------------------------------------------------------------------------------------
 // w = bytes [p, p + nb) (nb <= 16; the rest zero) as four little-endian words.  [tb, te) is the table: an aligned word that lies inside
@@ -88,8 +89,8 @@ __global__ __launch_bounds__(VF_THREADS) void k_vf_hash(const VfTable t, int L, 
 	const int g = threadIdx.x / VF_G, lane = threadIdx.x % VF_G;
 	const uint64_t i = (uint64_t)blockIdx.x * VF_RPB + g;
 	const bool live = i < t.n;
-	uint64_t h = vf_row_hash(t.rows, t.pitch, t.n, i, L, lane, live);
-	if (t.mates) h = vf_mix(h + VF_GOLD * vf_row_hash(t.mates, t.pitch, t.n, i, L, lane, live));
+	uint64_t h = vf_row_hash(t.part[0], t.pitch, t.n, i, L, lane, live);
+	for (int q = 1; q < t.np; ++q) h = vf_mix(h + VF_GOLD * vf_row_hash(t.part[q], t.pitch, t.n, i, L, lane, live));
 	if (live && lane == 0) { mcom_mm128 r; r.x = h & mask; r.y = i; rec[i] = r; }
 }
 
@@ -106,8 +107,8 @@ __device__ __forceinline__ bool vf_rows_differ(const uint8_t *ra, uint64_t pa, u
 }
 __device__ __forceinline__ bool vf_records_differ(const VfTable &a, uint64_t ia, const VfTable &b, uint64_t ib, int L, int lane)
 {
-	bool d = vf_rows_differ(a.rows, a.pitch, a.n, ia, b.rows, b.pitch, b.n, ib, L, lane);
-	if (a.mates) d = d || vf_rows_differ(a.mates, a.pitch, a.n, ia, b.mates, b.pitch, b.n, ib, L, lane);
+	bool d = false;
+	for (int q = 0; q < a.np; ++q) d = d || vf_rows_differ(a.part[q], a.pitch, a.n, ia, b.part[q], b.pitch, b.n, ib, L, lane);
 	return d;
 }
 // the four groups of a wave: bit q = some lane of group q says yes
@@ -216,15 +217,15 @@ __global__ __launch_bounds__(VF_THREADS) void k_vf_dirty_runs(const mcom_mm128 *
 	list[4 * slot + 2] = sb; list[4 * slot + 3] = vf_upper(rb, n_b, x) - sb;
 }
 
-// the records at sorted positions [first, first + len) back to back (a record: L bytes, paired form 2 L), for the host
+// the records at sorted positions [first, first + len) back to back (a record: L bytes per part), for the host
 __global__ __launch_bounds__(VF_THREADS) void k_vf_gather(const VfTable t, int L, const mcom_mm128 *__restrict__ rec, uint64_t first, uint64_t len, uint8_t *__restrict__ out)
 {
-	const uint64_t rl = t.mates ? 2 * (uint64_t)L : (uint64_t)L;
+	const uint64_t rl = (uint64_t)t.np * (uint64_t)L;
 	const uint64_t at = (uint64_t)blockIdx.x * VF_THREADS + threadIdx.x;
 	if (at >= len * rl) return;
 	const uint64_t r = at / rl, c = at % rl, y = rec[first + r].y;
 	if (y >= t.n) { out[at] = 0; return; }
-	out[at] = c < (uint64_t)L ? t.rows[y * t.pitch + c] : t.mates[y * t.pitch + (c - (uint64_t)L)];
+	out[at] = t.part[c / (uint64_t)L][y * t.pitch + c % (uint64_t)L];
 }
 
 // *out = min(*out, the smallest cand[i] that is not ~0 and, with has_prev, above prev): one atomic per wave that holds one
@@ -270,14 +271,15 @@ void vf_report_clear(mcom_verify_report *rep, uint64_t n_a, uint64_t n_b)
 	for (int q = 0; q < 8; ++q) rep->missing_ex[q] = rep->extra_ex[q] = ~0ull;
 }
 
-VfTable vf_table(const mcom_verify_table *t, bool paired) { VfTable v; v.rows = t->d_rows; v.mates = paired ? t->d_mates : nullptr; v.pitch = t->pitch; v.n = t->n; return v; }
+VfTable vf_table(const mcom_verify_table *t, bool paired) { VfTable v = {}; v.part[0] = t->d_rows; v.part[1] = paired ? t->d_mates : nullptr; v.np = paired ? 2 : 1; v.pitch = t->pitch; v.n = t->n; return v; }
+VfTable vf_table(const mcom_verify_parts *t, int np) { VfTable v = {}; for (int q = 0; q < np; ++q) v.part[q] = t->d_part[q]; v.np = np; v.pitch = t->pitch; v.n = t->n; return v; }
 
 // One marked run as a multiset of full records: the records of A that B does not give back and the converse, with multiplicity; within
 // equal records the first ones (by record index) are the matched ones.
 int vf_settle(mcom_ctx *ctx, const VfTable &A, const VfTable &B, int L, const mcom_mm128 *ra, const mcom_mm128 *rb, const uint64_t run[4],
               std::vector<uint64_t> &miss, std::vector<uint64_t> &extra)
 {
-	const uint64_t rl = A.mates ? 2 * (uint64_t)L : (uint64_t)L, la = run[1], lb = run[3], tot = la + lb;
+	const uint64_t rl = (uint64_t)A.np * (uint64_t)L, la = run[1], lb = run[3], tot = la + lb;
 	VfBlocks blk;
 	uint8_t *d_rows = nullptr;
 	MCOM_HIP(ctx, blk.get(&d_rows, tot * rl));
@@ -367,16 +369,12 @@ extern "C" int mcom_verify_ordered(mcom_ctx *ctx, const mcom_verify_table *a, co
 	return MCOM_OK;
 }
 
-extern "C" int mcom_verify_multiset(mcom_ctx *ctx, const mcom_verify_table *a, const mcom_verify_table *b, int L, mcom_verify_report *rep)
+// the multiset comparison over two checked sides of the same number of parts; rep is cleared
+static int vf_multiset(mcom_ctx *ctx, const VfTable &A, const VfTable &B, int L, mcom_verify_report *rep)
 {
-	if (!ctx) return MCOM_E_ARG;
-	int rc = vf_check(ctx, a, b, L, rep, "verify_multiset");
-	if (rc) return rc;
-	vf_report_clear(rep, a->n, b->n);
-	const uint64_t na = a->n, nb = b->n;
+	int rc;
+	const uint64_t na = A.n, nb = B.n;
 	if (na == 0 && nb == 0) { rep->identical = 1; return MCOM_OK; }
-	const bool paired = (na ? a->d_mates : b->d_mates) != nullptr;
-	const VfTable A = vf_table(a, paired), B = vf_table(b, paired);
 	const uint64_t mask = vf_mask(ctx->verify_hash_bits);
 	VfBlocks blk;
 	mcom_mm128 *ra = nullptr, *rb = nullptr;
@@ -452,4 +450,31 @@ extern "C" int mcom_verify_multiset(mcom_ctx *ctx, const mcom_verify_table *a, c
 	if (rep->extra && (rc = vf_examples(ctx, pb, nb, dev_extra, extra, cnt + 4, rep->extra_ex, &rep->n_extra_ex))) return rc;
 	rep->identical = rep->missing == 0 && rep->extra == 0;
 	return MCOM_OK;
+}
+
+extern "C" int mcom_verify_multiset(mcom_ctx *ctx, const mcom_verify_table *a, const mcom_verify_table *b, int L, mcom_verify_report *rep)
+{
+	if (!ctx) return MCOM_E_ARG;
+	int rc = vf_check(ctx, a, b, L, rep, "verify_multiset");
+	if (rc) return rc;
+	vf_report_clear(rep, a->n, b->n);
+	const bool paired = (a->n ? a->d_mates : b->d_mates) != nullptr;
+	return vf_multiset(ctx, vf_table(a, paired), vf_table(b, paired), L, rep);
+}
+
+extern "C" int mcom_verify_multiset_parts(mcom_ctx *ctx, const mcom_verify_parts *a, const mcom_verify_parts *b, int L, mcom_verify_report *rep)
+{
+	if (!ctx) return MCOM_E_ARG;
+	const char *who = "verify_multiset_parts";
+	if (!a || !b || !rep) return mcom_fail(ctx, MCOM_E_ARG, "%s: null pointer", who);
+	if (L < 1 || L > 256) return mcom_fail(ctx, MCOM_E_ARG, "%s: L = %d not in 1..256", who, L);
+	if (a->n_parts < 1 || a->n_parts > 4 || b->n_parts != a->n_parts) return mcom_fail(ctx, MCOM_E_ARG, "%s: %d and %d parts (1 .. 4, the same on both sides)", who, a->n_parts, b->n_parts);
+	const mcom_verify_parts *t[2] = {a, b};
+	for (int s = 0; s < 2; ++s) {
+		if (t[s]->n >= (1ull << 32)) return mcom_fail(ctx, MCOM_E_ARG, "%s: more than 2^32-1 records", who);
+		if (t[s]->n && t[s]->pitch < (uint64_t)L) return mcom_fail(ctx, MCOM_E_ARG, "%s: a pitch below L", who);
+		for (int q = 0; q < t[s]->n_parts; ++q) if (t[s]->n && !t[s]->d_part[q]) return mcom_fail(ctx, MCOM_E_ARG, "%s: part %d without rows", who, q);
+	}
+	vf_report_clear(rep, a->n, b->n);
+	return vf_multiset(ctx, vf_table(a, a->n_parts), vf_table(b, a->n_parts), L, rep);
 }

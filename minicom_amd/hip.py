@@ -31,6 +31,11 @@ class VerifyTable(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("d_mates", C.c_void_p), ("pitch", C.c_uint64), ("n", C.c_uint64)]
 
 
+class VerifyParts(C.Structure):
+    """mcom_verify_parts of include/mcom.h"""
+    _fields_ = [("d_part", C.c_void_p * 4), ("n_parts", C.c_int), ("pitch", C.c_uint64), ("n", C.c_uint64)]
+
+
 class VerifyReport(C.Structure):
     """mcom_verify_report of include/mcom.h"""
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("missing", C.c_uint64), ("extra", C.c_uint64), ("differing", C.c_uint64),
@@ -174,6 +179,9 @@ def load_library():
     L.mcom_fastq_emit.restype = i32; L.mcom_fastq_emit.argtypes = [vp, vp, u64, vp, u64, u64, u64, C.c_uint32, vp, C.POINTER(u64)]
     L.mcom_qual_bound.restype = u64; L.mcom_qual_bound.argtypes = [u64, C.c_uint32]
     L.mcom_qual_encode.restype = i32; L.mcom_qual_encode.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcom_qual_gather_rows.restype = i32; L.mcom_qual_gather_rows.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, vp, u64, vp]
+    L.mcom_dump_read_order.restype = i32; L.mcom_dump_read_order.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
+    L.mcom_verify_multiset_parts.restype = i32; L.mcom_verify_multiset_parts.argtypes = [vp, C.POINTER(VerifyParts), C.POINTER(VerifyParts), i32, C.POINTER(VerifyReport)]
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_name_bound.restype = u64; L.mcom_name_bound.argtypes = [u64]
@@ -994,6 +1002,42 @@ class Context:
         self._check(self.lib.mcom_qual_decode(self._h, self._p(member, torch.uint8), n_in, out.data_ptr(), pitch, int(out.shape[0]), C.byref(gn), C.byref(gL)))
         return out[:n, :L]
 
+    GATHER_F_BOUNDS, GATHER_F_DUP = 1, 2
+
+    def qual_gather_rows(self, rows, order, out=None):
+        """mcom_qual_gather_rows.  rows: uint8 device matrix [n_src, L] with contiguous rows (any row stride >= L,
+        any address); order: int32 / uint32 device vector of n_rows source row numbers.  Returns (out, flags): out row j = rows[order[j]]
+        as a uint8 device matrix [n_rows, L] (out given: written into it, rows of at least L bytes), flags the OR of GATHER_F_BOUNDS (an
+        entry >= n_src: its output row is left as it was) and GATHER_F_DUP (a source row named twice).  With n_rows == n_src, flags == 0
+        proves a permutation."""
+        torch = _torch()
+        if rows.dim() != 2 or rows.dtype != torch.uint8 or (rows.shape[0] and rows.stride(1) != 1):
+            raise McomError("qual_gather_rows: a uint8 matrix with contiguous rows")
+        if order.dim() != 1 or order.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or (order.shape[0] > 1 and order.stride(0) != 1):
+            raise McomError("qual_gather_rows: the order is a contiguous vector of 32-bit row numbers")
+        n_src, L, n_rows = int(rows.shape[0]), int(rows.shape[1]), int(order.shape[0])
+        pitch_in = int(rows.stride(0)) if n_src > 1 else L
+        if out is None:
+            out = torch.empty((n_rows, L), dtype=torch.uint8, device=self.device)
+        if out.dim() != 2 or out.dtype != torch.uint8 or int(out.shape[0]) != n_rows or int(out.shape[1]) < L or (n_rows and out.stride(1) != 1):
+            raise McomError("qual_gather_rows: out must be a uint8 matrix of %d rows of at least %d contiguous bytes" % (n_rows, L))
+        pitch_out = int(out.stride(0)) if n_rows > 1 else max(L, int(out.shape[1]))
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_qual_gather_rows(self._h, rows.data_ptr() if n_src else None, n_src, L, pitch_in, order.data_ptr() if n_rows else None, n_rows,
+                                                   out.data_ptr() if n_rows else None, pitch_out, self._p(flag)))
+        return out[:, :L], int(flag.item())
+
+    def dump_read_order(self, lists, mem, half: int = 0):
+        """mcom_dump_read_order (DESIGN.md section 3.11).  lists: int32 device vector, the read ids of the eight lists in the decoder's order;
+        mem: int64 device vector, the members in dump order (read id in the upper half).  half == 0: the read id of every entry; half > 0:
+        the ids of the entries that are reads of the first file (id < half), in their order.  Returns an int32 device vector of `rows` ids."""
+        torch = _torch()
+        nl, nm = int(lists.shape[0]), int(mem.shape[0])
+        order = torch.empty(max(int(half) if half else nl + nm, 1), dtype=torch.int32, device=self.device)
+        rows = C.c_uint64()
+        self._check(self.lib.mcom_dump_read_order(self._h, self._p(lists, torch.int32) if nl else None, nl, self._p(mem, torch.int64) if nm else None, nm, int(half), self._p(order), C.byref(rows)))
+        return order[:min(int(rows.value), int(order.shape[0]))]
+
     def fastq_qualities(self, text, L: int, first_record: int = 0, out=None):
         """mcom_decode_line_index + mcom_fastq_quality_rows.  text: uint8 device tensor holding whole four-line records (every line ends
         with a newline).  Returns (rows uint8 [first_record + n_records, L], flag bits of MCOM_FASTQ_F_*, the first flagged record or
@@ -1207,6 +1251,27 @@ class Context:
         """mcom_verify_multiset: are the records of table a and table b the same multiset?  a, b: see _verify_table."""
         ta, tb, r = self._verify_table(a, L), self._verify_table(b, L), VerifyReport()
         self._check(self.lib.mcom_verify_multiset(self._h, C.byref(ta), C.byref(tb), L, C.byref(r)))
+        return self._verify_dict(r)
+
+    def verify_multiset_parts(self, a, b, L: int) -> dict:
+        """mcom_verify_multiset_parts: a, b = (parts, pitch, n) with parts a list of 1 .. 4 uint8 device tensors whose first byte is row 0 of
+        that part (rows `pitch` apart in all parts of a side); a record is row i of every part, one after the other."""
+        torch = _torch()
+
+        def side(t):
+            parts, pitch, n = list(t[0]), int(t[1]), int(t[2])
+            if not 1 <= len(parts) <= 4:
+                raise McomError("verify_multiset_parts: 1 .. 4 parts")
+            for x in parts:
+                if n and (x is None or x.dtype != torch.uint8 or x.numel() < (n - 1) * pitch + L):
+                    raise McomError("a part must be a uint8 tensor that holds (n - 1) * pitch + L bytes from row 0 on")
+            v = VerifyParts()
+            for q, x in enumerate(parts):
+                v.d_part[q] = x.data_ptr() if n else None
+            v.n_parts, v.pitch, v.n = len(parts), pitch, n
+            return v
+        ta, tb, r = side(a), side(b), VerifyReport()
+        self._check(self.lib.mcom_verify_multiset_parts(self._h, C.byref(ta), C.byref(tb), L, C.byref(r)))
         return self._verify_dict(r)
 
     def verify_ordered(self, a, b, L: int) -> dict:

@@ -9,10 +9,10 @@
 #include <cstdlib>
 #include <cstring>
 
-struct CliOptions { mcomh_params prm; bool order = false; int device = 0; };
+struct CliOptions { mcomh_params prm; bool order = false, keep_order = false; int device = 0; };
 
 // options after the positional arguments: -k -e -m -w -s -S -E (README.md:39-51), -g (merge threshold), -R (max rounds)
-// (minicom:446-447), -t (host threads), -p (order preserving), -D (GPU)
+// (minicom:446-447), -t (host threads), -p (order preserving), -D (GPU), -O (also write OUTDIR/read_order.bin: mcomh_keep_read_order)
 static inline bool cli_parse(int argc, char **argv, int first, CliOptions &o)
 {
 	memset(&o.prm, 0, sizeof o.prm);
@@ -20,6 +20,7 @@ static inline bool cli_parse(int argc, char **argv, int first, CliOptions &o)
 		const char *a = argv[i];
 		if (a[0] != '-' || !a[1] || a[2]) return false;
 		if (a[1] == 'p') { o.order = true; continue; }
+		if (a[1] == 'O') { o.keep_order = true; continue; }
 		if (i + 1 >= argc) return false;
 		const int v = atoi(argv[++i]);
 		switch (a[1]) {

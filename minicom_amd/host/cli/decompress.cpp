@@ -9,6 +9,10 @@
 // decompress --fastq [--gpu] DIR OUT.fastq: a -p -Q archive (DIR holds qual.mcq) back to four-line records `@<i+1>`, read, `+`, qualities.
 // decompress --verify-quality DIR IN.fastq: qual.mcq against the quality lines of the FASTQ on GPU 0; exit status as --verify.
 // decompress --verify-names DIR IN.fastq: name.mcn against the names and '+' texts of the FASTQ on GPU 0; exit status as --verify.
+// decompress --fastq-reordered [--gpu] DIR OUT.fastq: a `minicom -q` archive of one file (DIR holds rqual.mcq) back to four-line records, in
+// the archive's own order.  decompress --fastq-pe [--gpu] DIR OUT_1.fastq OUT_2.fastq: the paired-end one (rqual_1.mcq, rqual_2.mcq).
+// decompress --verify-records DIR IN.fastq [IN_2.fastq]: the (read, quality) records -- (read 1, read 2, quality 1, quality 2) for a pair --
+// of such an archive against those of the FASTQ file(s) as multisets on GPU 0; exit status as --verify.
 // --fastq picks DIR/name.mcn up by itself (an archive made with -N): the records then carry the names and '+' texts.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
@@ -87,8 +91,40 @@ static int fastq(int argc, char **argv)
 	return 0;
 }
 
+static int fastq_reordered(int argc, char **argv, bool pe)
+{
+	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+	if (gpu) { --argc; ++argv; }
+	if (argc < (pe ? 4 : 3)) { fprintf(stderr, pe ? "usage: decompress --fastq-pe [--gpu] DIR OUT_1.fastq OUT_2.fastq\n" : "usage: decompress --fastq-reordered [--gpu] DIR OUT.fastq\n"); return 1; }
+	uint64_t n = 0;
+	const int rc = pe ? (gpu ? mcomh_decompress_fastq_pe_gpu(argv[1], argv[2], argv[3], &n, 0) : mcomh_decompress_fastq_pe(argv[1], argv[2], argv[3], &n))
+	                  : (gpu ? mcomh_decompress_fastq_reordered_gpu(argv[1], argv[2], &n, 0) : mcomh_decompress_fastq_reordered(argv[1], argv[2], &n));
+	if (rc) { fprintf(stderr, "decompress: %s is not a complete, consistent %s archive with quality values in its own order%s\n", argv[1], pe ? "paired-end" : "default-mode", gpu ? ", or the GPU route is not available" : ""); return 1; }
+	fprintf(stdout, "%llu %s\n", (unsigned long long)n, pe ? "pairs" : "records");
+	return 0;
+}
+
+static int verify_records(int argc, char **argv)
+{
+	if (argc < 3) { fprintf(stderr, "usage: decompress --verify-records DIR IN.fastq [IN_2.fastq]\n"); return 1; }
+	const bool pe = argc > 3;
+	mcomh_verify_report r;
+	if (mcomh_verify_records_gpu(argv[1], pe ? 2 : 0, argv[2], pe ? argv[3] : nullptr, 0, &r)) { fprintf(stderr, "decompress: the records of %s could not be verified against %s\n", argv[1], argv[2]); return 1; }
+	const char *unit = pe ? "pairs with their quality lines" : "reads with their quality lines";
+	if (r.identical) { printf("verified: %llu %s identical\n", (unsigned long long)r.n_input, unit); return 0; }
+	printf("DIFFERENT: the FASTQ holds %llu %s, the archive %llu\n", (unsigned long long)r.n_input, unit, (unsigned long long)r.n_archive);
+	printf("  %llu records of the FASTQ are missing from the archive, %llu records of the archive are not in the FASTQ\n", (unsigned long long)r.missing, (unsigned long long)r.extra);
+	examples("missing (numbered from 0 in the FASTQ)", r.missing_ex, r.n_missing_ex);
+	examples("extra (numbered from 0 in the archive's output)", r.extra_ex, r.n_extra_ex);
+	if (r.exact_runs) printf("  %llu runs of equal hashes were settled record by record\n", (unsigned long long)r.exact_runs);
+	return 2;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc > 1 && !strcmp(argv[1], "--fastq-reordered")) return fastq_reordered(argc - 1, argv + 1, false);
+	if (argc > 1 && !strcmp(argv[1], "--fastq-pe")) return fastq_reordered(argc - 1, argv + 1, true);
+	if (argc > 1 && !strcmp(argv[1], "--verify-records")) return verify_records(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify")) return verify(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify-quality")) return verify_quality(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify-names")) return verify_names(argc - 1, argv + 1);

@@ -8,6 +8,9 @@
 // mcomz e --fastq-qual L [--gpu] IN.fastq OUT: the quality lines of a four-line FASTQ file (plain or .gz) of reads of L bases -> a `.mcq`
 // member; every record is checked ('@' line, '+' line, both lengths, quality bytes 33 .. 126) and the first bad one is named -- on the
 // GPU by the kernels behind mcomh_fastq_qualities_to_device, without --gpu by their host twin.  Prints the number of records.
+// mcomz e --fastq-qual L --order FILE [--gpu] IN.fastq OUT: the same with row j of the member = record order[j] of IN.fastq, FILE holding
+// one little-endian u32 per record (read_order.bin of `minicom -q`); exit status 1 and no member when FILE is
+// no permutation of the records (its size, its entry count, an entry beyond the last record, a record named twice).
 // mcomz e --names [--gpu] IN OUT: IN is a name text (per record its name and the text of its third line, a line each; DESIGN.md section
 // 3.10), OUT a `.mcn` member; a line above 255 bytes is refused and its record named.  d knows such a member by its magic.
 // mcomz e --fastq-names [--gpu] IN.fastq OUT: the names and '+' texts of a four-line FASTQ file (plain or .gz) -> a `.mcn` member; every
@@ -31,23 +34,25 @@ int main(int argc, char **argv)
 {
 	bool gpu = false, bwt = false, names = false, fastq_names = false;
 	int at = 2, qual_L = 0, fastq_L = 0;
+	const char *order_path = nullptr;
 	for (; at < argc; ++at) {
 		if (!strcmp(argv[at], "--gpu") && !gpu) gpu = true;
 		else if (!strcmp(argv[at], "--qual") && !qual_L && at + 1 < argc) { qual_L = atoi(argv[++at]); if (qual_L < 1 || qual_L > 256) { fprintf(stderr, "mcomz: --qual takes the row length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--fastq-qual") && !fastq_L && at + 1 < argc) { fastq_L = atoi(argv[++at]); if (fastq_L < 1 || fastq_L > 256) { fprintf(stderr, "mcomz: --fastq-qual takes the read length, 1 .. 256\n"); return 1; } }
+		else if (!strcmp(argv[at], "--order") && !order_path && at + 1 < argc) order_path = argv[++at];
 		else if (!strcmp(argv[at], "--bwt") && !bwt) bwt = true;
 		else if (!strcmp(argv[at], "--names") && !names) names = true;
 		else if (!strcmp(argv[at], "--fastq-names") && !fastq_names) fastq_names = true;
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names))) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names))) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;
 	if (fastq_L) {
 		char err[320] = ""; uint64_t n = 0;
-		if (mcomh_fastq_quality_member(in, fastq_L, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
+		if (order_path ? mcomh_fastq_quality_member_ordered(in, fastq_L, device, order_path, out, &n, err, sizeof err) : mcomh_fastq_quality_member(in, fastq_L, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
 		printf("%llu\n", (unsigned long long)n);
 		return 0;
 	}

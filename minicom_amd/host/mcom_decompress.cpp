@@ -67,6 +67,8 @@ size_t file_bytes(const std::string &path)
 	return n > 0 ? (size_t)n : 0;
 }
 
+void shut(FILE *f) { if (f) fclose(f); }                      // (the routes that hand their rows out open no file)
+
 void revcomp(std::string &s)
 {
 	const size_t n = s.size();
@@ -76,9 +78,10 @@ void revcomp(std::string &s)
 
 } // namespace
 
-static int decompress_impl(const char *folder, const char *out_path, uint64_t *n_reads)
+// keep: the rows (L characters each, back to back) are handed out instead of being written (mcomh_decompress_fastq_reordered)
+static int decompress_impl(const char *folder, const char *out_path, uint64_t *n_reads, std::vector<char> *keep = nullptr, int *L_out = nullptr)
 {
-	if (!folder || !out_path) return -1;
+	if (!folder || (!out_path && !keep)) return -1;
 	const std::string dir(folder);
 	FILE *fi = fopen((dir + "/info.txt").c_str(), "r");
 	if (!fi) return -1;
@@ -86,10 +89,10 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 	if (fscanf(fi, "%d %d %ld %ld %ld", &L, &nth, &na, &nt, &nn) != 5) { fclose(fi); return -1; }
 	fclose(fi);
 	if (L < 1 || L > 256 || nth < 1 || nth > 4096 || na < 0 || nt < 0 || nn < 0) return -1;
-	FILE *out = fopen(out_path, "w");
-	if (!out) return -1;
+	FILE *out = keep ? nullptr : fopen(out_path, "w");
+	if (!keep && !out) return -1;
 	uint64_t total = 0;
-	auto line = [&](const std::string &s) { fwrite(s.data(), 1, s.size(), out); fputc('\n', out); ++total; };
+	auto line = [&](const std::string &s) { if (keep) { if ((int)s.size() == L) keep->insert(keep->end(), s.begin(), s.end()); } else { fwrite(s.data(), 1, s.size(), out); fputc('\n', out); } ++total; };
 	// all-A / all-T / all-N reads are only counted (decompress.c:660-688)
 	for (long i = 0; i < na; ++i) line(std::string((size_t)L, 'A'));
 	for (long i = 0; i < nt; ++i) line(std::string((size_t)L, 'T'));
@@ -99,16 +102,16 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 	std::string seq;
 	const char bases[3] = {'A', 'T', 'N'}; const char *names[3] = {"AA.txt", "TT.txt", "NN.txt"};
 	for (int q = 0; q < 3; ++q) {
-		if (!slurp(dir + "/" + names[q], buf)) { fclose(out); return -1; }
+		if (!slurp(dir + "/" + names[q], buf)) { shut(out); return -1; }
 		const std::string cref((size_t)L, bases[q]);
 		size_t s = 0;
-		for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { if (!decode_line((const char*)buf.data() + s, i - s, cref.c_str(), L, seq)) { fclose(out); return -1; } line(seq); s = i + 1; }
+		for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { if (!decode_line((const char*)buf.data() + s, i - s, cref.c_str(), L, seq)) { shut(out); return -1; } line(seq); s = i + 1; }
 	}
 	// reads kept as text because they contain N
-	if (!slurp(dir + "/single_N.seq", buf)) { fclose(out); return -1; }
-	{ size_t s = 0; for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { if (i - s != (size_t)L) { fclose(out); return -1; } line(std::string((const char*)buf.data() + s, i - s)); s = i + 1; } }
+	if (!slurp(dir + "/single_N.seq", buf)) { shut(out); return -1; }
+	{ size_t s = 0; for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { if (i - s != (size_t)L) { shut(out); return -1; } line(std::string((const char*)buf.data() + s, i - s)); s = i + 1; } }
 	// unclustered reads, 2 bits per base (:612-644); a trailing partial byte carries no complete read
-	if (!slurp(dir + "/single.seq", buf)) { fclose(out); return -1; }
+	if (!slurp(dir + "/single.seq", buf)) { shut(out); return -1; }
 	{
 		DnaReader r(buf);
 		for (;;) {
@@ -124,7 +127,7 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 		std::vector<uint8_t> bref, bpos, bdir, bdif;
 		const std::string sfx = "." + std::to_string(th);
 		if (!slurp(dir + "/ref.bin" + sfx, bref) || !slurp(dir + "/beg_pos.bin" + sfx, bpos) || !slurp(dir + "/dir.bin" + sfx, bdir) ||
-		    !slurp(dir + "/dif_char.txt" + sfx, bdif)) { fclose(out); return -1; }
+		    !slurp(dir + "/dif_char.txt" + sfx, bdif)) { shut(out); return -1; }
 		DnaReader rr(bref); BitReader dr(bdir);
 		size_t pp = 0, dp = 0;
 		std::string ref;
@@ -133,20 +136,22 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 			ref.clear();
 			int pre = 0;
 			for (uint32_t q = 0; q < num; ++q) {
-				if (pp + 2 > bpos.size()) { fclose(out); return -1; }
+				if (pp + 2 > bpos.size()) { shut(out); return -1; }
 				uint16_t d; memcpy(&d, bpos.data() + pp, 2); pp += 2;
 				const int pos = pre + d; pre = pos;
-				while ((int)ref.size() < pos + L) { const int c = rr.next(); if (c < 0) { fclose(out); return -1; } ref.push_back("ACGT"[c]); }   // getRef (:92-100)
+				while ((int)ref.size() < pos + L) { const int c = rr.next(); if (c < 0) { shut(out); return -1; } ref.push_back("ACGT"[c]); }   // getRef (:92-100)
 				const int rev = dr.next();
 				size_t e = dp; while (e < bdif.size() && bdif[e] != '\n') ++e;
-				if (e >= bdif.size() || !decode_line((const char*)bdif.data() + dp, e - dp, ref.c_str() + pos, L, seq)) { fclose(out); return -1; }
+				if (e >= bdif.size() || !decode_line((const char*)bdif.data() + dp, e - dp, ref.c_str() + pos, L, seq)) { shut(out); return -1; }
 				dp = e + 1;
 				if (rev) revcomp(seq);
 				line(seq);
 			}
 		}
 	}
-	fclose(out);
+	shut(out);
+	if (keep && keep->size() != (size_t)total * (size_t)L) return -1;
+	if (L_out) *L_out = L;
 	if (n_reads) *n_reads = total;
 	return 0;
 }
@@ -275,9 +280,12 @@ static int decompress_order_impl(const char *folder, const char *out_path, uint6
 // Reads of the first file are written to out_path1 in stream order (the eight lists, then the contig members); a read
 // of the second file carries the line number of its mate (peids streams, one file bit per read says which kind a
 // read is) and goes to that line of out_path2: line i of the two outputs is a pair.
-static int decompress_pe_impl(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+// keep1 / keep2: the rows of the two files (L characters each) are handed out instead of being written (mcomh_decompress_fastq_pe)
+static int decompress_pe_impl(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, std::vector<char> *keep1 = nullptr, std::vector<char> *keep2 = nullptr,
+                              int *L_out = nullptr)
 {
-	if (!folder || !out_path1 || !out_path2) return -1;
+	const bool keep = keep1 && keep2;
+	if (!folder || (!keep && (!out_path1 || !out_path2))) return -1;
 	const std::string dir(folder);
 	FILE *fi = fopen((dir + "/info.txt").c_str(), "r");
 	if (!fi) return -1;
@@ -292,8 +300,8 @@ static int decompress_pe_impl(const char *folder, const char *out_path1, const c
 	}
 	std::vector<char> table((size_t)half * (size_t)L, 0);
 	std::vector<uint8_t> seen((size_t)half, 0);
-	FILE *out = fopen(out_path1, "w");
-	if (!out) return -1;
+	FILE *out = keep ? nullptr : fopen(out_path1, "w");
+	if (!keep && !out) return -1;
 	uint64_t left = 0; bool bad = false;
 	struct Pairing {                                                      // file bits + mate numbers of one stream set
 		std::vector<uint8_t> fb, ids; size_t ip = 0; size_t bpos = 0; int k = 8; unsigned cur = 0;
@@ -305,27 +313,27 @@ static int decompress_pe_impl(const char *folder, const char *out_path1, const c
 		if (pr.bit()) {                                                    // a read of the second file: to its mate's line
 			uint32_t v; if (!pr.id(v) || v >= (uint64_t)half || seen[v]) { bad = true; return; }
 			memcpy(table.data() + (size_t)v * L, s.data(), (size_t)L); seen[v] = 1;
-		} else { fwrite(s.data(), 1, s.size(), out); fputc('\n', out); ++left; }
+		} else { if (keep) keep1->insert(keep1->end(), s.begin(), s.end()); else { fwrite(s.data(), 1, s.size(), out); fputc('\n', out); } ++left; }
 	};
 	std::vector<uint8_t> buf;
 	std::string seq;
 	Pairing sp;
-	if (!slurp(dir + "/file.bin.sp", sp.fb) || !slurp(dir + "/peids.bin.sp", sp.ids)) { fclose(out); return -1; }
+	if (!slurp(dir + "/file.bin.sp", sp.fb) || !slurp(dir + "/peids.bin.sp", sp.ids)) { shut(out); return -1; }
 	for (long i = 0; i < na; ++i) place(sp, std::string((size_t)L, 'A'));
 	for (long i = 0; i < nt; ++i) place(sp, std::string((size_t)L, 'T'));
 	for (long i = 0; i < nn; ++i) place(sp, std::string((size_t)L, 'N'));
 	{
 		const char bases[3] = {'A', 'T', 'N'}; const char *names[3] = {"AA.txt", "TT.txt", "NN.txt"};
 		for (int q = 0; q < 3; ++q) {
-			if (!slurp(dir + "/" + names[q], buf)) { fclose(out); return -1; }
+			if (!slurp(dir + "/" + names[q], buf)) { shut(out); return -1; }
 			const std::string cref((size_t)L, bases[q]);
 			size_t s = 0;
-			for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { if (!decode_line((const char*)buf.data() + s, i - s, cref.c_str(), L, seq)) { fclose(out); return -1; } s = i + 1; place(sp, seq); }
+			for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { if (!decode_line((const char*)buf.data() + s, i - s, cref.c_str(), L, seq)) { shut(out); return -1; } s = i + 1; place(sp, seq); }
 		}
 	}
-	if (!slurp(dir + "/single_N.seq", buf)) { fclose(out); return -1; }
+	if (!slurp(dir + "/single_N.seq", buf)) { shut(out); return -1; }
 	{ size_t s = 0; for (size_t i = 0; i < buf.size(); ++i) if (buf[i] == '\n') { seq.assign((const char*)buf.data() + s, i - s); s = i + 1; place(sp, seq); } }
-	if (!slurp(dir + "/single.seq", buf)) { fclose(out); return -1; }
+	if (!slurp(dir + "/single.seq", buf)) { shut(out); return -1; }
 	{
 		// the last byte may be padded with up to three A: reads are taken while whole reads remain (4 bases per byte)
 		const size_t whole = buf.size() * 4 / (size_t)L;
@@ -341,7 +349,7 @@ static int decompress_pe_impl(const char *folder, const char *out_path1, const c
 		Pairing pr;
 		const std::string sfx = "." + std::to_string(th);
 		if (!slurp(dir + "/ref.bin" + sfx, bref) || !slurp(dir + "/beg_pos.bin" + sfx, bpos) || !slurp(dir + "/dir.bin" + sfx, bdir) ||
-		    !slurp(dir + "/dif_char.txt" + sfx, bdif) || !slurp(dir + "/file.bin" + sfx, pr.fb) || !slurp(dir + "/peids.bin" + sfx, pr.ids)) { fclose(out); return -1; }
+		    !slurp(dir + "/dif_char.txt" + sfx, bdif) || !slurp(dir + "/file.bin" + sfx, pr.fb) || !slurp(dir + "/peids.bin" + sfx, pr.ids)) { shut(out); return -1; }
 		DnaReader rr(bref); BitReader dr(bdir);
 		size_t pp = 0, dp = 0;
 		std::string ref;
@@ -350,22 +358,23 @@ static int decompress_pe_impl(const char *folder, const char *out_path1, const c
 			ref.clear();
 			int pre = 0;
 			for (uint32_t q = 0; q < num; ++q) {
-				if (pp + 2 > bpos.size()) { fclose(out); return -1; }
+				if (pp + 2 > bpos.size()) { shut(out); return -1; }
 				uint16_t d; memcpy(&d, bpos.data() + pp, 2); pp += 2;
 				const int pos = pre + d; pre = pos;
-				while ((int)ref.size() < pos + L) { const int c = rr.next(); if (c < 0) { fclose(out); return -1; } ref.push_back("ACGT"[c]); }
+				while ((int)ref.size() < pos + L) { const int c = rr.next(); if (c < 0) { shut(out); return -1; } ref.push_back("ACGT"[c]); }
 				const int rev = dr.next();
 				size_t e = dp; while (e < bdif.size() && bdif[e] != '\n') ++e;
-				if (e >= bdif.size() || !decode_line((const char*)bdif.data() + dp, e - dp, ref.c_str() + pos, L, seq)) { fclose(out); return -1; }
+				if (e >= bdif.size() || !decode_line((const char*)bdif.data() + dp, e - dp, ref.c_str() + pos, L, seq)) { shut(out); return -1; }
 				dp = e + 1;
 				if (rev) revcomp(seq);
 				place(pr, seq);
 			}
 		}
 	}
-	fclose(out);
+	shut(out);
 	if (bad || left != (uint64_t)half) return -1;
 	for (uint8_t s : seen) if (!s) return -1;
+	if (keep) { keep2->swap(table); if (L_out) *L_out = L; if (n_pairs) *n_pairs = (uint64_t)half; return 0; }
 	FILE *out2 = fopen(out_path2, "w");
 	if (!out2) return -1;
 	for (long i = 0; i < half; ++i) { fwrite(table.data() + (size_t)i * L, 1, (size_t)L, out2); fputc('\n', out2); }
@@ -440,4 +449,74 @@ static int decompress_fastq_impl(const char *folder, const char *out_path, uint6
 extern "C" int mcomh_decompress_fastq(const char *folder, const char *out_path, uint64_t *n_reads)
 {
 	try { return decompress_fastq_impl(folder, out_path, n_reads); } catch (...) { return -1; }
+}
+
+// ---- `minicom -q` archives back to FASTQ on the host: the rows of the default / paired-end decoder in memory,
+// the quality rows of folder/rqual.mcq (paired end: rqual_1.mcq and rqual_2.mcq) by the host twin -- they are stored in the archive's
+// own order, row j beside read j -- then records `@<j+1>`, read, `+`, qualities.  The cross-check of the _gpu routes: the same bytes,
+// the same archives refused (-p archives, an archive of the other kind, a missing member, one of another n or L than the reads, a
+// refused member); no output file is left then.
+namespace {
+bool exists(const std::string &path) { FILE *f = fopen(path.c_str(), "rb"); if (!f) return false; fclose(f); return true; }
+
+bool load_quals(const std::string &path, uint64_t n, int L, std::vector<uint8_t> &quals)
+{
+	std::vector<uint8_t> member;
+	if (!slurp(path, member)) return false;
+	uint64_t qn = 0; uint32_t qL = 0;
+	if (mcomh_qual_info(member.data(), member.size(), &qn, &qL) || qn != n || (int)qL != L) return false;
+	quals.assign((size_t)n * (size_t)L + 1, 0);
+	return !mcomh_qual_decode(member.data(), member.size(), quals.data(), (uint64_t)L, n, &qn, &qL) && qn == n && (int)qL == L;
+}
+
+bool write_records(const char *path, const std::vector<char> &reads, const std::vector<uint8_t> &quals, uint64_t n, int L)
+{
+	FILE *out = fopen(path, "wb");
+	if (!out) return false;
+	bool ok = true;
+	for (uint64_t i = 0; i < n && ok; ++i)
+		ok = fprintf(out, "@%llu\n", (unsigned long long)(i + 1)) > 0 && fwrite(reads.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0 &&
+		     fwrite(quals.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
+	if (fclose(out) != 0 || !ok) { remove(path); return false; }
+	return true;
+}
+}  // namespace
+
+static int decompress_fastq_reordered_impl(const char *folder, const char *out_path, uint64_t *n_reads)
+{
+	if (!folder || !out_path) return -1;
+	const std::string dir(folder);
+	if (exists(dir + "/allA.ids.bin") || exists(dir + "/file.bin.sp")) return -1;      // a -p or a paired-end archive
+	std::vector<char> reads; int L = 0; uint64_t n = 0;
+	if (decompress_impl(folder, nullptr, &n, &reads, &L)) return -1;
+	std::vector<uint8_t> quals;
+	if (!load_quals(dir + "/rqual.mcq", n, L, quals)) return -1;
+	if (!write_records(out_path, reads, quals, n, L)) return -1;
+	if (n_reads) *n_reads = n;
+	return 0;
+}
+
+static int decompress_fastq_pe_impl(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+{
+	if (!folder || !out_path1 || !out_path2) return -1;
+	const std::string dir(folder);
+	if (exists(dir + "/allA.ids.bin")) return -1;                                       // a -p archive
+	std::vector<char> r1, r2; int L = 0; uint64_t n = 0;
+	if (decompress_pe_impl(folder, nullptr, nullptr, &n, &r1, &r2, &L)) return -1;
+	std::vector<uint8_t> q1, q2;
+	if (!load_quals(dir + "/rqual_1.mcq", n, L, q1) || !load_quals(dir + "/rqual_2.mcq", n, L, q2)) return -1;
+	if (!write_records(out_path1, r1, q1, n, L)) return -1;
+	if (!write_records(out_path2, r2, q2, n, L)) { remove(out_path1); return -1; }
+	if (n_pairs) *n_pairs = n;
+	return 0;
+}
+
+extern "C" int mcomh_decompress_fastq_reordered(const char *folder, const char *out_path, uint64_t *n_reads)
+{
+	try { return decompress_fastq_reordered_impl(folder, out_path, n_reads); } catch (...) { return -1; }
+}
+
+extern "C" int mcomh_decompress_fastq_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+{
+	try { return decompress_fastq_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
 }

@@ -379,18 +379,33 @@ int guarded(Mode mode, const char *folder, const char *o1, const char *o2, uint6
 // ---- a -p -Q archive back to FASTQ: the third tail.  folder/qual.mcq is decoded on the device (mcom_qual_decode), the records
 // `@<i+1>`, read, `+`, qualities are laid out by mcom_fastq_emit a piece at a time, the copy of piece i under the write of piece i - 1.
 // With folder/name.mcn the names and '+' texts are decoded on the device as well and mcom_fastq_emit_named lays the records out.
-int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out)
+// a `.mcq` member of the folder decoded on the device into rows `pitch` apart; it must state the reads' number and length.  flag: the
+// command-line flag that makes such a member ("-Q" for qual.mcq, "-q" for rqual*.mcq): the refusals name the member and the flag
+std::string g_why;                                      // the text of a refusal made of a member's name (Refuse carries a pointer)
+[[noreturn]] void refuse_member(const std::string &why) { g_why = why; throw Refuse{g_why.c_str()}; }
+uint8_t *load_quals(Arena &A, const char *folder, const char *member_name, const char *flag, uint64_t n_rows, int L, uint64_t pitch)
 {
+	const std::string name(member_name);
 	std::vector<uint8_t> member;
-	if (!slurp(std::string(folder) + "/qual.mcq", member)) throw Refuse{"no qual.mcq: not a -Q archive"};
+	if (!slurp(std::string(folder) + "/" + name, member)) refuse_member("no " + name + ": not a " + flag + " archive");
 	uint64_t qn = 0; uint32_t qL = 0;
-	if (mcom_qual_info(member.data(), member.size(), &qn, &qL) || qn != n_rows || (int)qL != L) throw Refuse{"qual.mcq does not state the reads' number and length"};
+	if (mcom_qual_info(member.data(), member.size(), &qn, &qL) || qn != n_rows || (int)qL != L) refuse_member(name + " does not state the reads' number and length");
 	const uint8_t *d_member = A.upload(member.data(), member.size());
-	uint8_t *quals = A.alloc<uint8_t>(n_rows * (uint64_t)L);
-	if (mcom_qual_decode(A.ctx, d_member, member.size(), quals, (uint64_t)L, n_rows, &qn, &qL)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"qual.mcq is refused"}; }
+	uint8_t *quals = A.alloc<uint8_t>(n_rows * pitch);
+	if (mcom_qual_decode(A.ctx, d_member, member.size(), quals, pitch, n_rows, &qn, &qL)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); refuse_member(name + " is refused"); }
+	return quals;
+}
+
+// the two page-locked pieces and their device twins that the records travel through: made once per call, also where it writes two files
+struct EmitBufs { uint8_t *pin[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr}; bool made = false; };
+
+// quals_ready: the quality rows (pitch L) when the caller has decoded them already (the `minicom -q` tails: no names there)
+int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out, const uint8_t *quals_ready = nullptr, EmitBufs *shared = nullptr)
+{
+	const uint8_t *quals = quals_ready ? quals_ready : load_quals(A, folder, "qual.mcq", "-Q", n_rows, L, (uint64_t)L);
 	// folder/name.mcn (`minicom -N`, section 3.10): decoded on the device too; the records then carry its names and '+' texts
 	std::vector<uint8_t> nmember;
-	const bool named = slurp(std::string(folder) + "/name.mcn", nmember);
+	const bool named = !quals_ready && slurp(std::string(folder) + "/name.mcn", nmember);
 	uint8_t *d_names = nullptr; uint64_t *d_off = nullptr, names_bytes = 0;
 	std::vector<uint64_t> off;                                             // the record offsets of the name text, on the host: pieces are cut by them
 	if (named) {
@@ -418,13 +433,15 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 		piece_at.push_back(end);
 	}
 	const uint64_t pieces = piece_at.size() - 1;
-	uint8_t *pin[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
-	for (int b = 0; b < 2; ++b) {
+	EmitBufs own, &E = shared ? *shared : own;
+	for (int b = 0; b < 2 && !E.made; ++b) {
 		void *p = nullptr;
 		if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"};
-		A.pinned.push_back(p); pin[b] = (uint8_t*)p;
-		d_out[b] = A.alloc<uint8_t>(pieces ? PIECE_BYTES : 1);
+		A.pinned.push_back(p); E.pin[b] = (uint8_t*)p;
+		E.d_out[b] = A.alloc<uint8_t>(pieces ? PIECE_BYTES : 1);
 	}
+	E.made = true;
+	uint8_t *const *pin = E.pin, *const *d_out = E.d_out;
 	struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } arrived;   // piece i is in pin[i & 1]
 	for (int b = 0; b < 2; ++b) if (hipEventCreateWithFlags(&arrived.e[b], hipEventDisableTiming) != hipSuccess) throw Refuse{"no events"};
 	FILE *out = fopen(out_path, "wb");
@@ -516,6 +533,74 @@ int verify(const char *folder, int mode, const char *fastq1, const char *fastq2,
 	return 0;
 }
 
+// records with their quality lines (`minicom -q`): side a = the reads and quality rows of the FASTQ file(s) at pitch L, side b = the decoder's
+// image and the rows of rqual*.mcq decoded beside it at pitch L + 1; 2 parts in the default mode, 4 in the paired-end mode
+int verify_records(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
+{
+	const double t_begin = now_ms();
+	{
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { fprintf(stderr, "minicom verify: no GPU %d (%d visible); there is no host route\n", device, n_dev); return -1; }
+	}
+	const std::string dir(folder);
+	{
+		FILE *f = fopen((dir + "/allA.ids.bin").c_str(), "rb");
+		if (f) { fclose(f); fprintf(stderr, "minicom verify: %s is a -p archive\n", folder); return -1; }
+		f = fopen((dir + "/file.bin.sp").c_str(), "rb");
+		if (f) fclose(f);
+		if ((f != nullptr) != (mode == PE)) { fprintf(stderr, "minicom verify: %s is %sa paired-end archive\n", folder, f ? "" : "not "); return -1; }
+	}
+	struct Dev { uint8_t *d = nullptr; ~Dev() { mcomh_device_free(d); } } in, qin[2];
+	size_t n_in = 0, nq[2] = {0, 0}; int L_in = 0;
+	char err[320] = "";
+	const int rc = mode == PE ? mcomh_fastq_pair_to_device(fastq1, fastq2, device, &L_in, 0, &in.d, &n_in, err, sizeof(err))
+	                          : mcomh_fastq_to_device(fastq1, device, &L_in, 0, &in.d, &n_in, err, sizeof(err));
+	if (rc) { fprintf(stderr, "minicom verify: cannot read %s%s%s: %s\n", fastq1, mode == PE ? " and " : "", mode == PE ? fastq2 : "", err[0] ? err : "not a FASTQ file of reads of one length"); return -1; }
+	const char *fq[2] = {fastq1, fastq2};
+	const int n_files = mode == PE ? 2 : 1;
+	const size_t n_rec = mode == PE ? n_in / 2 : n_in;
+	for (int k = 0; k < n_files; ++k) {
+		if (L_in < 1 || mcomh_fastq_qualities_to_device(fq[k], device, L_in, 0, &qin[k].d, &nq[k], err, sizeof(err)) || nq[k] != n_rec) {
+			fprintf(stderr, "minicom verify: cannot read the qualities of %s: %s\n", fq[k], err[0] ? err : "another number of records than reads"); return -1;
+		}
+	}
+	const double ingest = now_ms() - t_begin;
+	const int rr = run((Mode)mode, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L) {
+		if (n_in && L_in != L) { fprintf(stderr, "minicom verify: the reads of the FASTQ are %d long, those of the archive %d\n", L_in, L); return -1; }
+		const uint64_t row = (uint64_t)L + 1, nb = mode == PE ? half : n_rows;
+		mcom_verify_parts a, b;
+		memset(&a, 0, sizeof a); memset(&b, 0, sizeof b);
+		a.pitch = (uint64_t)L; a.n = n_rec; b.pitch = row; b.n = nb;
+		if (mode == PE) {
+			a.n_parts = b.n_parts = 4;
+			a.d_part[0] = in.d; a.d_part[1] = in.d + n_rec * (uint64_t)L; a.d_part[2] = qin[0].d; a.d_part[3] = qin[1].d;
+			b.d_part[0] = table; b.d_part[1] = table + half * row;
+			b.d_part[2] = load_quals(A, folder, "rqual_1.mcq", "-q", nb, L, row); b.d_part[3] = load_quals(A, folder, "rqual_2.mcq", "-q", nb, L, row);
+		} else {
+			a.n_parts = b.n_parts = 2;
+			a.d_part[0] = in.d; a.d_part[1] = qin[0].d;
+			b.d_part[0] = table; b.d_part[1] = load_quals(A, folder, "rqual.mcq", "-q", nb, L, row);
+		}
+		const uint64_t room = mcom_verify_room(a.n, b.n);
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess || room > fr) { fprintf(stderr, "minicom verify: the card has no room for the records and their sort (%llu bytes needed, %zu free)\n", (unsigned long long)room, fr); return -1; }
+		const double t0 = now_ms();
+		mcom_verify_report r;
+		ok(A.ctx, mcom_verify_multiset_parts(A.ctx, &a, &b, L, &r));
+		rep->times_ms[3] = now_ms() - t0;
+		rep->identical = r.identical; rep->n_input = r.n_a; rep->n_archive = r.n_b;
+		rep->missing = r.missing; rep->extra = r.extra; rep->differing = r.differing; rep->first_diff = r.first_diff; rep->exact_runs = r.exact_runs;
+		rep->n_missing_ex = r.n_missing_ex; rep->n_extra_ex = r.n_extra_ex;
+		memcpy(rep->missing_ex, r.missing_ex, sizeof(r.missing_ex)); memcpy(rep->extra_ex, r.extra_ex, sizeof(r.extra_ex));
+		return 0;
+	});
+	if (rr) return -1;
+	rep->mode = mode;
+	rep->times_ms[0] = ingest; rep->times_ms[1] = g_times[1]; rep->times_ms[2] = g_times[2]; rep->times_ms[5] = g_times[0]; rep->times_ms[7] = g_times[3];
+	rep->times_ms[4] = now_ms() - t_begin;
+	return 0;
+}
+
 } // namespace
 
 extern "C" int mcomh_decompress_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(DEFAULT, folder, out_path, nullptr, n_reads, device); }
@@ -527,6 +612,46 @@ extern "C" int mcomh_decompress_fastq_gpu(const char *folder, const char *out_pa
 	try {
 		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) { return write_fastq(A, folder, table, n_rows, L, out_path, n_reads); });
 	} catch (...) { return -1; }
+}
+// ---- `minicom -q` archives: the default / paired-end decoder's rows, the quality rows of rqual*.mcq (stored in
+// the archive's own order) beside them, the records laid out as above.  What the host routes of mcom_decompress.cpp refuse is refused.
+static bool file_exists(const std::string &path) { FILE *f = fopen(path.c_str(), "rb"); if (!f) return false; fclose(f); return true; }
+extern "C" int mcomh_decompress_fastq_reordered_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device)
+{
+	if (!folder || !out_path) return -1;
+	if (file_exists(std::string(folder) + "/allA.ids.bin") || file_exists(std::string(folder) + "/file.bin.sp")) { fprintf(stderr, "minicom gpu decoder: %s is a -p or a paired-end archive\n", folder); return -1; }
+	try {
+		return run(DEFAULT, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			const uint8_t *q = load_quals(A, folder, "rqual.mcq", "-q", n_rows, L, (uint64_t)L);
+			return write_fastq(A, folder, table, n_rows, L, out_path, n_reads, q);
+		});
+	} catch (...) { return -1; }
+}
+extern "C" int mcomh_decompress_fastq_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device)
+{
+	if (!folder || !out_path1 || !out_path2) return -1;
+	if (file_exists(std::string(folder) + "/allA.ids.bin")) { fprintf(stderr, "minicom gpu decoder: %s is a -p archive\n", folder); return -1; }
+	try {
+		return run(PE, folder, device, [&](Arena &A, const uint8_t *table, uint64_t, uint64_t half, int L) {
+			const uint8_t *q1 = load_quals(A, folder, "rqual_1.mcq", "-q", half, L, (uint64_t)L), *q2 = load_quals(A, folder, "rqual_2.mcq", "-q", half, L, (uint64_t)L);   // (both before a file is opened)
+			EmitBufs bufs;                                                         // both files through the same two pieces
+			if (write_fastq(A, folder, table, half, L, out_path1, n_pairs, q1, &bufs)) return -1;
+			int rc = -1;
+			try { rc = write_fastq(A, folder, table + half * ((uint64_t)L + 1), half, L, out_path2, n_pairs, q2, &bufs); } catch (...) { remove(out_path1); throw; }
+			if (rc) remove(out_path1);
+			return rc;
+		});
+	} catch (...) { return -1; }
+}
+// ---- verification of a `minicom -q` archive: records of (read, quality) or (read 1, read 2, quality 1, quality 2) as multisets ----
+extern "C" int mcomh_verify_records_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
+{
+	if (!folder || !fastq1 || !rep || (mode != 0 && mode != 2) || (mode == PE) != (fastq2 != nullptr)) {
+		fprintf(stderr, "minicom verify: bad arguments (a folder, mode 0 default | 2 paired end, one FASTQ file, and the mates' file with mode 2 only)\n");
+		return -1;
+	}
+	memset(rep, 0, sizeof(*rep));
+	try { return verify_records(folder, mode, fastq1, fastq2, device, rep); } catch (...) { return -1; }
 }
 extern "C" void mcomh_decompress_gpu_times(double *ms8) { if (ms8) memcpy(ms8, g_times, sizeof(g_times)); }
 extern "C" int mcomh_verify_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)

@@ -301,6 +301,7 @@ struct mcomh_pipeline {
 	bool read_batches = false;                                        // kt_for_reads in batches over two streams (A/B switch: mcomh_params.read_batches = 1)
 	bool overlap_screen = false;                                      // true: the first Stage-2 pass's row gather + screen on the copy stream (A/B switch)
 	int stream_sets = 1;                                              // stream sets cluster_dump writes (the reference: one per thread)
+	bool keep_order = false;                                          // mcomh_keep_read_order: cluster_dump also writes FOLDER/read_order.bin (default and paired-end modes)
 	bool host_dump = false;                                           // true: cluster_dump's default mode on the host, as the -p / paired-end modes (A/B switch)
 	int window_scan = 0;                                              // 1: window-driven kernel (mcom_realign_pass) instead
 	bool stage2_uploaded = false;
@@ -2646,15 +2647,20 @@ static int cluster_dump_device(mcomh_pipeline *p, const char *folder, int mode)
 	}
 	// paired end: the pairing streams (kthread_dump_pe.c:270-470, :583-612) over the eight lists and over the members
 	PinVec<uint8_t> h_pe_sp, h_pe_0, h_fb_sp, h_fb_0;
+	// the ids of the eight lists in the decoder's order, on the device once: the pairing streams and the read order both walk them
+	std::vector<uint32_t> list_ids;
+	DevBuf<uint32_t> d_lists;
+	if (pe || p->keep_order) {
+		for (const std::vector<uint32_t> *v : {&allA, &allT, &allN, &fpA, &fpT, &fpN, &nfile, &single_ids}) list_ids.insert(list_ids.end(), v->begin(), v->end());
+		if (!d_lists.reserve(list_ids.size() + 1)) return p->fail(MCOM_E_NOMEM, "list buffers");
+		if (!list_ids.empty() && (rc = p->h2d(d_lists.p, list_ids.data(), list_ids.size(), "upload lists"))) return rc;
+	}
 	if (pe) {
-		std::vector<uint32_t> lists;
-		for (const std::vector<uint32_t> *v : {&allA, &allT, &allN, &fpA, &fpT, &fpN, &nfile, &single_ids}) lists.insert(lists.end(), v->begin(), v->end());
-		const size_t nl = lists.size(), nm = D.n ? (size_t)D.members : 0;
-		DevBuf<uint32_t> d_lists, d_isp, d_i0; DevBuf<uint8_t> d_fsp, d_f0;
-		if (!d_lists.reserve(nl + 1) || !d_isp.reserve(nl + 1) || !d_i0.reserve(nm + 1) || !d_fsp.reserve((nl + 7) / 8 + 16) || !d_f0.reserve((nm + 7) / 8 + 16)) return p->fail(MCOM_E_NOMEM, "pairing buffers");
+		const size_t nl = list_ids.size(), nm = D.n ? (size_t)D.members : 0;
+		DevBuf<uint32_t> d_isp, d_i0; DevBuf<uint8_t> d_fsp, d_f0;
+		if (!d_isp.reserve(nl + 1) || !d_i0.reserve(nm + 1) || !d_fsp.reserve((nl + 7) / 8 + 16) || !d_f0.reserve((nm + 7) / 8 + 16)) return p->fail(MCOM_E_NOMEM, "pairing buffers");
 		uint64_t cnt[2] = {0, 0};
-		if ((nl && (rc = p->h2d(d_lists.p, lists.data(), nl, "upload lists"))) ||
-		    (rc = p->gpu(mcom_dump_pairing_at(p->ctx, d_lists.p, nl, d_mem_dump, nm, half, d_isp.p, d_fsp.p, d_i0.p, d_f0.p, cnt, sm.data(), T + 1, ssecond.data())))) return rc;
+		if ((rc = p->gpu(mcom_dump_pairing_at(p->ctx, d_lists.p, nl, d_mem_dump, nm, half, d_isp.p, d_fsp.p, d_i0.p, d_f0.p, cnt, sm.data(), T + 1, ssecond.data())))) return rc;
 		// file.bin.T: a set's file bits packed from bit 0 (the byte ranges of dir.bin.T: one bit per member either way)
 		if (T > 1) { if (!d_f0.reserve((size_t)sdir[T] + 16)) return p->fail(MCOM_E_NOMEM, "pairing buffers");
 			for (int t = 0; t < T; ++t) if ((rc = p->gpu(mcom_dump_member_bits(p->ctx, d_mem_dump + sm[t], sm[t + 1] - sm[t], 1, half, d_f0.p + sdir[t])))) return rc; }
@@ -2662,6 +2668,19 @@ static int cluster_dump_device(mcomh_pipeline *p, const char *folder, int mode)
 		if (!h_pe_sp.resize(4 * cnt[0]) || !h_pe_0.resize(4 * cnt[1]) || !h_fb_sp.resize((nl + 7) / 8) || !h_fb_0.resize(f0_bytes)) return p->fail(MCOM_E_NOMEM, "pairing images");
 		if ((cnt[0] && (rc = p->d2h(h_pe_sp.data(), (const uint8_t*)d_isp.p, 4 * cnt[0], "copy pairing"))) || (cnt[1] && (rc = p->d2h(h_pe_0.data(), (const uint8_t*)d_i0.p, 4 * cnt[1], "copy pairing"))) ||
 		    (nl && (rc = p->d2h(h_fb_sp.data(), d_fsp.p, (nl + 7) / 8, "copy pairing"))) || (f0_bytes && (rc = p->d2h(h_fb_0.data(), d_f0.p, f0_bytes, "copy pairing"))) || (rc = p->sync("pairing streams"))) return rc;
+	}
+	// the read order: which input read the decoder's j-th row (paired end: j-th pair) is
+	PinVec<uint8_t> h_order;
+	if (p->keep_order) {
+		const size_t nl = list_ids.size(), nm = D.n ? (size_t)D.members : 0;
+		const uint64_t want = pe ? (uint64_t)half : (uint64_t)p->n;
+		DevBuf<uint32_t> d_order;
+		uint64_t rows = 0;
+		if (!d_order.reserve((size_t)want + 1) || !h_order.resize(4 * (size_t)want)) return p->fail(MCOM_E_NOMEM, "read order buffers");
+		if (nl + nm != p->n) return p->fail(MCOM_E_ARG, "read order: %zu listed reads + %zu members, but %zu reads", nl, nm, (size_t)p->n);
+		if ((rc = p->gpu(mcom_dump_read_order(p->ctx, d_lists.p, nl, d_mem_dump, nm, pe ? half : 0u, d_order.p, &rows)))) return rc;
+		if (rows != want) return p->fail(MCOM_E_ARG, "read order: %llu rows, %llu expected", (unsigned long long)rows, (unsigned long long)want);
+		if ((want && (rc = p->d2h(h_order.data(), (const uint8_t*)d_order.p, 4 * (size_t)want, "copy read order"))) || (rc = p->sync("read order"))) return rc;
 	}
 	p->stat["t_dump_gpu"] += now_ms() - t0;
 	const double tw = now_ms();
@@ -2684,6 +2703,7 @@ static int cluster_dump_device(mcomh_pipeline *p, const char *folder, int mode)
 		}
 	}
 	jobs.push_back(Job{dir + "/single.seq", h_single.data(), h_single.size()});
+	if (p->keep_order) jobs.push_back(Job{dir + "/read_order.bin", h_order.data(), h_order.size()});
 	if (pe) { jobs.push_back(Job{dir + "/peids.bin.sp", h_pe_sp.data(), h_pe_sp.size()}); jobs.push_back(Job{dir + "/file.bin.sp", h_fb_sp.data(), h_fb_sp.size()}); }
 	{
 		std::sort(jobs.begin(), jobs.end(), [](const Job &x, const Job &y) { return x.bytes > y.bytes; });   // the large ones first
@@ -2756,6 +2776,7 @@ static int cluster_dump_impl(mcomh_pipeline *p, const char *folder, int mode)
 	FILE *fids = order ? open("ids.bin.0", "wb") : pe ? open("ids.txt.0", "w") : nullptr;   // kthread_dump.c:266-269, kthread_dump_pe.c:150
 	if (!fref || !fpos || !fdir || !fdif || (sorted && !fids)) return p->fail(MCOM_E_ARG, "cannot write into %s", folder);
 	std::vector<uint32_t> pe_members;                                             // paired end: the members in stream order
+	std::vector<uint32_t> order_members, order_single;                            // read_order.bin: the members, and the packed singletons, in stream order
 	BitWriter refbin(fref, 2), dirbin(fdir, 1);
 	ContigSet &C = p->C;
 	std::vector<char> t((size_t)L + 1), en;
@@ -2778,6 +2799,7 @@ static int cluster_dump_impl(mcomh_pipeline *p, const char *folder, int mode)
 			const uint64_t y = mm[q];
 			const uint32_t rid = (uint32_t)(y >> 32); const int pos = (int)((uint32_t)y >> 1), dir = (int)(y & 1);
 			if (pe) { fprintf(fids, "%d %u\n", rid < half ? 0 : 1, rid); pe_members.push_back(rid); }   // kthread_dump_pe.c:70-74
+			if (p->keep_order) order_members.push_back(rid);
 			read_str(rid, t.data());
 			if (dir) {                                                         // reverse_complement, N stays N (preprocess.c:22-37)
 				for (int i = 0, j = L - 1; i < j; ++i, --j) std::swap(t[i], t[j]);
@@ -2827,12 +2849,12 @@ static int cluster_dump_impl(mcomh_pipeline *p, const char *folder, int mode)
 		const uint32_t rid = p->sg[i];
 		if (has_n(rid)) nfile.push_back(rid);
 		else if (sorted) single_ids.push_back(rid);                               // :409-411
-		else push_single(rid);
+		else { push_single(rid); if (p->keep_order) order_single.push_back(rid); }
 	}
 	std::vector<uint32_t> fpA = p->fpA, fpT = p->fpT, fpN = p->fpN;
+	std::vector<uint32_t> allA = p->allA, allT = p->allT, allN = p->allN;
 	if (sorted) {
 		// every list sorted by read id (:420-427); the singles follow their sorted ids
-		std::vector<uint32_t> allA = p->allA, allT = p->allT, allN = p->allN;
 		for (std::vector<uint32_t> *v : {&fpA, &fpT, &fpN, &nfile, &single_ids, &allA, &allT, &allN}) std::sort(v->begin(), v->end());
 		const std::string d(folder);
 		if (pe) {
@@ -2859,6 +2881,14 @@ static int cluster_dump_impl(mcomh_pipeline *p, const char *folder, int mode)
 		for (uint32_t rid : single_ids) push_single(rid);
 	}
 	sb.flush(); fclose(fsingle);
+	if (p->keep_order) {
+		// the read order, as mcom_dump_read_order makes it: the eight lists as written, then the members; paired end: the first file's reads only
+		std::vector<uint32_t> seq;
+		if (sorted) order_single = single_ids;
+		for (const std::vector<uint32_t> *v : {&allA, &allT, &allN, &fpA, &fpT, &fpN, &nfile, &order_single, &order_members}) for (uint32_t rid : *v) if (!pe || rid < half) seq.push_back(rid);
+		if (seq.size() != (pe ? (size_t)half : n)) return p->fail(MCOM_E_ARG, "read order: %zu rows, %zu expected", seq.size(), pe ? (size_t)half : n);
+		if (!write_file(std::string(folder) + "/read_order.bin", seq.data(), 4 * seq.size())) return p->fail(MCOM_E_ARG, "cannot write read_order.bin");
+	}
 	FILE *fa = open("AA.txt", "w"), *ft = open("TT.txt", "w"), *fn = open("NN.txt", "w"), *fnf = open("single_N.seq", "w");
 	if (!fa || !ft || !fn || !fnf) return p->fail(MCOM_E_ARG, "cannot write text streams");
 	for (uint32_t rid : fpA) { read_str(rid, t.data()); fprintf(fa, "%s\n", const_base_text(t.data(), L, 'A').c_str()); }   // :566-597
@@ -2871,6 +2901,19 @@ static int cluster_dump_impl(mcomh_pipeline *p, const char *folder, int mode)
 
 extern "C" int mcomh_cluster_dump(mcomh_pipeline *p, const char *folder) { return cluster_dump_impl(p, folder, 0); }
 // the order-preserving mode (minicom -p = the reference compiled with ORDER): id streams beside every stream
-extern "C" int mcomh_cluster_dump_order(mcomh_pipeline *p, const char *folder) { return cluster_dump_impl(p, folder, 1); }
+extern "C" int mcomh_cluster_dump_order(mcomh_pipeline *p, const char *folder)
+{
+	if (p && p->keep_order) return p->fail(MCOM_E_ARG, "the order-preserving mode stores its order in the id streams: mcomh_keep_read_order is for the default and paired-end modes");
+	return cluster_dump_impl(p, folder, 1);
+}
+// while the flag is on, cluster_dump (default or paired-end mode) also writes FOLDER/read_order.bin: `rows` little-endian u32, the input read of the
+// decoder's row j.  A pipeline with a communicator refuses.
+extern "C" int mcomh_keep_read_order(mcomh_pipeline *p, int on)
+{
+	if (!p) return MCOM_E_ARG;
+	if (on && p->comm) return p->fail(MCOM_E_ARG, "keep_read_order: the distributed pipeline does not write the read order");
+	p->keep_order = on != 0;
+	return MCOM_OK;
+}
 // paired end (minicompe = the reference compiled with _PE): reads [0, n/2) come from the first file, read n/2 + i is the mate of read i
 extern "C" int mcomh_cluster_dump_pe(mcomh_pipeline *p, const char *folder) { return cluster_dump_impl(p, folder, 2); }

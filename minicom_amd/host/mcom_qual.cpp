@@ -207,3 +207,23 @@ extern "C" int mcomh_qual_estimate(const uint8_t *rows, uint64_t n_rows, uint32_
 	choose(g, h4, n_rows, (n_rows + rps - 1) / rps, 0, m, est5);
 	return 0;
 }
+
+// rows through an order: the host twin of mcom_qual_gather_rows -- the same inputs refused, the same two flags
+// raised, an index outside the table not followed, a row named twice copied both times
+extern "C" int mcomh_qual_gather_rows(const uint8_t *rows, uint64_t n_src, uint32_t L, uint64_t pitch_in, const uint32_t *order, uint64_t n_rows, uint8_t *out, uint64_t pitch_out,
+                                      uint32_t *flag)
+{
+	if (!flag || (n_rows && (!order || !out)) || (n_src && !rows)) return -1;
+	if (L < 1 || L > L_MAX || pitch_in < L || pitch_out < L || n_src >= ((uint64_t)1 << 32) || n_rows >= ((uint64_t)1 << 32)) return -1;
+	try {
+		std::vector<bool> seen((size_t)n_src, false);
+		for (uint64_t j = 0; j < n_rows; ++j) {
+			const uint64_t s = order[j];
+			if (s >= n_src) { *flag |= MCOMH_GATHER_F_BOUNDS; continue; }
+			if (seen[(size_t)s]) *flag |= MCOMH_GATHER_F_DUP;
+			seen[(size_t)s] = true;
+			memcpy(out + j * pitch_out, rows + s * pitch_in, L);
+		}
+	} catch (const std::bad_alloc &) { return -1; }
+	return 0;
+}

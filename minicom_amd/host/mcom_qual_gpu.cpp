@@ -321,7 +321,74 @@ int fastq_member(const char *fastq, int L, int device, const char *out_path, uin
 	return 0;
 }
 
+// The same with the rows put into an archive's own order first (bin/mcomz e --fastq-qual L --order FILE; `minicom -q`, DESIGN.md section
+// 3.11): FILE is read_order.bin, one little-endian u32 per row of the member -- row j of the member is record order[j] of the FASTQ file.
+// The ingest and its per-record checks are those above; then mcom_qual_gather_rows (host: its twin), which is also the check that the
+// order is a permutation of the records; then the coder.  No member is written when the order's size is no multiple of 4, its entry
+// count differs from the record count, or a flag is raised.  On the GPU the matrix is held twice: refused when the card has no room.
+int fastq_member_ordered(const char *fastq, int L, int device, const char *order_path, const char *out_path, uint64_t *n_out, char *err, size_t err_cap)
+{
+	if (!fastq || !out_path || !order_path) return fail(err, err_cap, "null pointer");
+	std::vector<uint8_t> ob;
+	if (!slurp_file(order_path, ob)) return fail(err, err_cap, "cannot read the order file");
+	if (ob.size() % 4) return fail(err, err_cap, "the order file holds %llu bytes: not a multiple of 4", (unsigned long long)ob.size());
+	const uint64_t n_order = ob.size() / 4;
+	std::vector<uint32_t> order((size_t)n_order);
+	for (uint64_t j = 0; j < n_order; ++j) order[(size_t)j] = (uint32_t)ob[4 * j] | (uint32_t)ob[4 * j + 1] << 8 | (uint32_t)ob[4 * j + 2] << 16 | (uint32_t)ob[4 * j + 3] << 24;
+	std::vector<uint8_t> out;
+	uint64_t len = 0; size_t n = 0;
+	uint32_t flag = 0;
+	auto flagged = [&]() {
+		if (err && err_cap) snprintf(err, err_cap, "the order file is not a permutation of the records:%s%s", flag & MCOM_GATHER_F_BOUNDS ? " an entry beyond the last record" : "",
+		                             flag & MCOM_GATHER_F_DUP ? " a record named twice" : "");
+		return -1;
+	};
+	if (device < 0) {
+		std::vector<uint8_t> rows;
+		if (host_qualities(fastq, L, rows, n, err, err_cap)) return -1;
+		if (n_order != n) return fail(err, err_cap, "the order file holds %llu entries, the FASTQ file %llu records", (unsigned long long)n_order, (unsigned long long)n);
+		std::vector<uint8_t> sorted(rows.size() + 1);
+		if (mcomh_qual_gather_rows(rows.data(), n, (uint32_t)L, (uint64_t)L, order.data(), n, sorted.data(), (uint64_t)L, &flag)) return fail(err, err_cap, "the row gather failed");
+		if (flag) return flagged();
+		out.resize(mcomh_qual_bound(n, (uint32_t)L));
+		if (mcomh_qual_encode(sorted.data(), n, (uint32_t)L, (uint64_t)L, out.data(), out.size(), &len, 0)) return fail(err, err_cap, "the quality coder failed");
+	} else {
+		struct Rows { uint8_t *d = nullptr; ~Rows() { mcomh_device_free(d); } } in;
+		if (qualities(fastq, device, L, 0, &in.d, &n, err, err_cap)) return -1;
+		if (n_order != n) return fail(err, err_cap, "the order file holds %llu entries, the FASTQ file %llu records", (unsigned long long)n_order, (unsigned long long)n);
+		const uint64_t cap = mcomh_qual_bound(n, (uint32_t)L), raw = (uint64_t)n * (uint64_t)L;
+		struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d_out = nullptr, *d_sorted = nullptr; uint32_t *d_order = nullptr;
+		             ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d_out) (void)hipFree(d_out); if (d_sorted) (void)hipFree(d_sorted); if (d_order) (void)hipFree(d_order); if (ctx) mcom_destroy(ctx); } } D;
+		if (mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
+		{
+			size_t fr = 0, tot = 0;
+			const uint64_t need = raw + 4 * (uint64_t)n + n / 8 + cap + ((uint64_t)64 << 20);   // the second matrix, the order and its marks, the member
+			if (hipMemGetInfo(&fr, &tot) != hipSuccess || need > fr)
+				return fail(err, err_cap, "the card has no room to hold the quality rows twice (%llu more bytes needed, %llu free)", (unsigned long long)need, (unsigned long long)fr);
+		}
+		if (hipMalloc((void**)&D.d_sorted, raw + 16) != hipSuccess || hipMalloc((void**)&D.d_order, 4 * (size_t)n + 16) != hipSuccess || hipMalloc((void**)&D.d_out, cap + 16) != hipSuccess)
+			return fail(err, err_cap, "no room on the card");
+		uint32_t *d_flag = D.d_order + n;                                     // (the word behind the order: 16 spare bytes were taken)
+		if ((n && hipMemcpy(D.d_order, order.data(), 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) || hipMemset(d_flag, 0, 4) != hipSuccess) return fail(err, err_cap, "upload failed");
+		if (mcom_qual_gather_rows(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, D.d_order, n, D.d_sorted, (uint64_t)L, d_flag)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
+		if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "cannot read the flag word");
+		if (flag) return flagged();
+		if (mcom_qual_encode(D.ctx, D.d_sorted, n, (uint32_t)L, (uint64_t)L, D.d_out, cap, &len, 0)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
+		out.resize(len);
+		if (len && hipMemcpy(out.data(), D.d_out, len, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "download failed");
+	}
+	if (!write_file(out_path, out.data(), len)) return fail(err, err_cap, "cannot write the member");
+	if (n_out) *n_out = n;
+	return 0;
+}
+
 }  // namespace
+
+extern "C" int mcomh_fastq_quality_member_ordered(const char *fastq, int L, int device, const char *order_path, const char *out_path, uint64_t *n, char *err, size_t err_cap)
+{
+	if (err && err_cap) err[0] = 0;
+	try { return fastq_member_ordered(fastq, L, device, order_path, out_path, n, err, err_cap); } catch (...) { return -1; }
+}
 
 extern "C" int mcomh_fastq_quality_member(const char *fastq, int L, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap)
 {

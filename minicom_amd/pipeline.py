@@ -112,6 +112,14 @@ def load_host_library():
     L.mcomh_decompress_fastq.restype = i32; L.mcomh_decompress_fastq.argtypes = [cp, cp, C.POINTER(u64)]
     L.mcomh_decompress_fastq_gpu.restype = i32; L.mcomh_decompress_fastq_gpu.argtypes = [cp, cp, C.POINTER(u64), i32]
     L.mcomh_verify_quality_gpu.restype = i32; L.mcomh_verify_quality_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_keep_read_order.restype = i32; L.mcomh_keep_read_order.argtypes = [vp, i32]
+    L.mcomh_qual_gather_rows.restype = i32; L.mcomh_qual_gather_rows.argtypes = [vp, u64, u32, u64, vp, u64, vp, u64, C.POINTER(u32)]
+    L.mcomh_fastq_quality_member_ordered.restype = i32; L.mcomh_fastq_quality_member_ordered.argtypes = [cp, i32, i32, cp, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_decompress_fastq_reordered.restype = i32; L.mcomh_decompress_fastq_reordered.argtypes = [cp, cp, C.POINTER(u64)]
+    L.mcomh_decompress_fastq_reordered_gpu.restype = i32; L.mcomh_decompress_fastq_reordered_gpu.argtypes = [cp, cp, C.POINTER(u64), i32]
+    L.mcomh_decompress_fastq_pe.restype = i32; L.mcomh_decompress_fastq_pe.argtypes = [cp, cp, cp, C.POINTER(u64)]
+    L.mcomh_decompress_fastq_pe_gpu.restype = i32; L.mcomh_decompress_fastq_pe_gpu.argtypes = [cp, cp, cp, C.POINTER(u64), i32]
+    L.mcomh_verify_records_gpu.restype = i32; L.mcomh_verify_records_gpu.argtypes = [cp, i32, cp, cp, i32, C.POINTER(VerifyReport)]
     L.mcomh_name_bound.restype = u64; L.mcomh_name_bound.argtypes = [u64]
     L.mcomh_name_info.restype = i32; L.mcomh_name_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcomh_name_encode.restype = i32; L.mcomh_name_encode.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
@@ -143,6 +151,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_qual_bound", "mcomh_qual_info", "mcomh_qual_estimate", "mcomh_qual_encode", "mcomh_qual_decode",
                     "mcomh_qual_pack_file", "mcomh_qual_unpack_file", "mcomh_fastq_quality_member", "mcomh_device_copy",
                     "mcomh_fastq_qualities_to_device", "mcomh_decompress_fastq", "mcomh_decompress_fastq_gpu", "mcomh_verify_quality_gpu",
+                    # quality values in the archive's own order (`minicom -q`)
+                    "mcomh_keep_read_order", "mcomh_qual_gather_rows", "mcomh_fastq_quality_member_ordered", "mcomh_decompress_fastq_reordered",
+                    "mcomh_decompress_fastq_reordered_gpu", "mcomh_decompress_fastq_pe", "mcomh_decompress_fastq_pe_gpu", "mcomh_verify_records_gpu",
                     # read names and '+' lines (host/mcom_names.cpp)
                     "mcomh_name_bound", "mcomh_name_info", "mcomh_name_encode", "mcomh_name_decode", "mcomh_name_pack_file",
                     "mcomh_name_unpack_file", "mcomh_fastq_names_to_device", "mcomh_fastq_name_member", "mcomh_verify_names_gpu",
@@ -254,11 +265,18 @@ def fastq_qualities(path: str, L: int, device: int = 0, piece_bytes: int = 0):
     return out
 
 
-def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None = None) -> int:
+def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None = None, order_path: str | None = None) -> int:
     """mcomh_fastq_quality_member: the quality lines of a four-line FASTQ file -> the `.mcq` member file out_path; returns the number of
-    records.  device=None: the host twin (same record rules, same member); an integer: gathered and coded on that GPU."""
+    records.  device=None: the host twin (same record rules, same member); an integer: gathered and coded on that GPU.
+    order_path (mcomh_fastq_quality_member_ordered): a read_order.bin; row j of the member is then record order[j]
+    of the file.  McomError, and no member, when it is not a permutation of the records."""
     err = C.create_string_buffer(320)
     n = C.c_uint64()
+    if order_path is not None:
+        if load_host_library().mcomh_fastq_quality_member_ordered(os.fsencode(fastq), int(L), -1 if device is None else int(device), os.fsencode(order_path), os.fsencode(out_path),
+                                                                  C.byref(n), err, 320):
+            raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
+        return int(n.value)
     if load_host_library().mcomh_fastq_quality_member(os.fsencode(fastq), int(L), -1 if device is None else int(device), os.fsencode(out_path), C.byref(n), err, 320):
         raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
     return int(n.value)
@@ -275,6 +293,91 @@ def decompress_fastq(folder: str, out_path: str, device: int | None = None) -> i
     if rc:
         raise McomError(f"cannot decode {folder} to FASTQ" + ("" if device is None else f" on GPU {device}") + ": not a -p archive with qual.mcq, or a refused member")
     return int(n.value)
+
+
+def read_order(order) -> np.ndarray:
+    """A read order as a uint32 array: an array of row numbers as it is, or the bytes / the path of a read_order.bin (little-endian u32
+    values); McomError for a file whose size is no multiple of 4."""
+    if isinstance(order, (str, os.PathLike)):
+        with open(order, "rb") as f:
+            order = f.read()
+    if isinstance(order, (bytes, bytearray, memoryview)):
+        if len(order) % 4:
+            raise McomError("read order: %d bytes are not a multiple of 4" % len(order))
+        return np.frombuffer(bytes(order), dtype="<u4").astype(np.uint32)
+    a = np.asarray(order)
+    if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32)):
+        raise McomError("read order: a vector of row numbers below 2^32")
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+def qual_gather(rows, order, device: int | None = None):
+    """Quality rows put into a read order (DESIGN.md section 3.11): row j of the result is rows[order[j]].  rows: uint8 matrix [n, L] (numpy);
+    order: see read_order -- it must be a permutation of 0 .. n - 1, which the gather itself checks: McomError for another entry count, an
+    entry >= n or a row named twice.  device=None: mcomh_qual_gather_rows on the host; an integer: mcom_qual_gather_rows on that GPU (an
+    error, never the host twin, when there is none).  Returns a uint8 numpy matrix [n, L]."""
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.dtype != np.uint8 or (rows.shape[0] and rows.strides[1] != 1):
+        raise McomError("qual_gather: a uint8 matrix with contiguous rows")
+    o = read_order(order)
+    n, L = int(rows.shape[0]), int(rows.shape[1])
+    if int(o.shape[0]) != n:
+        raise McomError("qual_gather: the order holds %d entries for %d rows" % (int(o.shape[0]), n))
+    if device is None:
+        pitch = int(rows.strides[0]) if n > 1 else L
+        out = np.zeros((n, L), dtype=np.uint8)
+        flag = C.c_uint32(0)
+        if load_host_library().mcomh_qual_gather_rows(rows.ctypes.data if n else None, n, L, pitch, o.ctypes.data if n else None, n, out.ctypes.data if n else None, L, C.byref(flag)):
+            raise McomError("qual_gather: rows of %d bytes at pitch %d" % (L, pitch))
+        flags = int(flag.value)
+    else:
+        import torch
+        from .hip import Context
+        dev = f"cuda:{int(device)}"
+        d_out, flags = Context(int(device)).qual_gather_rows(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(o.view(np.int32)).to(dev))
+        out = d_out.cpu().numpy()
+    if flags:
+        raise McomError("qual_gather: the order is not a permutation of the rows:" + (" an entry beyond the last row" if flags & 1 else "") + (" a row named twice" if flags & 2 else ""))
+    return out
+
+
+def decompress_fastq_reordered(folder: str, out_path: str, device: int | None = None) -> int:
+    """mcomh_decompress_fastq_reordered(_gpu): the stream files of a default-mode archive and its rqual.mcq (`minicom -q`) -> records
+    `@<j+1>`, read, `+`, qualities in the archive's own order.  Returns the number of records; device as for decompress_fastq."""
+    n = C.c_uint64()
+    lib = load_host_library()
+    rc = lib.mcomh_decompress_fastq_reordered(os.fsencode(folder), os.fsencode(out_path), C.byref(n)) if device is None else \
+        lib.mcomh_decompress_fastq_reordered_gpu(os.fsencode(folder), os.fsencode(out_path), C.byref(n), int(device))
+    if rc:
+        raise McomError(f"cannot decode {folder} to FASTQ" + ("" if device is None else f" on GPU {device}") + ": not a default-mode archive with rqual.mcq, or a refused member")
+    return int(n.value)
+
+
+def decompress_fastq_pe(folder: str, out_path1: str, out_path2: str, device: int | None = None) -> int:
+    """mcomh_decompress_fastq_pe(_gpu): the stream files of a paired-end archive with rqual_1.mcq and rqual_2.mcq (`minicom -1 -2 -q`) -> two
+    FASTQ files, record j of one the mate of record j of the other, both named `@<j+1>`.  Returns the number of pairs."""
+    n = C.c_uint64()
+    lib = load_host_library()
+    rc = lib.mcomh_decompress_fastq_pe(os.fsencode(folder), os.fsencode(out_path1), os.fsencode(out_path2), C.byref(n)) if device is None else \
+        lib.mcomh_decompress_fastq_pe_gpu(os.fsencode(folder), os.fsencode(out_path1), os.fsencode(out_path2), C.byref(n), int(device))
+    if rc:
+        raise McomError(f"cannot decode {folder} to two FASTQ files" + ("" if device is None else f" on GPU {device}") + ": not a paired-end archive with rqual_1.mcq and rqual_2.mcq, or a refused member")
+    return int(n.value)
+
+
+def verify_records(folder: str, fastq: str, fastq2: str | None = None, device: int = 0) -> dict:
+    """mcomh_verify_records_gpu: does a `minicom -q` archive give back exactly the (read, quality) records of `fastq` -- with fastq2 the
+    (read 1, read 2, quality 1, quality 2) pairs -- as a multiset, duplicates counted?  Decided on GPU `device`, nothing is written.
+    McomError when no comparison could be made; a difference is a verdict, not an error."""
+    r = VerifyReport()
+    if load_host_library().mcomh_verify_records_gpu(os.fsencode(folder), 2 if fastq2 is not None else 0, os.fsencode(fastq), os.fsencode(fastq2) if fastq2 is not None else None,
+                                                    int(device), C.byref(r)):
+        raise McomError(f"cannot verify the records in {folder} against {fastq} on GPU {device}")
+    t = r.times_ms
+    return {"identical": bool(r.identical), "mode": ("default", "order", "paired")[r.mode], "n_input": int(r.n_input), "n_archive": int(r.n_archive),
+            "missing": int(r.missing), "extra": int(r.extra), "exact_runs": int(r.exact_runs),
+            "missing_examples": [int(v) for v in r.missing_ex[: r.n_missing_ex]], "extra_examples": [int(v) for v in r.extra_ex[: r.n_extra_ex]],
+            "times_ms": {"ingest": t[0], "upload_index": t[1], "decode": t[2], "compare": t[3], "total": t[4]}}
 
 
 def verify_quality(folder: str, fastq: str, device: int = 0) -> dict:
@@ -680,6 +783,10 @@ class Pipeline:
         return cr.value
 
     def dump_stages(self, path: str): self._check(self.lib.mcomh_dump_stages(self._h, path.encode()))
+
+    def keep_read_order(self, on: bool = True):
+        """mcomh_keep_read_order: while on, cluster_dump (default or paired) also writes folder/read_order.bin."""
+        self._check(self.lib.mcomh_keep_read_order(self._h, 1 if on else 0))
 
     def cluster_dump(self, folder: str, order: bool = False, paired: bool = False):
         """Writes the reference's pre-bsc stream files (cluster_dump at one thread) into an existing directory;
