@@ -306,6 +306,7 @@ extern "C" int mcom_merge_consensus_jobs(mcom_ctx *ctx, const uint64_t *d_packed
 {
 	if (!ctx) return MCOM_E_ARG;
 	if (nj == 0) return MCOM_OK;
+	if (L < 1 || L > 256) return mcom_fail(ctx, MCOM_E_ARG, "bad read length");
 	if (!d_packed || !d_jm || !d_jmoff || !d_jroff || !d_refs) return mcom_fail(ctx, MCOM_E_ARG, "null device pointer");
 	const bool regions = d_jobs && d_seq && d_soff;                          // parents known: count the overlaps only
 	const size_t max_tiles = (size_t)(total_chars / MC_TILE) + nj + 1, max_units = (size_t)(total_chars / 32) + nj + 1;

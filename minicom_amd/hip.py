@@ -637,11 +637,14 @@ class Context:
         self._check(self.lib.mcom_contig_layout(self._h, self._p(soff, torch.int64), n, self._p(coff), self._p(clen), C.byref(tw)))
         return coff, clen[:n], int(tw.value)
 
-    def group_consensus(self, packed, members, goff, L: int, k_orig: int, e: int):
-        """mcom_group_consensus.  members is rewritten in place.  Returns dict(keep, nkept, sv, reflen, refs, stride)."""
+    def group_consensus(self, packed, members, goff, L: int, k_orig: int, e: int, stride=None):
+        """mcom_group_consensus.  members is rewritten in place.  Returns dict(keep, nkept, sv, reflen, refs, stride).
+        stride: bytes between two groups' strings in refs (None: 2L rounded up to 16; one that is no multiple of 4 keeps every group
+        away from the bit-sliced kernel)."""
         torch = _torch()
         ng, nm = int(goff.shape[0]) - 1, int(members.shape[0])
-        stride = (2 * L + 15) & ~15
+        stride = (2 * L + 15) & ~15 if stride is None else int(stride)
+        assert stride >= 0
         o = dict(keep=torch.empty(max(nm, 1), dtype=torch.uint8, device=self.device), nkept=torch.empty(max(ng, 1), dtype=torch.int32, device=self.device),
                  sv=torch.empty(max(ng, 1), dtype=torch.int16, device=self.device), reflen=torch.empty(max(ng, 1), dtype=torch.int16, device=self.device),
                  refs=torch.zeros(max(ng, 1) * stride + 16, dtype=torch.uint8, device=self.device), stride=stride)

@@ -5,9 +5,9 @@ find_next's member merge kthread_cb.c:297-325, construct_ref2 :105-218, cp_clust
 import numpy as np
 import pytest
 
+from consensus_reference import ACGT, COMP, _construct_ref, _majority, _oriented
+
 pytestmark = pytest.mark.gpu
-ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
-COMP = np.zeros(256, dtype=np.uint8); COMP[[65, 67, 71, 84]] = [84, 71, 67, 65]
 
 
 @pytest.fixture(scope="module")
@@ -21,19 +21,6 @@ def ctx():
 def _dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _oriented(read, d):
-    return COMP[read][::-1] if d else read
-
-
-def _majority(cols):
-    """counts [4][n] -> base per column, ties to the smaller code A < C < G < T (strict '>' scan, kthread_bucket.c:129-141)."""
-    best = np.zeros(cols.shape[1], dtype=np.int64); mx = cols[0].copy()
-    for q in (1, 2, 3):
-        m = cols[q] > mx
-        best[m] = q; mx[m] = cols[q][m]
-    return best, mx
 
 
 def test_scan_u64_and_contig_layout(ctx):
@@ -80,38 +67,6 @@ def _make_groups(rng, n_groups, L, k, e):
         goff.append(len(members))
     reads = np.stack(reads)
     return reads, pack_nt4(reads), np.array(members, dtype=np.uint64), np.array(goff, dtype=np.int32)
-
-
-def _construct_ref(reads, members, L, k, e):
-    """construct_ref for one group (kthread_bucket.c:69-377): returns (keep flags, new member words, sv, consensus bytes)."""
-    al, ds, rids = [], [], []
-    for y in members.tolist():
-        rid, pos, d = y >> 32, (y & 0xFFFFFFFF) >> 1, y & 1
-        al.append(L - pos + k - 2 if d else pos); ds.append(d); rids.append(rid)
-    offs = [al[0] - a for a in al]
-    TL = 2 * L
-    c1 = np.zeros((4, TL), dtype=np.int64)
-    ors = [(_oriented(reads[r], d) >> 1 ^ _oriented(reads[r], d) >> 2) & 3 for r, d in zip(rids, ds)]
-    for o, code in zip(offs, ors):
-        c1[code, o + np.arange(L)] += 1
-    first, mx = _majority(c1)
-    ref_len = int(np.argmax(mx == 0)) if (mx == 0).any() else TL
-    keep, c2, rend = [], np.zeros((4, TL), dtype=np.int64), 0
-    for o, code in zip(offs, ors):
-        cols = o + np.arange(L)
-        dif = int(((cols >= ref_len) | (first[np.minimum(cols, TL - 1)] != code)).sum())
-        kp = dif <= e                                                          # :189
-        keep.append(kp)
-        if kp:
-            c2[code, cols] += 1; rend = max(rend, o + L)
-    nk = sum(keep)
-    new = [(r << 32) | (o << 1) | d for r, o, d in zip(rids, offs, ds)]
-    if not nk:
-        return keep, new, 0, b""
-    cov = c2.sum(axis=0)[:ref_len] > 0
-    sv = int(np.argmax(cov)) if cov.any() else ref_len
-    second, _ = _majority(c2)
-    return keep, new, sv, ACGT[second[sv:rend]].tobytes()
 
 
 @pytest.mark.parametrize("L,k,e", [(100, 31, 4), (150, 31, 4), (64, 17, 2), (250, 31, 4), (40, 17, 2), (33, 11, 1)])
@@ -176,9 +131,11 @@ def _random_set(rng, n, L):
     return refs, mems, reads, pack_nt4(reads)
 
 
-@pytest.mark.parametrize("L", [100, 150, 250, 40])
+@pytest.mark.parametrize("L", [100, 150, 250, 40, 16, 32, 33, 256])
 def test_merge_round_pieces_against_numpy(ctx, L):
-    """One merge round on a random set: member merge, consensus (every column, and overlap only), carry of the rest."""
+    """One merge round on a random set: member merge, consensus (every column, and overlap only), carry of the rest.
+    L = 16, 32, 33 and 256 are the read-length edges of the consensus kernels: reads shorter than a 32-column unit, exactly one unit,
+    one base more, and the longest read the entry points take."""
     import torch
     rng = np.random.default_rng(77 + L)
     n = 300
@@ -191,7 +148,8 @@ def test_merge_round_pieces_against_numpy(ctx, L):
     jobs = []
     for j in range(90):
         ci, cj = int(perm[2 * j]), int(perm[2 * j + 1])
-        jobs.append((ci, cj, int(rng.integers(30, len(refs[ci]))), int(rng.integers(30, min(len(refs[cj]), 60)))))
+        amin = min(30, L - 2)                                                   # anchors lie inside the shortest contig (L columns)
+        jobs.append((ci, cj, int(rng.integers(amin, len(refs[ci]))), int(rng.integers(amin, min(len(refs[cj]), 60)))))
     flag = np.zeros(n, dtype=np.uint8)
     for ci, cj, _, _ in jobs:
         flag[ci] = flag[cj] = 1
@@ -251,7 +209,7 @@ def test_merge_round_pieces_against_numpy(ctx, L):
     for c in range(nn):
         assert s2[so2[c]:so2[c + 1]] == all_refs[c] and m2[mo2[c]:mo2[c + 1]].tolist() == all_mems[c], c
     # minimizers of the untouched contigs keep their values and take the new contig index
-    moff_r, rec = ctx.sketch_contigs(d_seq, d_soff, n, 19, 31)
+    moff_r, rec = ctx.sketch_contigs(d_seq, d_soff, n, *((19, 31) if L >= 32 else (5, 11)))      # k-mers no longer than the shortest contig
     ctx.sync()
     base = 1234
     rec2 = ctx.empty_records(base + int(rec.shape[0]) + 8)
