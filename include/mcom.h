@@ -848,6 +848,21 @@ int mcom_name_info(const uint8_t *h_member_prefix, uint64_t len, uint64_t *n_rec
 int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_text, uint64_t cap, uint64_t *text_len,
                      uint64_t *n_records, uint64_t *d_rec_off);
 int mcom_name_text_offsets(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n_records, uint64_t *d_rec_off);
+/* Kind 2: the name text of the second file of a pair coded against the first file's name text, its mate -- token t
+ * of record r against token t of the mate's name r, text tokens that match copied from the mate text.  Both texts are device buffers read
+ * up to their last byte and no further.
+ *   mcom_name_encode_mate  makes mcom_name_encode's member as well and keeps kind 2 only where it is strictly smaller: never a larger
+ *                     member than without a mate, the same bytes as mcomh_name_encode_mate.  MCOM_E_ARG also for a mate text that is not
+ *                     2 n_records complete lines of at most 255 bytes.
+ *   mcom_name_info_mate    mcom_name_info for a reader that holds a mate: kind 2 is a header too
+ *   mcom_name_decode_mate  takes kinds 0 and 1 as mcom_name_decode does (the mate is not looked at) and kind 2 against d_mate: MCOM_E_ARG
+ *                     for a mate of another n_records or another crc32, for MATCH / INC / DELTA on a token the mate does not have or of
+ *                     the wrong class, and for everything mcom_name_decode refuses.  mcom_name_decode itself refuses kind 2. */
+int mcom_name_encode_mate(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n_records, const uint8_t *d_mate, uint64_t mate_len,
+                          uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint64_t *bad_record);
+int mcom_name_info_mate(const uint8_t *h_member_prefix, uint64_t len, uint64_t *n_records, uint64_t *text_len);
+int mcom_name_decode_mate(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, const uint8_t *d_mate, uint64_t mate_len, uint8_t *d_text, uint64_t cap,
+                          uint64_t *text_len, uint64_t *n_records);
 int mcom_name_compare(mcom_ctx *ctx, const uint8_t *d_a, const uint64_t *d_off_a, uint64_t bytes_a, const uint8_t *d_b,
                       const uint64_t *d_off_b, uint64_t bytes_b, uint64_t n, uint64_t *differing, uint64_t *first_diff);
 /* The FASTQ ends of the name coder, siblings of mcom_fastq_quality_rows / mcom_fastq_emit over the same line index.

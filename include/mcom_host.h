@@ -369,6 +369,51 @@ int mcomh_name_encode(const uint8_t *text, uint64_t text_len, uint64_t n_records
 int mcomh_name_decode(const uint8_t *in, uint64_t in_len, uint8_t *text, uint64_t cap, uint64_t *text_len, uint64_t *n_records);
 int mcomh_name_pack_file(const char *in_path, const char *out_path, int device);
 int mcomh_name_unpack_file(const char *in_path, const char *out_path, int device);
+/* Kind 2: the name text of the second file of a pair against the first file's name text, its mate.  The host
+ * twins of mcom_name_encode_mate / mcom_name_info_mate / mcom_name_decode_mate (include/mcom.h): the same bytes, the same refusals.
+ *   mcomh_name_encode_mate  the member of mcomh_name_encode unless kind 2 is strictly smaller; -1 also for a mate that is not 2 n lines
+ *   mcomh_name_decode_mate  kinds 0 and 1 as mcomh_name_decode (the mate is not looked at); kind 2 against `mate`, -1 for a mate of
+ *                           another n_records or another crc32.  mcomh_name_decode itself refuses kind 2.
+ *   mcomh_name_pack_file_mate / _unpack_file_mate   the file forms with mate_path, a file of name text (bin/mcomz e --names --mate, d --mate)
+ *   mcomh_fastq_name_member_mate   mcomh_fastq_name_member for the second file of a pair: both files' name texts are gathered as there,
+ *                           the member of fastq2 is coded against the names of fastq1; an error when the files differ in records      */
+int mcomh_name_info_mate(const uint8_t *prefix, uint64_t len, uint64_t *n_records, uint64_t *text_len);
+int mcomh_name_encode_mate(const uint8_t *text, uint64_t text_len, uint64_t n_records, const uint8_t *mate, uint64_t mate_len, uint8_t *out,
+                           uint64_t cap, uint64_t *out_len, uint64_t *bad_record);
+int mcomh_name_decode_mate(const uint8_t *in, uint64_t in_len, const uint8_t *mate, uint64_t mate_len, uint8_t *text, uint64_t cap,
+                           uint64_t *text_len, uint64_t *n_records);
+int mcomh_name_pack_file_mate(const char *in_path, const char *mate_path, const char *out_path, int device);
+int mcomh_name_unpack_file_mate(const char *in_path, const char *mate_path, const char *out_path, int device);
+int mcomh_fastq_name_member_mate(const char *fastq2, const char *fastq1, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap);
+
+/* ---- `minicom -1 A_1.fastq -2 A_2.fastq -p [-Q [-N]]`: a pair kept in input order ----
+ * The pipeline holds the second file's reads behind the first's, so the order-preserving dump of the 2 n rows is the archive's read part;
+ * FOLDER/pe_order.txt (one line, `<n_pairs>`) marks it.  -Q adds qual_1.mcq and qual_2.mcq (n rows each), -N name_1.mcn (kind 0 or 1) and
+ * name_2.mcn, coded against the first file's names where that is smaller.
+ *   mcomh_cluster_dump_order_pe        mcomh_cluster_dump_order and pe_order.txt; refuses an odd number of reads
+ *   mcomh_decompress_order_pe[_gpu]    rows [0, n) -> out_path1, [n, 2 n) -> out_path2, in input order
+ *   mcomh_decompress_fastq_order_pe[_gpu]  four-line records: `@<j+1>` and a bare '+' in both files, or the names and '+' texts of
+ *                                      name_1.mcn / name_2.mcn (name_2 decoded with the decoded name_1 text as its mate): with both, the two
+ *                                      files are the two inputs byte for byte.  Host and GPU routes write the same bytes.
+ *   mcomh_verify_order_pe_reads_gpu    the reads of both files line against line with the decoded rows (mode 1)
+ *   mcomh_verify_quality_member_gpu / mcomh_verify_names_member_gpu   mcomh_verify_quality_gpu / mcomh_verify_names_gpu for a member of another
+ *                                      name; mate_member (may be NULL): the member of the folder the name member is decoded against
+ *   mcomh_verify_order_pe_parts_gpu    all checks the archive's members allow: part 0 the reads, 1 / 2 the quality lines of file 1 / 2,
+ *                                      3 / 4 the names and '+' lines of file 1 / 2; present[k] says which were made
+ *   mcomh_verify_order_pe_gpu          the same as one verdict
+ * Refused, with neither output file left: no pe_order.txt or one that is not half the reads' number; one quality member of two; a member
+ * of another n or L; name_2 without name_1 or the reverse; names without quality values (the FASTQ decoders need qual_*.mcq); any refused
+ * member.  The decoders of every other archive are what they were.                                                                     */
+int mcomh_cluster_dump_order_pe(mcomh_pipeline *p, const char *folder);
+int mcomh_decompress_order_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs);
+int mcomh_decompress_order_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device);
+int mcomh_decompress_fastq_order_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs);
+int mcomh_decompress_fastq_order_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device);
+int mcomh_verify_order_pe_reads_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep);
+int mcomh_verify_quality_member_gpu(const char *folder, const char *member, const char *fastq, int device, mcomh_verify_report *rep);
+int mcomh_verify_names_member_gpu(const char *folder, const char *member, const char *mate_member, const char *fastq, int device, mcomh_verify_report *rep);
+int mcomh_verify_order_pe_parts_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report rep[5], int present[5]);
+int mcomh_verify_order_pe_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep);
 /* ---- `minicom -N`: a -p -Q archive that also carries read names and '+' texts, as the member name.mcn in input order ----
  *   mcomh_fastq_names_to_device  the name text of a four-line FASTQ file (plain or .gz) in HBM (*d_names, *bytes long; release with
  *                                mcomh_device_free; *n records), through two page-locked pieces of piece_bytes (0 = 32 MiB) with the

@@ -43,6 +43,8 @@ SINGLES = ("single_N.seq", "single.seq", "AA.txt", "TT.txt", "NN.txt")      # :1
 NAME_MEMBER = "name.mcn"          # read names and '+' texts of a -p -Q archive: stored as it is
 REORDERED_MEMBERS = ("rqual.mcq", "rqual_1.mcq", "rqual_2.mcq")     # quality values in the archive's own order
 READ_ORDER = "read_order.bin"     # temporary of compress_fastq(quality_reordered=True): never a member
+PAIR_ORDER = "pe_order.txt"       # marks a pair kept in input order: one line, the number of pairs; stored as it is
+PAIR_MEMBERS = ("qual_1.mcq", "qual_2.mcq", "name_1.mcn", "name_2.mcn")     # its quality values and names, file by file; name_2 is coded against name_1
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -155,7 +157,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
     if os.path.isfile(os.path.join(folder, NAME_MEMBER)):        # likewise (section 3.10)
         with open(os.path.join(folder, NAME_MEMBER), "rb") as f:
             packed.append((NAME_MEMBER, f.read()))
-    for m in REORDERED_MEMBERS:                                  # likewise (section 3.11)
+    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS:   # likewise (sections 3.11 and 3.12)
         if os.path.isfile(os.path.join(folder, m)):
             with open(os.path.join(folder, m), "rb") as f:
                 packed.append((m, f.read()))
@@ -176,7 +178,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
     """`.minicom` file -> the stream files in `folder` (created if absent).  Returns what the archive says about itself:
     {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334), and "quality": True for an archive
     that carries quality values (the member qual.mcq, left in the folder as it is), "quality_reordered": True for one that carries them
-    in its own order (rqual.mcq, or rqual_1.mcq and rqual_2.mcq).
+    in its own order (rqual.mcq, or rqual_1.mcq and rqual_2.mcq), "pair_order": True for a pair kept in input order (pe_order.txt; then
+    "quality" / "names" speak of qual_1.mcq + qual_2.mcq / name_1.mcn + name_2.mcn).
     device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
@@ -185,7 +188,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS:
+        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -207,6 +210,10 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             kinds["names"] = True
         if name in REORDERED_MEMBERS:
             kinds["quality_reordered"] = True
+        if name == PAIR_ORDER:
+            kinds["pair_order"] = True
+        if name in PAIR_MEMBERS:
+            kinds["quality" if name.endswith(".mcq") else "names"] = True
         if name.startswith("idsbin.tar"):
             kinds["order"] = True
         if name.startswith("filebin.tar"):
@@ -238,6 +245,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     own order on `device` and travel as rqual.mcq (rqual_1.mcq and rqual_2.mcq for a pair); decompress_file gives four-line records in that
     order, named by their row.  Returns pack()'s member sizes plus the read count."""
     import tempfile
+    from .hip import McomError
     from .pipeline import Pipeline
     if order and path2 is not None:
         raise ValueError("-p is a single-end option (reference minicom:439-476)")
@@ -274,6 +282,37 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.close()
 
 
+def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = False, names: bool = False, codec: str = "xz", device: int = 0,
+                        threads: int = 8, **params) -> dict:
+    """Two FASTQ files of a pair -> a `.minicom` archive that keeps both in input order (`minicom -1 A_1.fastq -2 A_2.fastq -p [-Q [-N]]`,
+    DESIGN.md section 3.12): the order-preserving members of the second file's reads behind the first's, and pe_order.txt.  quality=True:
+    qual_1.mcq and qual_2.mcq; names=True (needs quality=True): name_1.mcn and name_2.mcn, the second coded against the first file's names
+    -- decompress_file then gives both input files back byte for byte.  Returns pack()'s member sizes plus the number of pairs."""
+    import tempfile
+    from .hip import McomError
+    from .pipeline import Pipeline, fastq_name_member
+    if names and not quality:
+        raise ValueError("names are kept beside the quality values only (quality=True)")
+    p = Pipeline.from_fastq(path1, device=device, path2=path2, host_threads=threads, **params)
+    try:
+        p.pre_process()
+        with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
+            p.cluster_dump_order_pe(td)
+            half = p.n // 2
+            for k, fq in ((1, path1), (2, path2)):
+                if quality:
+                    _quality_member(fq, half, p.L, device, os.path.join(td, "qual_%d.mcq" % k))
+                if names:
+                    n_names = fastq_name_member(fq, os.path.join(td, "name_%d.mcn" % k), device=device, mate_path=path1 if k == 2 else None)
+                    if n_names != half:
+                        raise McomError("%s: %d names for %d reads" % (fq, n_names, half))
+            sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
+        sizes["n_pairs"] = half
+        return sizes
+    finally:
+        p.close()
+
+
 def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str) -> None:
     """the quality lines of `fastq` -> rows on the device -> a `.mcq` member in out_path"""
     from .hip import Context, McomError
@@ -297,6 +336,11 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
     from .pipeline import decompress, decompress_fastq, decompress_pe
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        if kinds.get("pair_order"):                                  # seen first: its other members are those of a -p archive
+            from .pipeline import decompress_order_pe
+            if out_path2 is None:
+                raise ValueError("an archive of a pair decodes into two files")
+            return decompress_order_pe(td, out_path, out_path2, device=device, fastq=bool(kinds.get("quality") or kinds.get("names")))
         if kinds.get("quality_reordered"):
             from .pipeline import decompress_fastq_reordered, decompress_fastq_pe
             if kinds["paired"]:
@@ -326,6 +370,11 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
         raise McomError("no such archive: %s" % path)
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        if kinds.get("pair_order"):
+            from .pipeline import verify_order_pe
+            if fastq2 is None:
+                raise McomError("an archive of a pair is verified against two FASTQ files")
+            return verify_order_pe(td, fastq, fastq2, device=device)
         if kinds["paired"] != (fastq2 is not None):
             raise McomError("a paired-end archive is verified against two FASTQ files, any other against one")
         if kinds.get("quality_reordered"):

@@ -19,6 +19,11 @@
 //               | 3 NUM (the value, u32 -> num) | 4 TEXT (length u8 -> tlen, bytes -> text) | 5 END
 //   plus      per record: 0 the third line is a bare '+' | 1 its text equals the name | 2 a literal
 //   ptext     the lengths (u8) of all literals, record after record, then their bytes, literal after literal
+//   kind 2     the name text of the second file of a pair, coded against the first file's name text, its MATE:
+//             the seven streams and the op bytes of kind 0, but token t of record r is coded against token t of the mate's line 2 r cut
+//             by the token rule (never against the record before: recs_per_seg = 1), and a MATCH of a text token takes its bytes from
+//             the mate text.  Offset 88 holds the crc32 of the mate text (u32), then 0 u32; n_records is the mate's.  Only a reader that
+//             is handed the mate (read_nheader(.., true), walk_record_mate) takes kind 2; every other one refuses it as before.
 // All integers little endian.
 #pragma once
 #include <stdint.h>
@@ -37,7 +42,7 @@ namespace mcom_name {
 
 using mcom_rans::put_u16; using mcom_rans::put_u32; using mcom_rans::put_u64; using mcom_rans::get_u16; using mcom_rans::get_u32; using mcom_rans::get_u64;
 
-enum { KIND_STREAMS = 0, KIND_RANS = 1 };
+enum { KIND_STREAMS = 0, KIND_RANS = 1, KIND_MATE = 2 };
 enum { S_OPS = 0, S_DELTA, S_NUM, S_TLEN, S_TEXT, S_PLUS, S_PTEXT, N_STREAMS };
 enum { OP_MATCH = 0, OP_INC, OP_DELTA, OP_NUM, OP_TEXT, OP_END };
 enum { PLUS_BARE = 0, PLUS_NAME = 1, PLUS_LITERAL = 2 };
@@ -49,7 +54,8 @@ enum { NM_F_OP = 1,        // an op above 5, a plus byte above 2
        NM_F_LONG = 16,     // a name or '+' text above 255 bytes
        NM_F_NL = 32,       // a '\n' inside a text token or a literal
        NM_F_RUN = 64,      // a stream read beyond its end (cannot be once the counts agree)
-       NM_F_LINES = 128 }; // encoder: the name text is not 2 n complete lines
+       NM_F_LINES = 128,   // encoder: the name text is not 2 n complete lines
+       NM_F_MATE = 256 };  // kind 2: the mate text is not the 2 n lines (of at most 255 bytes) the member was coded against
 constexpr size_t NHEADER_BYTES = 96;
 constexpr uint32_t TOKEN_CAP = 24, NM_NAME_MAX = 255, RPS = 256, RPS_MAX = 4096, VALUE_END = 1000000000u, NUMERIC = 0xFFFFFFFFu;
 constexpr uint64_t N_MAX = 0xFFFFFFFFull / (TOKEN_CAP + 1);        // the ops of n records stay below 4 GiB whatever the names: 171 798 691
@@ -58,7 +64,7 @@ constexpr uint64_t TEXT_MAX = mcom_bwt::RAW_MAX;                   // a stream i
 struct NHeader {
 	uint8_t kind = KIND_STREAMS;
 	uint64_t n_records = 0, text_len = 0;
-	uint32_t crc = 0, rps = RPS;
+	uint32_t crc = 0, rps = RPS, mate_crc = 0;                  // mate_crc: kind 2 alone
 	uint64_t len[N_STREAMS] = {0, 0, 0, 0, 0, 0, 0};
 	uint64_t n_seg() const { return (n_records + rps - 1) / rps; }
 	uint64_t streams_bytes() const { uint64_t s = 0; for (int k = 0; k < N_STREAMS; ++k) s += len[k]; return s; }
@@ -68,23 +74,26 @@ static inline void write_nheader(uint8_t *p, const NHeader &h)
 	memcpy(p, "MCNM", 4); p[4] = 1; p[5] = h.kind; p[6] = (uint8_t)TOKEN_CAP; p[7] = 0;
 	put_u64(p + 8, h.n_records); put_u64(p + 16, h.text_len); put_u32(p + 24, h.crc); put_u16(p + 28, h.rps); put_u16(p + 30, 0);
 	for (int k = 0; k < N_STREAMS; ++k) put_u64(p + 32 + 8 * k, h.len[k]);
-	put_u64(p + 88, 0);
+	put_u32(p + 88, h.kind == KIND_MATE ? h.mate_crc : 0); put_u32(p + 92, 0);
 }
-// the fields alone, from the first 96 bytes: magic, version and the ranges every member keeps
-static inline bool read_nfields(const uint8_t *p, uint64_t len, NHeader &h)
+// the fields alone, from the first 96 bytes: magic, version and the ranges every member keeps.  mate: the reader holds a mate text, so
+// kind 2 is taken as well (recs_per_seg 1, the mate's crc at offset 88)
+static inline bool read_nfields(const uint8_t *p, uint64_t len, NHeader &h, bool mate = false)
 {
 	if (len < NHEADER_BYTES || memcmp(p, "MCNM", 4) || p[4] != 1) return false;
 	h.kind = p[5];
 	h.n_records = get_u64(p + 8); h.text_len = get_u64(p + 16); h.crc = get_u32(p + 24); h.rps = get_u16(p + 28);
 	for (int k = 0; k < N_STREAMS; ++k) h.len[k] = get_u64(p + 32 + 8 * k);
-	if (h.kind > KIND_RANS || p[6] != TOKEN_CAP || p[7] != 0 || get_u16(p + 30) != 0 || get_u64(p + 88) != 0) return false;
+	if (h.kind > (mate ? KIND_MATE : KIND_RANS) || p[6] != TOKEN_CAP || p[7] != 0 || get_u16(p + 30) != 0 || get_u32(p + 92) != 0) return false;
+	h.mate_crc = get_u32(p + 88);
+	if (h.kind == KIND_MATE ? h.rps != 1 : h.mate_crc != 0) return false;
 	if (h.rps < 1 || h.rps > RPS_MAX || h.n_records > N_MAX || h.text_len > TEXT_MAX) return false;
 	return h.text_len >= 2 * h.n_records && h.text_len <= 2 * (uint64_t)(NM_NAME_MAX + 1) * h.n_records;
 }
 // Everything the header says about sizes, against the member's length: true only when the member is exactly as long as it says.
-static inline bool read_nheader(const uint8_t *p, uint64_t len, NHeader &h)
+static inline bool read_nheader(const uint8_t *p, uint64_t len, NHeader &h, bool mate = false)
 {
-	if (!read_nfields(p, len, h)) return false;
+	if (!read_nfields(p, len, h, mate)) return false;
 	const uint64_t rest = len - NHEADER_BYTES;
 	if (h.kind == KIND_RANS) {
 		if (h.n_records == 0 || h.streams_bytes() != 0) return false;
@@ -152,8 +161,9 @@ MCOM_NM_HD static inline bool same_bytes(const uint8_t *a, const uint8_t *b, uin
 
 // ---- the op rule: one record against the one before it (plen tokens of prv count only when !first) ---------------------------------------
 // Sink: op(u8), delta(u8), num(u32), text(bytes, len) [the length goes to tlen, the bytes to text], plus(u8), literal(bytes, len).
+// Returns the record's plus kind, so that a caller that only counts need not take the literal's length through its sink.
 template <class Sink>
-MCOM_NM_HD static inline void code_record(const uint8_t *cur, uint32_t clen, const uint8_t *prv, uint32_t plen, bool first,
+MCOM_NM_HD static inline uint32_t code_record(const uint8_t *cur, uint32_t clen, const uint8_t *prv, uint32_t plen, bool first,
                                           const uint8_t *pl, uint32_t pl_len, Sink &s)
 {
 	uint32_t cpos = 0, ppos = 0;
@@ -168,9 +178,10 @@ MCOM_NM_HD static inline void code_record(const uint8_t *cur, uint32_t clen, con
 		else { s.op(OP_TEXT); s.text(cur + c.at, c.len); }
 	}
 	s.op(OP_END);
-	if (pl_len == 0) s.plus(PLUS_BARE);
-	else if (pl_len == clen && same_bytes(pl, cur, clen)) s.plus(PLUS_NAME);
-	else { s.plus(PLUS_LITERAL); s.literal(pl, pl_len); }
+	const uint32_t kind = pl_len == 0 ? (uint32_t)PLUS_BARE : pl_len == clen && same_bytes(pl, cur, clen) ? (uint32_t)PLUS_NAME : (uint32_t)PLUS_LITERAL;
+	s.plus(kind);
+	if (kind == PLUS_LITERAL) s.literal(pl, pl_len);
+	return kind;
 }
 
 // ---- the record walk: the decoder's one step ---------------------------------------------------------------------------------------------
@@ -220,6 +231,53 @@ MCOM_NM_HD static inline uint32_t walk_record(const View &v, Cursor &c, Tab &tab
 		}
 		tab.val(t) = val; tab.len(t) = len;
 		nl += bytes; ++t;
+	}
+	return NM_F_TOKENS;                                          // (not reached: step TOKEN_CAP returns)
+}
+
+// The same step for kind 2: the tokens of the mate's name m[0 .. mlen) stand where the record before stood.  They are cut by the token
+// rule as the walk goes (token t only ever looks at mate token t), so nothing is kept between records and a lane can take any record.
+// A MATCH of a text token copies the mate's bytes.  Reads nothing outside the streams and m[0 .. mlen); writes at most `room` bytes.
+MCOM_NM_HD static inline uint32_t walk_record_mate(const View &v, Cursor &c, const uint8_t *m, uint32_t mlen, uint8_t *out, uint32_t room, uint32_t &name_len)
+{
+	uint32_t nl = 0, mpos = 0;
+	bool have_m = true;
+	Tok k;
+	for (uint32_t step = 0; step <= TOKEN_CAP; ++step) {
+		if (c.op >= v.n_ops) return NM_F_RUN;
+		const uint32_t op = v.ops[c.op++];
+		if (op == OP_END) { name_len = nl; return 0; }
+		if (op > OP_END) return NM_F_OP;
+		if (step == TOKEN_CAP) return NM_F_TOKENS;
+		have_m = have_m && next_token(m, mlen, mpos, step, k);
+		uint32_t val = 0, len = NUMERIC;
+		const uint8_t *src = v.text;
+		if (op <= OP_DELTA) {
+			if (!have_m) return NM_F_PREV;
+			if (op == OP_MATCH) { if (k.num) val = k.val; else { len = k.len; val = k.at; src = m; } }
+			else {
+				if (!k.num) return NM_F_PREV;
+				uint32_t d = 1;
+				if (op == OP_DELTA) { if (c.delta >= v.n_delta) return NM_F_RUN; d = v.delta[c.delta++]; }
+				val = k.val + d;                                       // (k.val < 10^9, d <= 255)
+			}
+		} else if (op == OP_NUM) {
+			if (c.num >= v.n_num) return NM_F_RUN;
+			{ const uint8_t *q = v.num + 4 * c.num++; val = q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24; }
+		} else {
+			if (c.tlen >= v.n_tlen) return NM_F_RUN;
+			len = v.tlen[c.tlen++];
+			if (len > v.n_text - c.text) return NM_F_RUN;
+			val = (uint32_t)c.text; c.text += len;
+		}
+		if (len == NUMERIC && val >= VALUE_END) return NM_F_VALUE;
+		const uint32_t bytes = len == NUMERIC ? n_digits(val) : len;
+		if (nl + bytes > room) return NM_F_LONG;
+		if (out) {
+			if (len == NUMERIC) put_digits(out + nl, val, bytes);
+			else for (uint32_t j = 0; j < bytes; ++j) out[nl + j] = src[(uint64_t)val + j];
+		}
+		nl += bytes;
 	}
 	return NM_F_TOKENS;                                          // (not reached: step TOKEN_CAP returns)
 }

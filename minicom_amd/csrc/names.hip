@@ -1,6 +1,6 @@
 // minicom_amd/csrc/names.hip -- read names and '+' lines as `.mcn` members: names cut into tokens, coded against the record before,
 // seven streams through the block-sorting coder (format, token rule, op rule, record walk: name_model.hpp; specification and
-// cross-check: host/mcom_names.cpp).
+// cross-check: host/mcom_names.cpp; DESIGN.md sections 3.10 and 3.12).
 //
 // encode
 //   (mcom_decode_line_index)  the 2 n lines of the name text
@@ -26,6 +26,13 @@
 // of section 3.5): header ranges, member lengths and the embedded members' raw lengths are judged on the host before a launch; the
 // counts above are compared on the host between launches; inside the kernels whatever becomes an index is compared with the size of
 // what it indexes, a violation raises the flag word and the access is skipped.
+//
+// kind 2 (section 3.12), a name text against the name text of its mate file:
+//   encode          k_name_count / k_name_write with the mate's line index: record r and the mate's name r go through code_record side by
+//                   side; mcom_name_encode's member is made first and kept unless the kind-2 member is strictly smaller
+//   decode          recs_per_seg is 1, so the scans above give every RECORD its cursors; k_name_walk_mate<0 / 1>, one lane per record,
+//                   cuts the mate's name r into tokens as it goes (name_model.hpp's walk_record_mate) and copies matched text tokens from
+//                   the mate text: no table, no chain from record to record
 //
 // FASTQ ends (`minicom -N`): k_fastq_name_lens / k_fastq_name_copy (text -> name text, sixteen lanes per record), k_fastq_emit_named
 // (rows and name text -> records), k_name_compare (two name texts, record against record).
@@ -54,14 +61,22 @@ unsigned grid_capped(mcom_ctx *ctx, uint64_t items)
 }  // namespace
 
 // ---- encode ----------------------------------------------------------------------------------------------------------------------------
+// (The bytes of a record's literal are not counted here: a record has at most one, of pl_len bytes, and k_name_count takes that length
+// itself from the plus kind code_record returns, behind an optimisation barrier.  Summed in literal(), or selected from pl_len in plain
+// sight, the code that hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0) makes for gfx950 at -O3 gave 0 bytes to a '+'
+// text that is as long as the name without being the name: the value is set to pl_len before code_record's compare loop and cleared
+// behind it for every lane that ran the loop, whatever the loop found, so the member came out without its literal bytes.  DESIGN.md
+// section 3.12 has the assembly and a reduced form of the source.  k_name_write runs the same code_record into stores, which cannot be
+// folded that way; tests/test_gpu_mate_names.py holds both kernels to the host twin's bytes on exactly such records.  Check the
+// barrier again with every new compiler: without it that test fails.)
 struct NmCountSink {
-	uint32_t ops = 0, n_delta = 0, n_num = 0, n_tlen = 0, n_text = 0, n_lit = 0, n_ptext = 0;
+	uint32_t ops = 0, n_delta = 0, n_num = 0, n_tlen = 0, n_text = 0, n_lit = 0;
 	__device__ void op(uint32_t) { ++ops; }
 	__device__ void delta(uint8_t) { ++n_delta; }
 	__device__ void num(uint32_t) { ++n_num; }
 	__device__ void text(const uint8_t *, uint32_t n) { ++n_tlen; n_text += n; }
 	__device__ void plus(uint32_t) {}
-	__device__ void literal(const uint8_t *, uint32_t n) { ++n_lit; n_ptext += n; }
+	__device__ void literal(const uint8_t *, uint32_t) { ++n_lit; }
 };
 struct NmWriteSink {
 	uint8_t *ops, *deltas, *nums, *tlens, *texts, *plus_at, *lit_len, *lit_bytes;
@@ -74,13 +89,18 @@ struct NmWriteSink {
 };
 // the three lines a record is coded from; false: one of them is longer than NM_NAME_MAX (the record, or the one after it, is flagged)
 struct NmLines { const uint8_t *cur, *prv, *pl; uint32_t clen, plen, pl_len; bool first; };
-__device__ __forceinline__ bool nm_lines(const uint8_t *text, const uint64_t *start, uint64_t r, uint32_t rps, NmLines &l)
+// mate != NULL (kind 2): the record is coded against line 2 r of the mate text, never against the record before
+__device__ __forceinline__ bool nm_lines(const uint8_t *text, const uint64_t *start, uint64_t r, uint32_t rps, const uint8_t *mate, const uint64_t *mstart, NmLines &l)
 {
 	const uint64_t a = start[2 * r], b = start[2 * r + 1], c = start[2 * r + 2];
 	if (!(a < b && b < c) || b - 1 - a > NM_NAME_MAX || c - 1 - b > NM_NAME_MAX) return false;
 	l.cur = text + a; l.clen = (uint32_t)(b - 1 - a); l.pl = text + b; l.pl_len = (uint32_t)(c - 1 - b);
-	l.first = r % rps == 0; l.prv = l.cur; l.plen = 0;
-	if (!l.first) {
+	l.first = !mate && r % rps == 0; l.prv = l.cur; l.plen = 0;
+	if (mate) {
+		const uint64_t p = mstart[2 * r], q = mstart[2 * r + 1];
+		if (!(p < q) || q - 1 - p > NM_NAME_MAX) return false;
+		l.prv = mate + p; l.plen = (uint32_t)(q - 1 - p);
+	} else if (!l.first) {
 		const uint64_t p = start[2 * r - 2], q = start[2 * r - 1];
 		if (!(p < q) || q - 1 - p > NM_NAME_MAX) return false;
 		l.prv = text + p; l.plen = (uint32_t)(q - 1 - p);
@@ -90,33 +110,39 @@ __device__ __forceinline__ bool nm_lines(const uint8_t *text, const uint64_t *st
 
 // cnt: four arrays of n + 1 words behind one another: ops << 32 | deltas, nums << 32 | tlens, text bytes << 32 | literal bytes, literals
 __global__ __launch_bounds__(NM_THREADS) void k_name_count(const uint8_t *__restrict__ text, uint64_t text_len, const uint64_t *__restrict__ start, uint64_t n, uint32_t rps,
-                                                           uint64_t *__restrict__ cnt, uint32_t *__restrict__ flag)
+                                                           const uint8_t *__restrict__ mate, const uint64_t *__restrict__ mstart, uint64_t *__restrict__ cnt, uint32_t *__restrict__ flag)
 {
 	const uint64_t r = (uint64_t)blockIdx.x * NM_THREADS + threadIdx.x;
 	if (r == 0 && start[2 * n] != text_len) atomicOr(&flag[0], (uint32_t)NM_F_LINES);
 	if (r > n) return;
 	NmCountSink s;
+	uint32_t n_ptext = 0;
 	if (r < n) {
 		NmLines l;
 		const uint64_t a = start[2 * r], b = start[2 * r + 1], c = start[2 * r + 2];
 		if (c > text_len || !(a < b && b < c)) atomicOr(&flag[0], (uint32_t)NM_F_LINES);
 		else if (b - 1 - a > NM_NAME_MAX || c - 1 - b > NM_NAME_MAX) { atomicOr(&flag[0], (uint32_t)NM_F_LONG); atomicMin(&flag[1], (uint32_t)r); }
-		else if (nm_lines(text, start, r, rps, l)) code_record(l.cur, l.clen, l.prv, l.plen, l.first, l.pl, l.pl_len, s);
+		else if (nm_lines(text, start, r, rps, mate, mstart, l)) {
+			const uint32_t kind = code_record(l.cur, l.clen, l.prv, l.plen, l.first, l.pl, l.pl_len, s);
+			uint32_t pl = l.pl_len;
+			asm volatile("" : "+v"(pl));                                          // (see NmCountSink)
+			n_ptext = kind == PLUS_LITERAL ? pl : 0u;
+		}
 	}
 	cnt[r] = (uint64_t)s.ops << 32 | s.n_delta;
 	cnt[(n + 1) + r] = (uint64_t)s.n_num << 32 | s.n_tlen;
-	cnt[2 * (n + 1) + r] = (uint64_t)s.n_text << 32 | s.n_ptext;
+	cnt[2 * (n + 1) + r] = (uint64_t)s.n_text << 32 | n_ptext;
 	cnt[3 * (n + 1) + r] = s.n_lit;
 }
 
 // off: the scans of cnt.  streams: the seven streams behind one another at base[0 .. 6]; n_lit: literals in all
-__global__ __launch_bounds__(NM_THREADS) void k_name_write(const uint8_t *__restrict__ text, const uint64_t *__restrict__ start, uint64_t n, uint32_t rps, const uint64_t *__restrict__ off,
-                                                           uint8_t *__restrict__ streams, const uint64_t *__restrict__ base, uint64_t n_lit)
+__global__ __launch_bounds__(NM_THREADS) void k_name_write(const uint8_t *__restrict__ text, const uint64_t *__restrict__ start, uint64_t n, uint32_t rps,
+                                                           const uint8_t *__restrict__ mate, const uint64_t *__restrict__ mstart, const uint64_t *__restrict__ off, uint8_t *__restrict__ streams, const uint64_t *__restrict__ base, uint64_t n_lit)
 {
 	const uint64_t r = (uint64_t)blockIdx.x * NM_THREADS + threadIdx.x;
 	if (r >= n) return;
 	NmLines l;
-	if (!nm_lines(text, start, r, rps, l)) return;                          // (cannot be: the count pass flagged it and nothing is written then)
+	if (!nm_lines(text, start, r, rps, mate, mstart, l)) return;                          // (cannot be: the count pass flagged it and nothing is written then)
 	const uint64_t a = off[r], b = off[(n + 1) + r], c = off[2 * (n + 1) + r], d = off[3 * (n + 1) + r];
 	NmWriteSink s;
 	s.ops = streams + base[S_OPS] + (a >> 32); s.deltas = streams + base[S_DELTA] + (a & 0xFFFFFFFFu);
@@ -236,6 +262,57 @@ __global__ __launch_bounds__(NM_WALK_THREADS) void k_name_walk(NmDecodeArgs A, u
 	if (bad) atomicOr(flag, bad);
 }
 
+// Kind 2: one lane per record.  A record's cursors are what k_name_walk reads for a segment (recs_per_seg is 1: seg_op[r] is record r's
+// first op); its mate name is line 2 r of the mate text (mstart: the mate's line index, checked by k_name_lines before the launch).
+// WRITE as above.  A refused record reads nothing outside the streams and the mate text and writes at most its own room.
+template <int WRITE>
+__global__ __launch_bounds__(NM_THREADS) void k_name_walk_mate(NmDecodeArgs A, const uint8_t *__restrict__ mate, uint64_t mate_len, const uint64_t *__restrict__ mstart,
+                                                               uint64_t *__restrict__ rec, uint8_t *__restrict__ out, uint32_t *__restrict__ flag)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * NM_THREADS + threadIdx.x;
+	if (r >= A.n) return;
+	uint32_t bad = 0;
+	do {
+		const uint64_t ma = mstart[2 * r], mb = mstart[2 * r + 1];
+		if (!(ma < mb) || mb > mate_len || mb - 1 - ma > NM_NAME_MAX) { bad = NM_F_MATE; break; }
+		Cursor c;
+		c.op = A.seg_op[r];
+		if (c.op > A.v.n_ops) { bad = NM_F_RUN; break; }
+		c.tlen = A.sa[c.op] & 0xFFFFFFFFu; c.delta = A.sb[c.op] >> 32; c.num = A.sb[c.op] & 0xFFFFFFFFu;
+		if (c.tlen > A.v.n_tlen || c.delta > A.v.n_delta || c.num > A.v.n_num) { bad = NM_F_RUN; break; }
+		c.text = A.st[c.tlen];
+		const uint64_t lit = A.sp[r];
+		if (lit > A.n_lit) { bad = NM_F_RUN; break; }
+		const uint64_t lit_at = A.n_lit + A.sl[lit];
+		uint8_t *o = nullptr; uint32_t room = NM_NAME_MAX, have = 0;
+		if (WRITE) {
+			const uint64_t at = rec[r], end = rec[r + 1];
+			if (end < at || end > A.text_len || end - at < 2) { bad = NM_F_RUN; break; }
+			o = out + at; have = (uint32_t)(end - at < 2 * NM_NAME_MAX + 2 ? end - at : 2 * NM_NAME_MAX + 2) - 2;
+			room = have < NM_NAME_MAX ? have : NM_NAME_MAX;
+		}
+		uint32_t nl = 0;
+		if ((bad = walk_record_mate(A.v, c, mate + ma, (uint32_t)(mb - 1 - ma), o, room, nl))) break;
+		const uint32_t kind = A.plus[r];
+		uint32_t pl = 0;
+		if (kind == PLUS_NAME) pl = nl;
+		else if (kind == PLUS_LITERAL) {
+			if (lit >= A.n_lit) { bad = NM_F_RUN; break; }
+			pl = A.ptext[lit];
+			if (lit_at + pl > A.n_ptext) { bad = NM_F_RUN; break; }
+		} else if (kind != PLUS_BARE) { bad = NM_F_OP; break; }
+		if (WRITE) {
+			if (nl + pl != have) { bad = NM_F_RUN; break; }                     // (cannot be: the first walk measured this record)
+			o[nl] = '\n';
+			uint8_t *q = o + nl + 1;
+			if (kind == PLUS_NAME) for (uint32_t j = 0; j < nl; ++j) q[j] = o[j];
+			else if (kind == PLUS_LITERAL) for (uint32_t j = 0; j < pl; ++j) q[j] = A.ptext[lit_at + j];
+			q[pl] = '\n';
+		} else rec[r] = (uint64_t)nl + pl + 2;
+	} while (0);
+	if (bad) atomicOr(flag, bad);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 extern "C" uint64_t mcom_name_bound(uint64_t text_len) { return bound(text_len); }
 
@@ -247,26 +324,12 @@ extern "C" int mcom_name_info(const uint8_t *h_member_prefix, uint64_t len, uint
 	return 0;
 }
 
-extern "C" int mcom_name_encode(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint64_t *bad_record)
+// The seven streams of a name text of n > 0 records as `.bwt` members behind one another: *coded (a block of B), *coded_len bytes, their
+// lengths in hd.len.  d_mate NULL: every record against the one before it (hd.rps records a segment); otherwise against line 2 r of the
+// mate text, whose line index mstart the caller has checked.
+static int name_streams(mcom_ctx *ctx, Blocks &B, const uint8_t *d_text, uint64_t text_len, uint64_t n, const uint8_t *d_mate, const uint64_t *mstart, NHeader &hd,
+                        uint8_t **coded_out, uint64_t *coded_len, uint64_t *bad_record)
 {
-	if (!ctx) return MCOM_E_ARG;
-	if (bad_record) *bad_record = ~(uint64_t)0;
-	if (!out_len || !d_out || (text_len && !d_text)) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: null pointer");
-	*out_len = 0;
-	if (n > N_MAX || text_len > TEXT_MAX) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: %llu records, %llu bytes of name text (at most %llu records; a text below 4 GiB: larger ones are not split)",
-	                                                     (unsigned long long)n, (unsigned long long)text_len, (unsigned long long)N_MAX);
-	if (text_len < 2 * n || (n == 0 && text_len)) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: %llu bytes are not the two lines of each of %llu records", (unsigned long long)text_len, (unsigned long long)n);
-	if (cap < NHEADER_BYTES) return mcom_fail(ctx, MCOM_E_OVERFLOW, "name_encode: room for %llu bytes", (unsigned long long)cap);
-	NHeader hd; hd.n_records = n; hd.text_len = text_len;
-	uint8_t head[NHEADER_BYTES];
-	if (n == 0) {
-		write_nheader(head, hd);
-		MCOM_HIP(ctx, hipMemcpyAsync(d_out, head, NHEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
-		MCOM_HIP(ctx, mcom_stream_sync(ctx));
-		*out_len = NHEADER_BYTES;
-		return MCOM_OK;
-	}
-	Blocks B(ctx);
 	int rc;
 	// the lines, and what every record adds to every stream
 	uint64_t *start = nullptr, *cnt = nullptr; uint32_t *d_flag = nullptr;
@@ -282,7 +345,7 @@ extern "C" int mcom_name_encode(mcom_ctx *ctx, const uint8_t *d_text, uint64_t t
 	if ((rc = mcom_decode_line_index(ctx, d_text, text_len, nullptr, 0, &lines, nullptr))) return rc;
 	if (lines != 2 * n) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: %llu lines, not the two lines of each of %llu records", (unsigned long long)lines, (unsigned long long)n);
 	if ((rc = mcom_decode_line_index(ctx, d_text, text_len, start, 2 * n, &lines, d_flag + 2))) return rc;
-	MCOM_LAUNCH(k_name_count, dim3(blocks_for(n + 1)), dim3(NM_THREADS), 0, ctx->stream, d_text, text_len, (const uint64_t*)start, n, hd.rps, cnt, d_flag);
+	MCOM_LAUNCH(k_name_count, dim3(blocks_for(n + 1)), dim3(NM_THREADS), 0, ctx->stream, d_text, text_len, (const uint64_t*)start, n, hd.rps, d_mate, mstart, cnt, d_flag);
 	MCOM_LAUNCH_CHECK(ctx);
 	for (int k = 0; k < 4; ++k) if ((rc = mcom_scan64(ctx, cnt + k * (n + 1), cnt + k * (n + 1), n + 1, nullptr))) return rc;
 	uint64_t tot[4]; uint32_t flag[4];
@@ -308,17 +371,53 @@ extern "C" int mcom_name_encode(mcom_ctx *ctx, const uint8_t *d_text, uint64_t t
 	MCOM_HIP(ctx, B.get(&d_base, sizeof base));
 	MCOM_HIP(ctx, hipMemcpyAsync(d_base, base, sizeof base, hipMemcpyHostToDevice, ctx->stream));
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));                                    // (base lives on this frame)
-	MCOM_LAUNCH(k_name_write, dim3(blocks_for(n)), dim3(NM_THREADS), 0, ctx->stream, d_text, (const uint64_t*)start, n, hd.rps, (const uint64_t*)cnt, streams, (const uint64_t*)d_base, n_lit);
+	MCOM_LAUNCH(k_name_write, dim3(blocks_for(n)), dim3(NM_THREADS), 0, ctx->stream, d_text, (const uint64_t*)start, n, hd.rps, d_mate, mstart, (const uint64_t*)cnt, streams, (const uint64_t*)d_base, n_lit);
 	MCOM_LAUNCH_CHECK(ctx);
 	// the seven members, back to back as the member holds them
 	MCOM_HIP(ctx, B.get(&coded, room));
 	uint64_t at = 0;
 	for (int k = 0; k < N_STREAMS; ++k) {
+		hd.len[k] = 0;
 		if (!raw[k]) continue;
 		uint64_t got = 0;
 		if ((rc = mcom_bwt_encode(ctx, streams + base[k], raw[k], coded + at, room - at, &got))) return rc;
 		hd.len[k] = got; at += got;
 	}
+	*coded_out = coded; *coded_len = at;
+	return MCOM_OK;
+}
+
+extern "C" int mcom_name_info_mate(const uint8_t *h_member_prefix, uint64_t len, uint64_t *n_records, uint64_t *text_len)
+{
+	NHeader hd;
+	if (!h_member_prefix || !n_records || !text_len || !read_nfields(h_member_prefix, len, hd, true)) return -1;
+	*n_records = hd.n_records; *text_len = hd.text_len;
+	return 0;
+}
+
+extern "C" int mcom_name_encode(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint64_t *bad_record)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (bad_record) *bad_record = ~(uint64_t)0;
+	if (!out_len || !d_out || (text_len && !d_text)) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: null pointer");
+	*out_len = 0;
+	if (n > N_MAX || text_len > TEXT_MAX) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: %llu records, %llu bytes of name text (at most %llu records; a text below 4 GiB: larger ones are not split)",
+	                                                     (unsigned long long)n, (unsigned long long)text_len, (unsigned long long)N_MAX);
+	if (text_len < 2 * n || (n == 0 && text_len)) return mcom_fail(ctx, MCOM_E_ARG, "name_encode: %llu bytes are not the two lines of each of %llu records", (unsigned long long)text_len, (unsigned long long)n);
+	if (cap < NHEADER_BYTES) return mcom_fail(ctx, MCOM_E_OVERFLOW, "name_encode: room for %llu bytes", (unsigned long long)cap);
+	NHeader hd; hd.n_records = n; hd.text_len = text_len;
+	uint8_t head[NHEADER_BYTES];
+	if (n == 0) {
+		write_nheader(head, hd);
+		MCOM_HIP(ctx, hipMemcpyAsync(d_out, head, NHEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+		MCOM_HIP(ctx, mcom_stream_sync(ctx));
+		*out_len = NHEADER_BYTES;
+		return MCOM_OK;
+	}
+	Blocks B(ctx);
+	int rc;
+	uint8_t *coded = nullptr; uint64_t at = 0;
+	if ((rc = name_streams(ctx, B, d_text, text_len, n, nullptr, nullptr, hd, &coded, &at, bad_record))) return rc;
 	if ((rc = mcom_device_crc32(ctx, d_text, text_len, &hd.crc))) return rc;
 	uint64_t total = NHEADER_BYTES + at;
 	// kind 1, made last: the `.rans` member of the name text
@@ -339,6 +438,40 @@ extern "C" int mcom_name_encode(mcom_ctx *ctx, const uint8_t *d_text, uint64_t t
 	return MCOM_OK;
 }
 
+// the 2 n lines of a mate text, checked: its line index in *mstart (a block of B).  MCOM_E_ARG when the text is not 2 n complete lines of at
+// most 255 bytes each
+static int mate_lines(mcom_ctx *ctx, Blocks &B, const char *who, const uint8_t *d_mate, uint64_t mate_len, uint64_t n, uint64_t **mstart);
+
+extern "C" int mcom_name_encode_mate(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n, const uint8_t *d_mate, uint64_t mate_len, uint8_t *d_out, uint64_t cap,
+                                     uint64_t *out_len, uint64_t *bad_record)
+{
+	if (!ctx) return MCOM_E_ARG;
+	uint64_t ind_len = 0;
+	int rc = mcom_name_encode(ctx, d_text, text_len, n, d_out, cap, &ind_len, bad_record);      // the member without a mate: kept unless kind 2 is strictly smaller
+	if (rc) return rc;
+	*out_len = 0;
+	if (mate_len && !d_mate) return mcom_fail(ctx, MCOM_E_ARG, "name_encode_mate: null pointer");
+	if (mate_len > TEXT_MAX || mate_len < 2 * n || (n == 0 && mate_len)) return mcom_fail(ctx, MCOM_E_ARG, "name_encode_mate: %llu bytes of mate text are not the two lines of each of %llu records", (unsigned long long)mate_len, (unsigned long long)n);
+	if (n == 0) { *out_len = ind_len; return MCOM_OK; }
+	Blocks B(ctx);
+	uint64_t *mstart = nullptr;
+	if ((rc = mate_lines(ctx, B, "name_encode_mate", d_mate, mate_len, n, &mstart))) return rc;
+	NHeader hd; hd.kind = KIND_MATE; hd.rps = 1; hd.n_records = n; hd.text_len = text_len;
+	uint8_t *coded = nullptr; uint64_t at = 0;
+	if ((rc = name_streams(ctx, B, d_text, text_len, n, d_mate, (const uint64_t*)mstart, hd, &coded, &at, bad_record))) return rc;
+	if (NHEADER_BYTES + at < ind_len) {
+		if ((rc = mcom_device_crc32(ctx, d_text, text_len, &hd.crc)) || (rc = mcom_device_crc32(ctx, d_mate, mate_len, &hd.mate_crc))) return rc;
+		uint8_t head[NHEADER_BYTES];
+		write_nheader(head, hd);
+		MCOM_HIP(ctx, hipMemcpyAsync(d_out, head, NHEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+		MCOM_HIP(ctx, hipMemcpyAsync(d_out + NHEADER_BYTES, coded, at, hipMemcpyDeviceToDevice, ctx->stream));
+		MCOM_HIP(ctx, mcom_stream_sync(ctx));
+		ind_len = NHEADER_BYTES + at;
+	}
+	*out_len = ind_len;
+	return MCOM_OK;
+}
+
 // the lines of a name text that came out of an embedded `.rans` member: 2 n of them, complete, none above NM_NAME_MAX; rec_off[r] = start[2 r]
 __global__ __launch_bounds__(NM_THREADS) void k_name_lines(const uint64_t *__restrict__ start, uint64_t n, uint64_t text_len, uint64_t *__restrict__ rec_off, uint32_t *__restrict__ flag)
 {
@@ -350,10 +483,30 @@ __global__ __launch_bounds__(NM_THREADS) void k_name_lines(const uint64_t *__res
 	if (rec_off) rec_off[r] = a;
 }
 
-extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_text, uint64_t cap, uint64_t *text_len, uint64_t *n_records, uint64_t *d_rec_off)
+static int mate_lines(mcom_ctx *ctx, Blocks &B, const char *who, const uint8_t *d_mate, uint64_t mate_len, uint64_t n, uint64_t **mstart)
+{
+	int rc;
+	uint64_t lines = 0; uint32_t *d_flag = nullptr, flag[2] = {0, 0};
+	if ((rc = mcom_decode_line_index(ctx, d_mate, mate_len, nullptr, 0, &lines, nullptr))) return rc;
+	if (lines != 2 * n) return mcom_fail(ctx, MCOM_E_ARG, "%s: the mate text has %llu lines, not the two lines of each of %llu records (flag 0x%x)", who, (unsigned long long)lines, (unsigned long long)n, (uint32_t)NM_F_MATE);
+	MCOM_HIP(ctx, B.get(mstart, (2 * n + 1) * 8));
+	MCOM_HIP(ctx, B.get(&d_flag, 8));
+	MCOM_HIP(ctx, hipMemsetAsync(d_flag, 0, 8, ctx->stream));
+	if ((rc = mcom_decode_line_index(ctx, d_mate, mate_len, *mstart, 2 * n, &lines, d_flag + 1))) return rc;
+	MCOM_LAUNCH(k_name_lines, dim3(blocks_for(n + 1)), dim3(NM_THREADS), 0, ctx->stream, (const uint64_t*)*mstart, n, mate_len, (uint64_t*)nullptr, d_flag);
+	MCOM_LAUNCH_CHECK(ctx);
+	MCOM_HIP(ctx, hipMemcpyAsync(flag, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	if (flag[0] || flag[1]) return mcom_fail(ctx, MCOM_E_ARG, "%s: the mate text is not two complete lines of at most 255 bytes per record (flag 0x%x)", who, (uint32_t)NM_F_MATE);
+	return MCOM_OK;
+}
+
+// with_mate: the caller holds a mate text (mcom_name_decode_mate): kind 2 is taken and decoded against it; kinds 0 and 1 do not look at it
+static int name_decode_impl(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, bool with_mate, const uint8_t *d_mate, uint64_t mate_len, uint8_t *d_text, uint64_t cap, uint64_t *text_len,
+                            uint64_t *n_records, uint64_t *d_rec_off)
 {
 	if (!ctx) return MCOM_E_ARG;
-	if (!text_len || !n_records || (in_len && !d_in)) return mcom_fail(ctx, MCOM_E_ARG, "name_decode: null pointer");
+	if (!text_len || !n_records || (in_len && !d_in) || (with_mate && mate_len && !d_mate)) return mcom_fail(ctx, MCOM_E_ARG, "name_decode: null pointer");
 	*text_len = 0; *n_records = 0;
 	if (in_len < NHEADER_BYTES) return mcom_fail(ctx, MCOM_E_ARG, "name_decode: not a .mcn member (%llu bytes)", (unsigned long long)in_len);
 	Blocks B(ctx);
@@ -362,7 +515,7 @@ extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 	MCOM_HIP(ctx, hipMemcpyAsync(hb, d_in, head_bytes, hipMemcpyDeviceToHost, ctx->stream));
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
 	NHeader hd;
-	if (!read_nheader(hb, in_len, hd)) return mcom_fail(ctx, MCOM_E_ARG, "name_decode: the header does not describe this member");
+	if (!read_nheader(hb, in_len, hd, with_mate)) return mcom_fail(ctx, MCOM_E_ARG, "name_decode: the header does not describe this member");
 	*text_len = hd.text_len; *n_records = hd.n_records;
 	if (hd.text_len > cap) return mcom_fail(ctx, MCOM_E_OVERFLOW, "name_decode: %llu bytes of name text, room for %llu", (unsigned long long)hd.text_len, (unsigned long long)cap);
 	auto refuse = [&](const char *why, uint32_t flag = 0) { *text_len = 0; *n_records = 0; return mcom_fail(ctx, MCOM_E_ARG, "name_decode: %s (flag 0x%x)", why, flag); };
@@ -372,6 +525,14 @@ extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 	uint32_t *d_flag = nullptr, flag = 0;
 	MCOM_HIP(ctx, B.get(&d_flag, 16));
 	MCOM_HIP(ctx, hipMemsetAsync(d_flag, 0, 16, ctx->stream));
+	uint64_t *mstart = nullptr;
+	if (hd.kind == KIND_MATE) {                                            // the mate: the 2 n lines the member was coded against
+		uint32_t mcrc = 0;
+		if (mate_len > TEXT_MAX || mate_len < 2 * n || (n == 0 && mate_len)) return refuse("the mate text is not the two lines of each of the member's records", NM_F_MATE);
+		if (n && (rc = mate_lines(ctx, B, "name_decode", d_mate, mate_len, n, &mstart))) { *text_len = 0; *n_records = 0; return rc; }
+		if (mate_len && (rc = mcom_device_crc32(ctx, d_mate, mate_len, &mcrc))) { *text_len = 0; *n_records = 0; return rc; }
+		if (mcrc != hd.mate_crc) return refuse("the mate text is not the one the member was coded against", NM_F_MATE);
+	}
 	if (n == 0) { if (d_rec_off) MCOM_HIP(ctx, hipMemsetAsync(d_rec_off, 0, 8, ctx->stream)); MCOM_HIP(ctx, mcom_stream_sync(ctx)); return MCOM_OK; }
 	if (hd.kind == KIND_RANS) {
 		uint64_t got = 0, lines = 0;
@@ -456,7 +617,11 @@ extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 	A.plus = plus; A.ptext = ptext; A.n_ptext = raw[S_PTEXT]; A.n_lit = n_lit;
 	A.sa = sa; A.sb = sb; A.st = st; A.sp = sp; A.sl = sl; A.seg_op = seg_op;
 	A.n = n; A.n_seg = n_seg; A.text_len = hd.text_len; A.rps = hd.rps;
-	MCOM_LAUNCH(k_name_walk<0>, dim3(blocks_for(n_seg, NM_WALK_THREADS)), dim3(NM_WALK_THREADS), 0, ctx->stream, A, rec, (uint8_t*)nullptr, d_flag);
+	if (mstart) {
+		MCOM_LAUNCH(k_name_walk_mate<0>, dim3(blocks_for(n)), dim3(NM_THREADS), 0, ctx->stream, A, d_mate, mate_len, (const uint64_t*)mstart, rec, (uint8_t*)nullptr, d_flag);
+	} else {
+		MCOM_LAUNCH(k_name_walk<0>, dim3(blocks_for(n_seg, NM_WALK_THREADS)), dim3(NM_WALK_THREADS), 0, ctx->stream, A, rec, (uint8_t*)nullptr, d_flag);
+	}
 	MCOM_LAUNCH_CHECK(ctx);
 	if ((rc = mcom_scan64(ctx, rec, rec, n + 1, nullptr))) return rc;
 	uint64_t total = 0;
@@ -465,7 +630,11 @@ extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
 	if (flag) return refuse("corrupt member", flag);
 	if (total != hd.text_len) return refuse("the records do not add up to the text");
-	MCOM_LAUNCH(k_name_walk<1>, dim3(blocks_for(n_seg, NM_WALK_THREADS)), dim3(NM_WALK_THREADS), 0, ctx->stream, A, rec, d_text, d_flag);
+	if (mstart) {
+		MCOM_LAUNCH(k_name_walk_mate<1>, dim3(blocks_for(n)), dim3(NM_THREADS), 0, ctx->stream, A, d_mate, mate_len, (const uint64_t*)mstart, rec, d_text, d_flag);
+	} else {
+		MCOM_LAUNCH(k_name_walk<1>, dim3(blocks_for(n_seg, NM_WALK_THREADS)), dim3(NM_WALK_THREADS), 0, ctx->stream, A, rec, d_text, d_flag);
+	}
 	MCOM_LAUNCH_CHECK(ctx);
 	MCOM_HIP(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
@@ -474,6 +643,17 @@ extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 	if ((rc = mcom_device_crc32(ctx, d_text, hd.text_len, &crc))) return rc;
 	if (crc != hd.crc) return refuse("CRC mismatch");
 	return MCOM_OK;
+}
+
+extern "C" int mcom_name_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_text, uint64_t cap, uint64_t *text_len, uint64_t *n_records, uint64_t *d_rec_off)
+{
+	return name_decode_impl(ctx, d_in, in_len, false, nullptr, 0, d_text, cap, text_len, n_records, d_rec_off);
+}
+
+extern "C" int mcom_name_decode_mate(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, const uint8_t *d_mate, uint64_t mate_len, uint8_t *d_text, uint64_t cap, uint64_t *text_len,
+                                     uint64_t *n_records)
+{
+	return name_decode_impl(ctx, d_in, in_len, true, d_mate, mate_len, d_text, cap, text_len, n_records, nullptr);
 }
 
 extern "C" int mcom_name_text_offsets(mcom_ctx *ctx, const uint8_t *d_text, uint64_t text_len, uint64_t n, uint64_t *d_rec_off)

@@ -188,6 +188,9 @@ def load_library():
     L.mcom_name_encode.restype = i32; L.mcom_name_encode.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_name_info.restype = i32; L.mcom_name_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_name_decode.restype = i32; L.mcom_name_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
+    L.mcom_name_encode_mate.restype = i32; L.mcom_name_encode_mate.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_name_info_mate.restype = i32; L.mcom_name_info_mate.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_name_decode_mate.restype = i32; L.mcom_name_decode_mate.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_name_text_offsets.restype = i32; L.mcom_name_text_offsets.argtypes = [vp, vp, u64, u64, vp]
     L.mcom_name_compare.restype = i32; L.mcom_name_compare.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_fastq_name_text.restype = i32; L.mcom_fastq_name_text.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp]
@@ -1120,6 +1123,38 @@ class Context:
         gt, gn = C.c_uint64(), C.c_uint64()
         self._check(self.lib.mcom_name_decode(self._h, self._p(member, torch.uint8), n_in, self._p(out, torch.uint8), int(out.shape[0]), C.byref(gt), C.byref(gn), self._p(off)))
         return out[:t], off
+
+    def name_encode_mate(self, text, n_records: int, mate, out=None):
+        """mcom_name_encode_mate.  text, mate: uint8 device tensors, the name texts of the second and the first
+        file of a pair (n_records records each; both are read up to their last byte and no further).  Returns the `.mcn` member: kind 2,
+        coded against the mate, where that is strictly smaller than name_encode's member, and that member otherwise."""
+        torch = _torch()
+        n, nm = int(text.shape[0]), int(mate.shape[0])
+        cap = int(out.shape[0]) if out is not None else int(self.lib.mcom_name_bound(n))
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        got, bad = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mcom_name_encode_mate(self._h, self._p(text, torch.uint8) if n else None, n, int(n_records), self._p(mate, torch.uint8) if nm else None, nm,
+                                                   self._p(out), cap, C.byref(got), C.byref(bad)))
+        return out[:got.value]
+
+    def name_decode_mate(self, member, mate, out=None):
+        """mcom_name_decode_mate.  member, mate: uint8 device tensors.  Returns the name text as a uint8 device tensor; a kind-2 member is
+        decoded against the mate and refused (McomError) when the mate is not the text it was coded against; kinds 0 and 1 as name_decode.
+        out: a uint8 device tensor to decode into (its length is the room offered)."""
+        torch = _torch()
+        n_in, nm = int(member.shape[0]), int(mate.shape[0])
+        head = bytes(member[:96].cpu().numpy())
+        n, t = C.c_uint64(), C.c_uint64()
+        if self.lib.mcom_name_info_mate(head if head else None, n_in, C.byref(n), C.byref(t)):
+            raise McomError("name_decode_mate: not a .mcn member")
+        t = int(t.value)
+        if out is None:
+            out = torch.empty(max(t, 1), dtype=torch.uint8, device=self.device)
+        gt, gn = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mcom_name_decode_mate(self._h, self._p(member, torch.uint8), n_in, self._p(mate, torch.uint8) if nm else None, nm, self._p(out, torch.uint8),
+                                                   int(out.shape[0]), C.byref(gt), C.byref(gn)))
+        return out[:t]
 
     def name_compare(self, text_a, off_a, text_b, off_b):
         """mcom_name_compare.  Two name texts (uint8 device tensors) with their record offsets (int64 device tensors of n + 1 entries).

@@ -14,6 +14,11 @@
 // decompress --verify-records DIR IN.fastq [IN_2.fastq]: the (read, quality) records -- (read 1, read 2, quality 1, quality 2) for a pair --
 // of such an archive against those of the FASTQ file(s) as multisets on GPU 0; exit status as --verify.
 // --fastq picks DIR/name.mcn up by itself (an archive made with -N): the records then carry the names and '+' texts.
+// decompress --order-pe [--gpu] DIR OUT_1.reads OUT_2.reads: a pair kept in input order (`minicom -1 -2 -p`; DIR holds pe_order.txt): the
+// first file's reads and the second's, each in its input order.  decompress --fastq-order-pe [--gpu] DIR OUT_1.fastq OUT_2.fastq: the same
+// with qual_1.mcq / qual_2.mcq as four-line records, and with name_1.mcn / name_2.mcn the two input files byte for byte.
+// decompress --verify-order-pe DIR IN_1.fastq IN_2.fastq: reads, quality lines and names of such an archive against the two files, each
+// check the members allow, on GPU 0; exit status as --verify (1 before 2 before 0).
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
@@ -120,8 +125,42 @@ static int verify_records(int argc, char **argv)
 	return 2;
 }
 
+static int order_pe(int argc, char **argv, bool fastq)
+{
+	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+	if (gpu) { --argc; ++argv; }
+	if (argc < 4) { fprintf(stderr, "usage: decompress %s [--gpu] DIR OUT_1 OUT_2\n", fastq ? "--fastq-order-pe" : "--order-pe"); return 1; }
+	uint64_t n = 0;
+	const int rc = fastq ? (gpu ? mcomh_decompress_fastq_order_pe_gpu(argv[1], argv[2], argv[3], &n, 0) : mcomh_decompress_fastq_order_pe(argv[1], argv[2], argv[3], &n))
+	                     : (gpu ? mcomh_decompress_order_pe_gpu(argv[1], argv[2], argv[3], &n, 0) : mcomh_decompress_order_pe(argv[1], argv[2], argv[3], &n));
+	if (rc) { fprintf(stderr, "decompress: %s is not a complete, consistent archive of a pair kept in input order%s%s\n", argv[1], fastq ? " with quality values" : "", gpu ? ", or the GPU route is not available" : ""); return 1; }
+	fprintf(stdout, "%llu pairs\n", (unsigned long long)n);
+	return 0;
+}
+
+static int verify_order_pe(int argc, char **argv)
+{
+	if (argc < 4) { fprintf(stderr, "usage: decompress --verify-order-pe DIR IN_1.fastq IN_2.fastq\n"); return 1; }
+	mcomh_verify_report r[5]; int present[5];
+	if (mcomh_verify_order_pe_parts_gpu(argv[1], argv[2], argv[3], 0, r, present)) { fprintf(stderr, "decompress: %s could not be verified against %s and %s\n", argv[1], argv[2], argv[3]); return 1; }
+	static const char *what[5] = {"reads of both files", "quality lines of file 1", "quality lines of file 2", "names and '+' lines of file 1", "names and '+' lines of file 2"};
+	int rc = 0;
+	for (int k = 0; k < 5; ++k) {
+		if (!present[k]) continue;
+		if (r[k].identical) { printf("verified: %llu %s identical\n", (unsigned long long)r[k].n_input, what[k]); continue; }
+		rc = 2;
+		printf("DIFFERENT: %s: the FASTQ holds %llu, the archive %llu\n  %llu differ", what[k], (unsigned long long)r[k].n_input, (unsigned long long)r[k].n_archive, (unsigned long long)r[k].differing);
+		if (r[k].differing) printf(", the first one is %s %llu (from 0)", k >= 3 ? "record" : "line", (unsigned long long)r[k].first_diff);
+		printf("\n");
+	}
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc > 1 && !strcmp(argv[1], "--order-pe")) return order_pe(argc - 1, argv + 1, false);
+	if (argc > 1 && !strcmp(argv[1], "--fastq-order-pe")) return order_pe(argc - 1, argv + 1, true);
+	if (argc > 1 && !strcmp(argv[1], "--verify-order-pe")) return verify_order_pe(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--fastq-reordered")) return fastq_reordered(argc - 1, argv + 1, false);
 	if (argc > 1 && !strcmp(argv[1], "--fastq-pe")) return fastq_reordered(argc - 1, argv + 1, true);
 	if (argc > 1 && !strcmp(argv[1], "--verify-records")) return verify_records(argc - 1, argv + 1);

@@ -15,6 +15,10 @@
 // 3.10), OUT a `.mcn` member; a line above 255 bytes is refused and its record named.  d knows such a member by its magic.
 // mcomz e --fastq-names [--gpu] IN.fastq OUT: the names and '+' texts of a four-line FASTQ file (plain or .gz) -> a `.mcn` member; every
 // record is checked ('@' line, '+' line, at most 255 bytes behind either) and the first bad one is named.  Prints the number of records.
+// mcomz e --names --mate TEXT1 [--gpu] IN OUT, mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT, mcomz d --mate TEXT1 IN OUT:
+// IN is the second file of a pair and the mate the first; the member is coded against the mate's names where that is smaller (kind 2,
+// DESIGN.md section 3.12), and d --mate gives the text back from a `.mcn` member of any kind (exit status 1 for a member of another
+// coder: --mate has no meaning there).  d without --mate refuses a kind-2 member.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstdlib>
@@ -34,19 +38,20 @@ int main(int argc, char **argv)
 {
 	bool gpu = false, bwt = false, names = false, fastq_names = false;
 	int at = 2, qual_L = 0, fastq_L = 0;
-	const char *order_path = nullptr;
+	const char *order_path = nullptr, *mate_path = nullptr;
 	for (; at < argc; ++at) {
 		if (!strcmp(argv[at], "--gpu") && !gpu) gpu = true;
 		else if (!strcmp(argv[at], "--qual") && !qual_L && at + 1 < argc) { qual_L = atoi(argv[++at]); if (qual_L < 1 || qual_L > 256) { fprintf(stderr, "mcomz: --qual takes the row length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--fastq-qual") && !fastq_L && at + 1 < argc) { fastq_L = atoi(argv[++at]); if (fastq_L < 1 || fastq_L > 256) { fprintf(stderr, "mcomz: --fastq-qual takes the read length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--order") && !order_path && at + 1 < argc) order_path = argv[++at];
+		else if (!strcmp(argv[at], "--mate") && !mate_path && at + 1 < argc) mate_path = argv[++at];
 		else if (!strcmp(argv[at], "--bwt") && !bwt) bwt = true;
 		else if (!strcmp(argv[at], "--names") && !names) names = true;
 		else if (!strcmp(argv[at], "--fastq-names") && !fastq_names) fastq_names = true;
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names))) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;
@@ -58,12 +63,14 @@ int main(int argc, char **argv)
 	}
 	if (fastq_names) {
 		char err[320] = ""; uint64_t n = 0;
-		if (mcomh_fastq_name_member(in, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the names"); return 1; }
+		if (mate_path ? mcomh_fastq_name_member_mate(in, mate_path, device, out, &n, err, sizeof err) : mcomh_fastq_name_member(in, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the names"); return 1; }
 		printf("%llu\n", (unsigned long long)n);
 		return 0;
 	}
+	if (mate_path && dec && !has_magic(in, "MCNM")) { fprintf(stderr, "mcomz: --mate goes with a .mcn member; %s is none\n", in); return 1; }
 	if (names || (dec && has_magic(in, "MCNM"))) {
-		rc = enc ? mcomh_name_pack_file(in, out, device) : mcomh_name_unpack_file(in, out, device);
+		if (mate_path) rc = enc ? mcomh_name_pack_file_mate(in, mate_path, out, device) : mcomh_name_unpack_file_mate(in, mate_path, out, device);
+		else rc = enc ? mcomh_name_pack_file(in, out, device) : mcomh_name_unpack_file(in, out, device);
 		if (rc) fprintf(stderr, enc ? "mcomz: cannot pack %s into %s%s\n" : "mcomz: %s is not a complete, intact .mcn member, or %s cannot be written%s\n", in, out, gpu ? " (or the GPU route is not available)" : "");
 		return rc ? 1 : 0;
 	}

@@ -520,3 +520,104 @@ extern "C" int mcomh_decompress_fastq_pe(const char *folder, const char *out_pat
 {
 	try { return decompress_fastq_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
 }
+
+// ---- a pair kept in input order (`minicom -1 -2 -p [-Q [-N]]`) on the host: the 2 n rows of decompress_order_impl,
+// rows [0, n) to the first file and [n, 2 n) to the second.  folder/pe_order.txt (one line, n) must agree with the reads' number.  With
+// quality values: qual_1.mcq and qual_2.mcq, n rows each; with names: name_1.mcn (kind 0 or 1) and name_2.mcn, which is decoded with the
+// decoded name_1 text as its mate.  The cross-check of the _gpu routes: the same bytes, the same archives refused; neither file is left.
+namespace {
+// n_pairs of folder/pe_order.txt, which must be half of n_rows
+bool pair_count(const std::string &dir, uint64_t n_rows, uint64_t &n_pairs)
+{
+	std::vector<uint8_t> t;
+	if (!slurp(dir + "/pe_order.txt", t) || t.empty() || t.size() > 24 || t.back() != '\n') return false;
+	uint64_t v = 0;
+	for (size_t i = 0; i + 1 < t.size(); ++i) { if (t[i] < '0' || t[i] > '9') return false; v = v * 10 + (uint64_t)(t[i] - '0'); }
+	n_pairs = v;
+	return t.size() > 1 && (n_rows & 1) == 0 && v == n_rows / 2;
+}
+struct NameText { std::vector<uint8_t> text; std::vector<uint64_t> at; uint64_t len = 0; };
+bool index_names(NameText &t, uint64_t n)
+{
+	t.at.clear(); t.at.reserve(2 * n + 1); t.at.push_back(0);
+	for (uint64_t i = 0; i < t.len; ++i) if (t.text[i] == '\n') t.at.push_back(i + 1);
+	return t.at.size() == 2 * n + 1;
+}
+// reads: rows of L characters from row `first`; names NULL: records `@<i+1>` with a bare '+'
+bool write_records_named(const char *path, const char *reads, const std::vector<uint8_t> &quals, const NameText *names, uint64_t n, int L)
+{
+	FILE *out = fopen(path, "wb");
+	if (!out) return false;
+	bool ok = true;
+	for (uint64_t i = 0; i < n && ok; ++i) {
+		if (names) {
+			const uint64_t a = names->at[2 * i], b = names->at[2 * i + 1], c = names->at[2 * i + 2];
+			ok = fputc('@', out) != EOF && fwrite(names->text.data() + a, 1, b - a, out) == b - a && fwrite(reads + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+", out) >= 0 &&
+			     fwrite(names->text.data() + b, 1, c - b, out) == c - b;
+		} else
+			ok = fprintf(out, "@%llu\n", (unsigned long long)(i + 1)) > 0 && fwrite(reads + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0;
+		ok = ok && fwrite(quals.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
+	}
+	if (fclose(out) != 0 || !ok) { remove(path); return false; }
+	return true;
+}
+}  // namespace
+
+static int decompress_order_pe_impl(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+{
+	if (!folder || !out_path1 || !out_path2) return -1;
+	std::vector<char> reads; int L = 0; uint64_t n = 0, half = 0;
+	if (decompress_order_impl(folder, nullptr, &n, &reads, &L)) return -1;
+	if (!pair_count(folder, n, half)) return -1;
+	const char *paths[2] = {out_path1, out_path2};
+	for (int k = 0; k < 2; ++k) {
+		FILE *out = fopen(paths[k], "wb");
+		bool ok = out != nullptr;
+		for (uint64_t i = 0; i < half && ok; ++i) ok = fwrite(reads.data() + ((uint64_t)k * half + i) * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
+		if (out && fclose(out) != 0) ok = false;
+		if (!ok) { remove(out_path1); remove(out_path2); return -1; }
+	}
+	if (n_pairs) *n_pairs = half;
+	return 0;
+}
+
+static int decompress_fastq_order_pe_impl(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+{
+	if (!folder || !out_path1 || !out_path2) return -1;
+	const std::string dir(folder);
+	std::vector<char> reads; int L = 0; uint64_t n = 0, half = 0;
+	if (decompress_order_impl(folder, nullptr, &n, &reads, &L)) return -1;
+	if (!pair_count(dir, n, half)) return -1;
+	std::vector<uint8_t> q[2];
+	if (!load_quals(dir + "/qual_1.mcq", half, L, q[0]) || !load_quals(dir + "/qual_2.mcq", half, L, q[1])) return -1;
+	NameText nm[2];
+	std::vector<uint8_t> m1, m2;
+	const bool has1 = slurp(dir + "/name_1.mcn", m1), has2 = slurp(dir + "/name_2.mcn", m2);
+	if (has1 != has2) return -1;                                                        // name_2 is coded against name_1; one alone is no archive
+	if (has1) {
+		uint64_t nn = 0, tl = 0;
+		if (mcomh_name_info(m1.data(), m1.size(), &nn, &tl) || nn != half) return -1;
+		nm[0].text.resize(tl + 1);
+		if (mcomh_name_decode(m1.data(), m1.size(), nm[0].text.data(), tl, &tl, &nn) || nn != half) return -1;
+		nm[0].len = tl;
+		if (mcomh_name_info_mate(m2.data(), m2.size(), &nn, &tl) || nn != half) return -1;
+		nm[1].text.resize(tl + 1);
+		if (mcomh_name_decode_mate(m2.data(), m2.size(), nm[0].text.data(), nm[0].len, nm[1].text.data(), tl, &tl, &nn) || nn != half) return -1;
+		nm[1].len = tl;
+		if (!index_names(nm[0], half) || !index_names(nm[1], half)) return -1;
+	}
+	if (!write_records_named(out_path1, reads.data(), q[0], has1 ? &nm[0] : nullptr, half, L)) return -1;
+	if (!write_records_named(out_path2, reads.data() + half * (size_t)L, q[1], has1 ? &nm[1] : nullptr, half, L)) { remove(out_path1); return -1; }
+	if (n_pairs) *n_pairs = half;
+	return 0;
+}
+
+extern "C" int mcomh_decompress_order_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+{
+	try { return decompress_order_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
+}
+
+extern "C" int mcomh_decompress_fastq_order_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
+{
+	try { return decompress_fastq_order_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
+}

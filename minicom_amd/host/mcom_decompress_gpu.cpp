@@ -399,24 +399,32 @@ uint8_t *load_quals(Arena &A, const char *folder, const char *member_name, const
 // the two page-locked pieces and their device twins that the records travel through: made once per call, also where it writes two files
 struct EmitBufs { uint8_t *pin[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr}; bool made = false; };
 
-// quals_ready: the quality rows (pitch L) when the caller has decoded them already (the `minicom -q` tails: no names there)
-int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out, const uint8_t *quals_ready = nullptr, EmitBufs *shared = nullptr)
+// a name text the caller has decoded already, with its record offsets on the device and on the host (the pair-in-input-order tail)
+struct NamesReady { const uint8_t *d_names; const uint64_t *d_off; uint64_t bytes; const std::vector<uint64_t> *off; };
+
+// quals_ready: the quality rows (pitch L) when the caller has decoded them already (the `minicom -q` tails: no names there, unless the
+// caller hands them in as names_ready)
+int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out, const uint8_t *quals_ready = nullptr, EmitBufs *shared = nullptr,
+                const NamesReady *names_ready = nullptr)
 {
 	const uint8_t *quals = quals_ready ? quals_ready : load_quals(A, folder, "qual.mcq", "-Q", n_rows, L, (uint64_t)L);
 	// folder/name.mcn (`minicom -N`, section 3.10): decoded on the device too; the records then carry its names and '+' texts
 	std::vector<uint8_t> nmember;
-	const bool named = !quals_ready && slurp(std::string(folder) + "/name.mcn", nmember);
-	uint8_t *d_names = nullptr; uint64_t *d_off = nullptr, names_bytes = 0;
-	std::vector<uint64_t> off;                                             // the record offsets of the name text, on the host: pieces are cut by them
-	if (named) {
+	const bool own_names = !quals_ready && !names_ready && slurp(std::string(folder) + "/name.mcn", nmember), named = own_names || names_ready;
+	const uint8_t *d_names = nullptr; const uint64_t *d_off = nullptr; uint64_t names_bytes = 0;
+	std::vector<uint64_t> off_own;                                         // the record offsets of the name text, on the host: pieces are cut by them
+	if (names_ready) { d_names = names_ready->d_names; d_off = names_ready->d_off; names_bytes = names_ready->bytes; }
+	if (own_names) {
 		uint64_t nn = 0;
 		if (mcom_name_info(nmember.data(), nmember.size(), &nn, &names_bytes) || nn != n_rows) throw Refuse{"name.mcn does not state the reads' number"};
 		const uint8_t *d_nm = A.upload(nmember.data(), nmember.size());
-		d_names = A.alloc<uint8_t>(names_bytes); d_off = A.alloc<uint64_t>(n_rows + 1);
-		if (mcom_name_decode(A.ctx, d_nm, nmember.size(), d_names, names_bytes, &names_bytes, &nn, d_off) || nn != n_rows) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"name.mcn is refused"}; }
-		off.resize(n_rows + 1);
-		if (hipMemcpy(off.data(), d_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+		uint8_t *dn = A.alloc<uint8_t>(names_bytes); uint64_t *dof = A.alloc<uint64_t>(n_rows + 1);
+		if (mcom_name_decode(A.ctx, d_nm, nmember.size(), dn, names_bytes, &names_bytes, &nn, dof) || nn != n_rows) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"name.mcn is refused"}; }
+		d_names = dn; d_off = dof;
+		off_own.resize(n_rows + 1);
+		if (hipMemcpy(off_own.data(), d_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
 	}
+	const std::vector<uint64_t> &off = names_ready ? *names_ready->off : off_own;
 	const double t0 = now_ms();
 	const uint64_t rec_max = 2 * (uint64_t)L + 17, per_piece = PIECE_BYTES / rec_max;
 	// where every piece begins: a fixed number of records without names; with names the most records whose bytes fit a piece (bisection
@@ -641,6 +649,92 @@ extern "C" int mcomh_decompress_fastq_pe_gpu(const char *folder, const char *out
 			if (rc) remove(out_path1);
 			return rc;
 		});
+	} catch (...) { return -1; }
+}
+// ---- a pair kept in input order (`minicom -1 -2 -p [-Q [-N]]`): the -p decoder's 2 n rows, [0, n) the first file and
+// [n, 2 n) the second; folder/pe_order.txt must state n.  What the host routes of mcom_decompress.cpp refuse is refused, neither file is left.
+namespace {
+uint64_t pair_count(const char *folder, uint64_t n_rows)
+{
+	std::vector<uint8_t> t;
+	if (!slurp(std::string(folder) + "/pe_order.txt", t) || t.size() < 2 || t.size() > 24 || t.back() != '\n') throw Refuse{"no pe_order.txt: not a pair kept in input order"};
+	uint64_t v = 0;
+	for (size_t i = 0; i + 1 < t.size(); ++i) { if (t[i] < '0' || t[i] > '9') throw Refuse{"pe_order.txt is not a number"}; v = v * 10 + (uint64_t)(t[i] - '0'); }
+	if ((n_rows & 1) || v != n_rows / 2) throw Refuse{"pe_order.txt does not state half the reads' number"};
+	return v;
+}
+// name_1.mcn and name_2.mcn decoded on the device, name_2 against the decoded name_1 text; false: the archive has neither
+struct PairNames { NamesReady r[2]; std::vector<uint64_t> off[2]; };
+bool load_pair_names(Arena &A, const char *folder, uint64_t half, PairNames &P)
+{
+	std::vector<uint8_t> m[2];
+	const bool has1 = slurp(std::string(folder) + "/name_1.mcn", m[0]), has2 = slurp(std::string(folder) + "/name_2.mcn", m[1]);
+	if (has1 != has2) throw Refuse{"one of name_1.mcn and name_2.mcn is missing: name_2 is coded against name_1"};
+	if (!has1) return false;
+	uint8_t *d_text[2]; uint64_t bytes[2] = {0, 0};
+	for (int k = 0; k < 2; ++k) {
+		uint64_t nn = 0;
+		if ((k ? mcom_name_info_mate(m[k].data(), m[k].size(), &nn, &bytes[k]) : mcom_name_info(m[k].data(), m[k].size(), &nn, &bytes[k])) || nn != half) throw Refuse{"a name member does not state the pairs' number"};
+		const uint8_t *d_nm = A.upload(m[k].data(), m[k].size());
+		d_text[k] = A.alloc<uint8_t>(bytes[k]);
+		uint64_t *d_off = A.alloc<uint64_t>(half + 1);
+		const int rc = k ? (mcom_name_decode_mate(A.ctx, d_nm, m[k].size(), d_text[0], bytes[0], d_text[1], bytes[1], &bytes[1], &nn) || mcom_name_text_offsets(A.ctx, d_text[1], bytes[1], half, d_off))
+		                 : mcom_name_decode(A.ctx, d_nm, m[k].size(), d_text[0], bytes[0], &bytes[0], &nn, d_off);
+		if (rc || nn != half) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"a name member is refused"}; }
+		P.off[k].resize(half + 1);
+		if (hipMemcpy(P.off[k].data(), d_off, (half + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+		P.r[k] = NamesReady{d_text[k], d_off, bytes[k], &P.off[k]};
+	}
+	return true;
+}
+}  // namespace
+extern "C" int mcomh_decompress_order_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device)
+{
+	if (!folder || !out_path1 || !out_path2) return -1;
+	try {
+		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			const uint64_t half = pair_count(folder, n_rows);
+			return write_files(PE, A, table, n_rows, half, L, out_path1, out_path2, n_pairs);
+		});
+	} catch (...) { return -1; }
+}
+extern "C" int mcomh_decompress_fastq_order_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device)
+{
+	if (!folder || !out_path1 || !out_path2) return -1;
+	try {
+		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			const uint64_t half = pair_count(folder, n_rows);
+			const uint8_t *q1 = load_quals(A, folder, "qual_1.mcq", "-Q", half, L, (uint64_t)L), *q2 = load_quals(A, folder, "qual_2.mcq", "-Q", half, L, (uint64_t)L);
+			PairNames P;
+			const bool named = load_pair_names(A, folder, half, P);              // (every member is decoded before a file is opened)
+			EmitBufs bufs;
+			if (write_fastq(A, folder, table, half, L, out_path1, n_pairs, q1, &bufs, named ? &P.r[0] : nullptr)) return -1;
+			int rc = -1;
+			try { rc = write_fastq(A, folder, table + half * ((uint64_t)L + 1), half, L, out_path2, n_pairs, q2, &bufs, named ? &P.r[1] : nullptr); } catch (...) { remove(out_path1); throw; }
+			if (rc) remove(out_path1);
+			return rc;
+		});
+	} catch (...) { return -1; }
+}
+// the reads of such an archive against the two FASTQ files, line against line over both files: the report's mode is 1
+extern "C" int mcomh_verify_order_pe_reads_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
+{
+	if (!folder || !fastq1 || !fastq2 || !rep) return -1;
+	memset(rep, 0, sizeof(*rep));
+	try {
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { fprintf(stderr, "minicom verify: no GPU %d (%d visible); there is no host route\n", device, n_dev); return -1; }
+		struct Reads { uint8_t *d = nullptr; ~Reads() { mcomh_device_free(d); } } in;
+		size_t n_in = 0; int L_in = 0;
+		char err[256] = "";
+		if (mcomh_fastq_pair_to_device(fastq1, fastq2, device, &L_in, 0, &in.d, &n_in, err, sizeof(err))) { fprintf(stderr, "minicom verify: cannot read %s and %s: %s\n", fastq1, fastq2, err[0] ? err : "not two FASTQ files of as many reads of one length"); return -1; }
+		const int rr = run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			(void)pair_count(folder, n_rows);
+			return compare_rows(ORDER, A, table, n_rows, 0, L, in.d, (uint64_t)n_in, L_in, rep);
+		});
+		if (rr) return -1;
+		rep->mode = 1;
+		return 0;
 	} catch (...) { return -1; }
 }
 // ---- verification of a `minicom -q` archive: records of (read, quality) or (read 1, read 2, quality 1, quality 2) as multisets ----

@@ -6,6 +6,8 @@
 // is carried in front of the next; on the card mcom_decode_line_index finds the lines and mcom_fastq_name_text checks every record and
 // gathers its two lines.  This is a pass of its own over the file: `minicom -Q -N` reads the file once for qual.mcq and once for name.mcn.
 // mcomh_fastq_name_member: that and mcom_name_encode; device = -1 a host twin of the record rules and mcomh_name_encode.
+// The _mate forms: the same drivers with a second name text, the mate, beside the first -- mcom[h]_name_encode_mate
+// and mcom[h]_name_decode_mate stand where the calls without a mate stood.
 // mcomh_verify_names_gpu: name.mcn decoded on the device against the file's name text, record against record (mcom_name_compare).
 #include "../../include/mcom_host.h"
 #include "../../include/mcom.h"
@@ -36,7 +38,13 @@ bool write_file(const char *path, const uint8_t *p, size_t n)
 	if (fclose(f) || !ok) { remove(path); return false; }
 	return true;
 }
-struct DevBuf { mcom_ctx *ctx = nullptr; uint8_t *a = nullptr, *b = nullptr; ~DevBuf() { if (ctx) (void)mcom_sync(ctx); if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (ctx) mcom_destroy(ctx); } };
+struct DevBuf { mcom_ctx *ctx = nullptr; uint8_t *a = nullptr, *b = nullptr, *m = nullptr; ~DevBuf() { if (ctx) (void)mcom_sync(ctx); for (uint8_t *p : {a, b, m}) if (p) (void)hipFree(p); if (ctx) mcom_destroy(ctx); } };
+// the mate text in a block of exactly its length (the coder reads it up to its last byte and no further)
+bool upload_mate(DevBuf &D, const std::vector<uint8_t> &mate)
+{
+	if (mate.empty()) return true;
+	return hipMalloc((void**)&D.m, mate.size()) == hipSuccess && hipMemcpy(D.m, mate.data(), mate.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
 bool open_device(DevBuf &D, int device, size_t bytes_a, size_t bytes_b)
 {
 	int n_dev = 0;
@@ -206,24 +214,33 @@ int host_names(const char *path, std::vector<uint8_t> &names, size_t &n, char *e
 
 struct DevText { uint8_t *d = nullptr; ~DevText() { mcomh_device_free(d); } };
 
-int fastq_member(const char *fastq, int device, const char *out_path, uint64_t *n_out, char *err, size_t err_cap)
+// mate_fastq != NULL: `fastq` is the second file of a pair and mate_fastq the first; the member is coded against the first file's names
+int fastq_member(const char *fastq, const char *mate_fastq, int device, const char *out_path, uint64_t *n_out, char *err, size_t err_cap)
 {
 	if (!fastq || !out_path) return fail(err, err_cap, "null pointer");
 	std::vector<uint8_t> out;
-	uint64_t len = 0, bad = ~(uint64_t)0; size_t n = 0;
+	uint64_t len = 0, bad = ~(uint64_t)0; size_t n = 0, n_mate = 0;
 	if (device < 0) {
-		std::vector<uint8_t> names;
+		std::vector<uint8_t> names, mate;
 		if (host_names(fastq, names, n, err, err_cap)) return -1;
+		if (mate_fastq && host_names(mate_fastq, mate, n_mate, err, err_cap)) return -1;
+		if (mate_fastq && n_mate != n) return fail(err, err_cap, "%llu records, its mate file has %llu", (unsigned long long)n, (unsigned long long)n_mate);
 		out.resize(mcomh_name_bound(names.size()));
-		if (mcomh_name_encode(names.data(), names.size(), n, out.data(), out.size(), &len, &bad)) return fail(err, err_cap, "the name coder failed (more than 171798691 records, or 4 GiB of names or more?)");
+		if (mate_fastq ? mcomh_name_encode_mate(names.data(), names.size(), n, mate.data(), mate.size(), out.data(), out.size(), &len, &bad)
+		               : mcomh_name_encode(names.data(), names.size(), n, out.data(), out.size(), &len, &bad)) return fail(err, err_cap, "the name coder failed (more than 171798691 records, or 4 GiB of names or more?)");
 	} else {
-		DevText in; uint64_t bytes = 0;
+		DevText in, mate; uint64_t bytes = 0, mate_bytes = 0;
 		if (names_to_device(fastq, device, 0, &in.d, &bytes, &n, err, err_cap)) return -1;
+		if (mate_fastq && names_to_device(mate_fastq, device, 0, &mate.d, &mate_bytes, &n_mate, err, err_cap)) return -1;
+		if (mate_fastq && n_mate != n) return fail(err, err_cap, "%llu records, its mate file has %llu", (unsigned long long)n, (unsigned long long)n_mate);
 		const uint64_t cap = mcomh_name_bound(bytes);
 		struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d_out = nullptr; ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d_out) (void)hipFree(d_out); if (ctx) mcom_destroy(ctx); } } D;
 		if (mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
 		if (hipMalloc((void**)&D.d_out, cap + 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
-		if (mcom_name_encode(D.ctx, in.d, bytes, n, D.d_out, cap, &len, &bad)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
+		if (mate_fastq ? mcom_name_encode_mate(D.ctx, in.d, bytes, n, mate.d, mate_bytes, D.d_out, cap, &len, &bad) : mcom_name_encode(D.ctx, in.d, bytes, n, D.d_out, cap, &len, &bad)) {
+			if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx));
+			return -1;
+		}
 		out.resize(len);
 		if (len && hipMemcpy(out.data(), D.d_out, len, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "download failed");
 	}
@@ -232,12 +249,16 @@ int fastq_member(const char *fastq, int device, const char *out_path, uint64_t *
 	return 0;
 }
 
-int verify_names(const char *folder, const char *fastq, int device, mcomh_verify_report *rep)
+// member: name.mcn, or name_1.mcn / name_2.mcn of a pair.  mate_member != NULL: the member is decoded against the decoded text of that
+// member of the folder (name_2.mcn against name_1.mcn)
+int verify_names(const char *folder, const char *member_name, const char *mate_member, const char *fastq, int device, mcomh_verify_report *rep)
 {
-	std::vector<uint8_t> member;
-	if (!slurp_file((std::string(folder) + "/name.mcn").c_str(), member)) { fprintf(stderr, "minicom verify: %s has no name.mcn\n", folder); return -1; }
-	uint64_t nn = 0, tl = 0;
-	if (mcom_name_info(member.data(), member.size(), &nn, &tl)) { fprintf(stderr, "minicom verify: %s/name.mcn is not a .mcn member\n", folder); return -1; }
+	std::vector<uint8_t> member, mmember;
+	if (!slurp_file((std::string(folder) + "/" + member_name).c_str(), member)) { fprintf(stderr, "minicom verify: %s has no %s\n", folder, member_name); return -1; }
+	if (mate_member && !slurp_file((std::string(folder) + "/" + mate_member).c_str(), mmember)) { fprintf(stderr, "minicom verify: %s has no %s, which %s is coded against\n", folder, mate_member, member_name); return -1; }
+	uint64_t nn = 0, tl = 0, mn = 0, mtl = 0;
+	if (mate_member ? mcom_name_info_mate(member.data(), member.size(), &nn, &tl) : mcom_name_info(member.data(), member.size(), &nn, &tl)) { fprintf(stderr, "minicom verify: %s/%s is not a .mcn member\n", folder, member_name); return -1; }
+	if (mate_member && mcom_name_info(mmember.data(), mmember.size(), &mn, &mtl)) { fprintf(stderr, "minicom verify: %s/%s is not a .mcn member\n", folder, mate_member); return -1; }
 	DevText in; uint64_t in_bytes = 0; size_t n_in = 0;
 	char err[320] = "";
 	if (names_to_device(fastq, device, 0, &in.d, &in_bytes, &n_in, err, sizeof err)) { fprintf(stderr, "minicom verify: cannot read the names of %s: %s\n", fastq, err); return -1; }
@@ -248,7 +269,14 @@ int verify_names(const char *folder, const char *fastq, int device, mcomh_verify
 	uint64_t *d_off = (uint64_t*)D.get((nn + 1) * 8), *d_off_in = (uint64_t*)D.get((n_in + 1) * 8);
 	if (!d_member || !d_text || !d_off || !d_off_in) { fprintf(stderr, "minicom verify: the card has no room for the names\n"); return -1; }
 	if (hipMemcpy(d_member, member.data(), member.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-	if (mcom_name_decode(D.ctx, d_member, member.size(), d_text, tl, &tl, &nn, d_off)) { fprintf(stderr, "minicom verify: %s/name.mcn refused: %s\n", folder, mcom_last_error(D.ctx)); return -1; }
+	if (mate_member) {
+		uint8_t *d_mm = (uint8_t*)D.get(mmember.size()), *d_mate = (uint8_t*)D.get(mtl);
+		if (!d_mm || !d_mate || hipMemcpy(d_mm, mmember.data(), mmember.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+		if (mcom_name_decode(D.ctx, d_mm, mmember.size(), d_mate, mtl, &mtl, &mn, nullptr)) { fprintf(stderr, "minicom verify: %s/%s refused: %s\n", folder, mate_member, mcom_last_error(D.ctx)); return -1; }
+		if (mcom_name_decode_mate(D.ctx, d_member, member.size(), d_mate, mtl, d_text, tl, &tl, &nn) || mcom_name_text_offsets(D.ctx, d_text, tl, nn, d_off)) {
+			fprintf(stderr, "minicom verify: %s/%s refused: %s\n", folder, member_name, mcom_last_error(D.ctx)); return -1;
+		}
+	} else if (mcom_name_decode(D.ctx, d_member, member.size(), d_text, tl, &tl, &nn, d_off)) { fprintf(stderr, "minicom verify: %s/%s refused: %s\n", folder, member_name, mcom_last_error(D.ctx)); return -1; }
 	rep->mode = 1; rep->n_input = n_in; rep->n_archive = nn;
 	rep->missing = n_in > nn ? n_in - nn : 0; rep->extra = nn > n_in ? nn - n_in : 0;
 	const uint64_t common = n_in < nn ? n_in : nn;
@@ -261,11 +289,54 @@ int verify_names(const char *folder, const char *fastq, int device, mcomh_verify
 	return 0;
 }
 
-int name_file(const char *in_path, const char *out_path, int device, bool pack)
+// name_1.mcn against the names of fastq1 and name_2.mcn against those of fastq2 in one context: name_1 is decoded once and serves both
+// as what is compared with the first file and as the mate that name_2 is decoded against
+int verify_names_pair(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep1, mcomh_verify_report *rep2)
+{
+	std::vector<uint8_t> m[2];
+	uint64_t nn[2] = {0, 0}, tl[2] = {0, 0};
+	for (int k = 0; k < 2; ++k) {
+		const char *name = k ? "name_2.mcn" : "name_1.mcn";
+		if (!slurp_file((std::string(folder) + "/" + name).c_str(), m[k])) { fprintf(stderr, "minicom verify: %s has no %s\n", folder, name); return -1; }
+		if (k ? mcom_name_info_mate(m[k].data(), m[k].size(), &nn[k], &tl[k]) : mcom_name_info(m[k].data(), m[k].size(), &nn[k], &tl[k])) { fprintf(stderr, "minicom verify: %s/%s is not a .mcn member\n", folder, name); return -1; }
+	}
+	struct Dev { mcom_ctx *ctx = nullptr; std::vector<void*> v; ~Dev() { if (ctx) (void)mcom_sync(ctx); for (void *p : v) (void)hipFree(p); if (ctx) mcom_destroy(ctx); }
+	             void *get(size_t bytes) { void *p = nullptr; if (hipMalloc(&p, bytes + 16) != hipSuccess) return nullptr; v.push_back(p); return p; } } D;
+	if (mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; return -1; }
+	uint8_t *d_text[2] = {nullptr, nullptr}; uint64_t *d_off[2] = {nullptr, nullptr};
+	const char *fq[2] = {fastq1, fastq2};
+	mcomh_verify_report *rep[2] = {rep1, rep2};
+	for (int k = 0; k < 2; ++k) {
+		uint8_t *d_member = (uint8_t*)D.get(m[k].size());
+		d_text[k] = (uint8_t*)D.get(tl[k]); d_off[k] = (uint64_t*)D.get((nn[k] + 1) * 8);
+		if (!d_member || !d_text[k] || !d_off[k] || hipMemcpy(d_member, m[k].data(), m[k].size(), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "minicom verify: the card has no room for the names\n"); return -1; }
+		const int rc = k ? (mcom_name_decode_mate(D.ctx, d_member, m[1].size(), d_text[0], tl[0], d_text[1], tl[1], &tl[1], &nn[1]) || mcom_name_text_offsets(D.ctx, d_text[1], tl[1], nn[1], d_off[1]))
+		                 : mcom_name_decode(D.ctx, d_member, m[0].size(), d_text[0], tl[0], &tl[0], &nn[0], d_off[0]);
+		if (rc) { fprintf(stderr, "minicom verify: %s/name_%d.mcn refused: %s\n", folder, k + 1, mcom_last_error(D.ctx)); return -1; }
+		DevText in; uint64_t in_bytes = 0; size_t n_in = 0;
+		char err[320] = "";
+		if (names_to_device(fq[k], device, 0, &in.d, &in_bytes, &n_in, err, sizeof err)) { fprintf(stderr, "minicom verify: cannot read the names of %s: %s\n", fq[k], err); return -1; }
+		uint64_t *d_off_in = (uint64_t*)D.get((n_in + 1) * 8);
+		if (!d_off_in) return -1;
+		mcomh_verify_report *r = rep[k];
+		r->mode = 1; r->n_input = n_in; r->n_archive = nn[k];
+		r->missing = n_in > nn[k] ? n_in - nn[k] : 0; r->extra = nn[k] > n_in ? nn[k] - n_in : 0;
+		uint64_t differing = 0, first = ~(uint64_t)0;
+		if (mcom_name_text_offsets(D.ctx, in.d, in_bytes, n_in, d_off_in) ||
+		    mcom_name_compare(D.ctx, in.d, d_off_in, in_bytes, d_text[k], d_off[k], tl[k], n_in < nn[k] ? n_in : nn[k], &differing, &first)) { fprintf(stderr, "minicom verify: %s\n", mcom_last_error(D.ctx)); return -1; }
+		r->differing = differing; r->first_diff = first;
+		r->identical = n_in == nn[k] && differing == 0;
+	}
+	return 0;
+}
+
+// mate_path != NULL: a file of name text, the mate the member is coded against or was coded against
+int name_file(const char *in_path, const char *mate_path, const char *out_path, int device, bool pack)
 {
 	if (!in_path || !out_path) return -1;
-	std::vector<uint8_t> in, out;
+	std::vector<uint8_t> in, out, mate;
 	if (!slurp_file(in_path, in)) return -1;
+	if (mate_path && !slurp_file(mate_path, mate)) return -1;
 	if (pack) {
 		uint64_t lines = 0, len = 0, bad = ~(uint64_t)0;
 		for (uint8_t c : in) lines += c == '\n';
@@ -273,7 +344,7 @@ int name_file(const char *in_path, const char *out_path, int device, bool pack)
 		const uint64_t n = lines / 2, cap = mcomh_name_bound(in.size());
 		out.resize(cap);
 		if (device < 0) {
-			if (mcomh_name_encode(in.data(), in.size(), n, out.data(), cap, &len, &bad)) {
+			if (mate_path ? mcomh_name_encode_mate(in.data(), in.size(), n, mate.data(), mate.size(), out.data(), cap, &len, &bad) : mcomh_name_encode(in.data(), in.size(), n, out.data(), cap, &len, &bad)) {
 				if (bad != ~(uint64_t)0) fprintf(stderr, "mcomz: record %llu has a name or a '+' text above 255 bytes\n", (unsigned long long)bad + 1);
 				return -1;
 			}
@@ -281,20 +352,24 @@ int name_file(const char *in_path, const char *out_path, int device, bool pack)
 			DevBuf D;
 			if (!open_device(D, device, in.size(), cap)) return -1;
 			if (in.size() && hipMemcpy(D.a, in.data(), in.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-			if (mcom_name_encode(D.ctx, D.a, in.size(), n, D.b, cap, &len, &bad)) { fprintf(stderr, "mcomz: %s\n", mcom_last_error(D.ctx)); return -1; }
+			if (!upload_mate(D, mate)) return -1;
+			if (mate_path ? mcom_name_encode_mate(D.ctx, D.a, in.size(), n, D.m, mate.size(), D.b, cap, &len, &bad) : mcom_name_encode(D.ctx, D.a, in.size(), n, D.b, cap, &len, &bad)) { fprintf(stderr, "mcomz: %s\n", mcom_last_error(D.ctx)); return -1; }
 			if (hipMemcpy(out.data(), D.b, len, hipMemcpyDeviceToHost) != hipSuccess) return -1;
 		}
 		return write_file(out_path, out.data(), len) ? 0 : -1;
 	}
 	uint64_t n = 0, text_len = 0, gn = 0, gt = 0;
-	if (mcomh_name_info(in.data(), in.size(), &n, &text_len)) return -1;
+	if (mate_path ? mcomh_name_info_mate(in.data(), in.size(), &n, &text_len) : mcomh_name_info(in.data(), in.size(), &n, &text_len)) return -1;
 	out.resize(text_len + 1);
-	if (device < 0) { if (mcomh_name_decode(in.data(), in.size(), out.data(), text_len, &gt, &gn)) return -1; }
+	if (device < 0) {
+		if (mate_path ? mcomh_name_decode_mate(in.data(), in.size(), mate.data(), mate.size(), out.data(), text_len, &gt, &gn) : mcomh_name_decode(in.data(), in.size(), out.data(), text_len, &gt, &gn)) return -1;
+	}
 	else {
 		DevBuf D;
 		if (!open_device(D, device, in.size(), text_len)) return -1;
 		if (hipMemcpy(D.a, in.data(), in.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-		if (mcom_name_decode(D.ctx, D.a, in.size(), D.b, text_len, &gt, &gn, nullptr)) { fprintf(stderr, "mcomz: %s\n", mcom_last_error(D.ctx)); return -1; }
+		if (!upload_mate(D, mate)) return -1;
+		if (mate_path ? mcom_name_decode_mate(D.ctx, D.a, in.size(), D.m, mate.size(), D.b, text_len, &gt, &gn) : mcom_name_decode(D.ctx, D.a, in.size(), D.b, text_len, &gt, &gn, nullptr)) { fprintf(stderr, "mcomz: %s\n", mcom_last_error(D.ctx)); return -1; }
 		if (text_len && hipMemcpy(out.data(), D.b, text_len, hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	}
 	return write_file(out_path, out.data(), text_len) ? 0 : -1;
@@ -302,8 +377,18 @@ int name_file(const char *in_path, const char *out_path, int device, bool pack)
 
 }  // namespace
 
-extern "C" int mcomh_name_pack_file(const char *in_path, const char *out_path, int device) { try { return name_file(in_path, out_path, device, true); } catch (...) { return -1; } }
-extern "C" int mcomh_name_unpack_file(const char *in_path, const char *out_path, int device) { try { return name_file(in_path, out_path, device, false); } catch (...) { return -1; } }
+extern "C" int mcomh_name_pack_file(const char *in_path, const char *out_path, int device) { try { return name_file(in_path, nullptr, out_path, device, true); } catch (...) { return -1; } }
+extern "C" int mcomh_name_unpack_file(const char *in_path, const char *out_path, int device) { try { return name_file(in_path, nullptr, out_path, device, false); } catch (...) { return -1; } }
+extern "C" int mcomh_name_pack_file_mate(const char *in_path, const char *mate_path, const char *out_path, int device)
+{
+	if (!mate_path) return -1;
+	try { return name_file(in_path, mate_path, out_path, device, true); } catch (...) { return -1; }
+}
+extern "C" int mcomh_name_unpack_file_mate(const char *in_path, const char *mate_path, const char *out_path, int device)
+{
+	if (!mate_path) return -1;
+	try { return name_file(in_path, mate_path, out_path, device, false); } catch (...) { return -1; }
+}
 
 extern "C" int mcomh_fastq_names_to_device(const char *path, int device, size_t piece_bytes, uint8_t **d_names, uint64_t *bytes, size_t *n, char *err, size_t err_cap)
 {
@@ -313,14 +398,52 @@ extern "C" int mcomh_fastq_names_to_device(const char *path, int device, size_t 
 extern "C" int mcomh_fastq_name_member(const char *fastq, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap)
 {
 	if (err && err_cap) err[0] = 0;
-	try { return fastq_member(fastq, device, out_path, n, err, err_cap); } catch (...) { return -1; }
+	try { return fastq_member(fastq, nullptr, device, out_path, n, err, err_cap); } catch (...) { return -1; }
 }
-extern "C" int mcomh_verify_names_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep)
+extern "C" int mcomh_fastq_name_member_mate(const char *fastq2, const char *fastq1, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap)
 {
-	if (!folder || !fastq || !rep) { fprintf(stderr, "minicom verify: bad arguments (a folder with name.mcn and one FASTQ file)\n"); return -1; }
+	if (err && err_cap) err[0] = 0;
+	if (!fastq1) return fail(err, err_cap, "null pointer");
+	try { return fastq_member(fastq2, fastq1, device, out_path, n, err, err_cap); } catch (...) { return -1; }
+}
+extern "C" int mcomh_verify_names_member_gpu(const char *folder, const char *member, const char *mate_member, const char *fastq, int device, mcomh_verify_report *rep)
+{
+	if (!folder || !member || !fastq || !rep) { fprintf(stderr, "minicom verify: bad arguments (a folder with name.mcn and one FASTQ file)\n"); return -1; }
 	memset(rep, 0, sizeof(*rep));
 	rep->first_diff = ~(uint64_t)0;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { fprintf(stderr, "minicom verify: no GPU %d (%d visible); there is no host route\n", device, n_dev); return -1; }
-	try { return verify_names(folder, fastq, device, rep); } catch (...) { return -1; }
+	try { return verify_names(folder, member, mate_member, fastq, device, rep); } catch (...) { return -1; }
+}
+extern "C" int mcomh_verify_names_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep) { return mcomh_verify_names_member_gpu(folder, "name.mcn", nullptr, fastq, device, rep); }
+
+// ---- a pair kept in input order: every check the archive's members allow, file by file ----
+// part 0 the reads, line against line over both files; 1 / 2 the quality lines of file 1 / 2; 3 / 4 the names and '+' lines of file 1 / 2.
+// present[k] says whether check k was made (the archive holds its members).  -1 when a check could not be made, or when the archive
+// holds one quality member of two, name_2 without name_1 (or the reverse), or names without quality values.
+extern "C" int mcomh_verify_order_pe_parts_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report rep[5], int present[5])
+{
+	if (!folder || !fastq1 || !fastq2 || !rep || !present) { fprintf(stderr, "minicom verify: bad arguments (a folder and the two FASTQ files)\n"); return -1; }
+	auto has = [&](const char *name) { FILE *f = fopen((std::string(folder) + "/" + name).c_str(), "rb"); if (f) fclose(f); return f != nullptr; };
+	const bool q1 = has("qual_1.mcq"), q2 = has("qual_2.mcq"), n1 = has("name_1.mcn"), n2 = has("name_2.mcn");
+	if (q1 != q2 || n1 != n2 || (n1 && !q1)) { fprintf(stderr, "minicom verify: %s holds one member of a pair of members without the other, or names without quality values\n", folder); return -1; }
+	for (int k = 0; k < 5; ++k) { memset(&rep[k], 0, sizeof rep[k]); present[k] = 0; }
+	present[0] = 1; present[1] = present[2] = q1; present[3] = present[4] = n1;
+	int rc = mcomh_verify_order_pe_reads_gpu(folder, fastq1, fastq2, device, &rep[0]);
+	if (q1) rc |= mcomh_verify_quality_member_gpu(folder, "qual_1.mcq", fastq1, device, &rep[1]) | mcomh_verify_quality_member_gpu(folder, "qual_2.mcq", fastq2, device, &rep[2]);
+	if (n1) {
+		rep[3].first_diff = rep[4].first_diff = ~(uint64_t)0;
+		try { rc |= verify_names_pair(folder, fastq1, fastq2, device, &rep[3], &rep[4]); } catch (...) { rc = -1; }
+	}
+	return rc ? -1 : 0;
+}
+// the same as one verdict: identical when every check made says so; the counts are the reads', `differing` is summed over the checks
+extern "C" int mcomh_verify_order_pe_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
+{
+	if (!rep) return -1;
+	mcomh_verify_report part[5]; int present[5];
+	if (mcomh_verify_order_pe_parts_gpu(folder, fastq1, fastq2, device, part, present)) return -1;
+	*rep = part[0];
+	for (int k = 1; k < 5; ++k) if (present[k]) { rep->identical = rep->identical && part[k].identical; rep->differing += part[k].differing; }
+	return 0;
 }

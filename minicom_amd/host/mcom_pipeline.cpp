@@ -2917,3 +2917,17 @@ extern "C" int mcomh_keep_read_order(mcomh_pipeline *p, int on)
 }
 // paired end (minicompe = the reference compiled with _PE): reads [0, n/2) come from the first file, read n/2 + i is the mate of read i
 extern "C" int mcomh_cluster_dump_pe(mcomh_pipeline *p, const char *folder) { return cluster_dump_impl(p, folder, 2); }
+// a pair kept in input order: the order-preserving dump of the 2 n rows -- the second file's reads stand behind the
+// first's -- and FOLDER/pe_order.txt, one line `<n_pairs>`, which tells the decoders that rows [0, n) are file 1 and [n, 2 n) file 2
+extern "C" int mcomh_cluster_dump_order_pe(mcomh_pipeline *p, const char *folder)
+{
+	if (!p || !folder) return MCOM_E_ARG;
+	if (p->n & 1) return p->fail(MCOM_E_ARG, "paired-end mode needs as many reads in the second file as in the first");
+	const int rc = mcomh_cluster_dump_order(p, folder);
+	if (rc) return rc;
+	FILE *f = fopen((std::string(folder) + "/pe_order.txt").c_str(), "w");
+	if (!f) return p->fail(MCOM_E_ARG, "cannot write into %s", folder);
+	const bool ok = fprintf(f, "%llu\n", (unsigned long long)(p->n / 2)) > 0;
+	if (fclose(f) != 0 || !ok) return p->fail(MCOM_E_ARG, "cannot write into %s", folder);
+	return MCOM_OK;
+}

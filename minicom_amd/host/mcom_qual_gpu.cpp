@@ -152,19 +152,20 @@ int qualities(const char *path, int device, int L, size_t piece_bytes, uint8_t *
 	return 0;
 }
 
-int verify_quality(const char *folder, const char *fastq, int device, mcomh_verify_report *rep)
+// member: the `.mcq` member of the folder that holds the file's quality rows in input order (qual.mcq; qual_1.mcq / qual_2.mcq of a pair)
+int verify_quality(const char *folder, const char *member_name, const char *fastq, int device, mcomh_verify_report *rep)
 {
 	const double t_begin = now_ms();
 	std::vector<uint8_t> member;
 	{
-		FILE *f = fopen((std::string(folder) + "/qual.mcq").c_str(), "rb");
-		if (!f) { fprintf(stderr, "minicom verify: %s has no qual.mcq\n", folder); return -1; }
+		FILE *f = fopen((std::string(folder) + "/" + member_name).c_str(), "rb");
+		if (!f) { fprintf(stderr, "minicom verify: %s has no %s\n", folder, member_name); return -1; }
 		uint8_t buf[65536]; size_t got;
 		while ((got = fread(buf, 1, sizeof buf, f)) > 0) member.insert(member.end(), buf, buf + got);
 		fclose(f);
 	}
 	uint64_t qn = 0; uint32_t qL = 0;
-	if (mcom_qual_info(member.data(), member.size(), &qn, &qL)) { fprintf(stderr, "minicom verify: %s/qual.mcq is not a .mcq member\n", folder); return -1; }
+	if (mcom_qual_info(member.data(), member.size(), &qn, &qL)) { fprintf(stderr, "minicom verify: %s/%s is not a .mcq member\n", folder, member_name); return -1; }
 	struct Rows { uint8_t *d = nullptr; ~Rows() { mcomh_device_free(d); } } in;
 	size_t n_in = 0;
 	char err[320] = "";
@@ -176,7 +177,7 @@ int verify_quality(const char *folder, const char *fastq, int device, mcomh_veri
 	if (hipMemcpy(D.d_member, member.data(), member.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
 	double t0 = now_ms();
 	uint64_t gn = 0; uint32_t gL = 0;
-	if (mcom_qual_decode(D.ctx, D.d_member, member.size(), D.d_rows, qL, qn, &gn, &gL)) { fprintf(stderr, "minicom verify: %s/qual.mcq refused: %s\n", folder, mcom_last_error(D.ctx)); return -1; }
+	if (mcom_qual_decode(D.ctx, D.d_member, member.size(), D.d_rows, qL, qn, &gn, &gL)) { fprintf(stderr, "minicom verify: %s/%s refused: %s\n", folder, member_name, mcom_last_error(D.ctx)); return -1; }
 	rep->times_ms[2] = now_ms() - t0;
 	mcom_verify_table a, b;
 	a.d_rows = in.d; a.pitch = qL; a.n = n_in; a.d_mates = nullptr;
@@ -409,12 +410,13 @@ extern "C" int mcomh_fastq_qualities_to_device(const char *path, int device, int
 	try { return qualities(path, device, L, piece_bytes, d_rows, n, err, err_cap); } catch (...) { return -1; }
 }
 
-extern "C" int mcomh_verify_quality_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep)
+extern "C" int mcomh_verify_quality_member_gpu(const char *folder, const char *member, const char *fastq, int device, mcomh_verify_report *rep)
 {
-	if (!folder || !fastq || !rep) { fprintf(stderr, "minicom verify: bad arguments (a folder with qual.mcq and one FASTQ file)\n"); return -1; }
+	if (!folder || !member || !fastq || !rep) { fprintf(stderr, "minicom verify: bad arguments (a folder with qual.mcq and one FASTQ file)\n"); return -1; }
 	memset(rep, 0, sizeof(*rep));
 	rep->first_diff = ~(uint64_t)0;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { fprintf(stderr, "minicom verify: no GPU %d (%d visible); there is no host route\n", device, n_dev); return -1; }
-	try { return verify_quality(folder, fastq, device, rep); } catch (...) { return -1; }
+	try { return verify_quality(folder, member, fastq, device, rep); } catch (...) { return -1; }
 }
+extern "C" int mcomh_verify_quality_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep) { return mcomh_verify_quality_member_gpu(folder, "qual.mcq", fastq, device, rep); }

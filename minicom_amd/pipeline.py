@@ -129,6 +129,21 @@ def load_host_library():
     L.mcomh_verify_names_gpu.restype = i32; L.mcomh_verify_names_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport)]
     L.mcomh_name_pack_file.restype = i32; L.mcomh_name_pack_file.argtypes = [cp, cp, i32]
     L.mcomh_name_unpack_file.restype = i32; L.mcomh_name_unpack_file.argtypes = [cp, cp, i32]
+    L.mcomh_name_info_mate.restype = i32; L.mcomh_name_info_mate.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_name_encode_mate.restype = i32; L.mcomh_name_encode_mate.argtypes = [vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_name_decode_mate.restype = i32; L.mcomh_name_decode_mate.argtypes = [vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_name_pack_file_mate.restype = i32; L.mcomh_name_pack_file_mate.argtypes = [cp, cp, cp, i32]
+    L.mcomh_name_unpack_file_mate.restype = i32; L.mcomh_name_unpack_file_mate.argtypes = [cp, cp, cp, i32]
+    L.mcomh_cluster_dump_order_pe.restype = i32; L.mcomh_cluster_dump_order_pe.argtypes = [vp, cp]
+    for f in ("mcomh_decompress_order_pe", "mcomh_decompress_fastq_order_pe"):
+        getattr(L, f).restype = i32; getattr(L, f).argtypes = [cp, cp, cp, C.POINTER(u64)]
+        getattr(L, f + "_gpu").restype = i32; getattr(L, f + "_gpu").argtypes = [cp, cp, cp, C.POINTER(u64), i32]
+    L.mcomh_verify_order_pe_reads_gpu.restype = i32; L.mcomh_verify_order_pe_reads_gpu.argtypes = [cp, cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_verify_order_pe_gpu.restype = i32; L.mcomh_verify_order_pe_gpu.argtypes = [cp, cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_verify_order_pe_parts_gpu.restype = i32; L.mcomh_verify_order_pe_parts_gpu.argtypes = [cp, cp, cp, i32, C.POINTER(VerifyReport), C.POINTER(i32)]
+    L.mcomh_verify_quality_member_gpu.restype = i32; L.mcomh_verify_quality_member_gpu.argtypes = [cp, cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_verify_names_member_gpu.restype = i32; L.mcomh_verify_names_member_gpu.argtypes = [cp, cp, cp, cp, i32, C.POINTER(VerifyReport)]
+    L.mcomh_fastq_name_member_mate.restype = i32; L.mcomh_fastq_name_member_mate.argtypes = [cp, cp, i32, cp, C.POINTER(u64), C.c_char_p, sz]
     _lib = L
     return L
 
@@ -157,6 +172,13 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     # read names and '+' lines (host/mcom_names.cpp)
                     "mcomh_name_bound", "mcomh_name_info", "mcomh_name_encode", "mcomh_name_decode", "mcomh_name_pack_file",
                     "mcomh_name_unpack_file", "mcomh_fastq_names_to_device", "mcomh_fastq_name_member", "mcomh_verify_names_gpu",
+                    # names coded against a mate file's names (section 3.12)
+                    "mcomh_name_info_mate", "mcomh_name_encode_mate", "mcomh_name_decode_mate", "mcomh_name_pack_file_mate",
+                    "mcomh_name_unpack_file_mate", "mcomh_fastq_name_member_mate",
+                    # a pair kept in input order (section 3.12)
+                    "mcomh_cluster_dump_order_pe", "mcomh_decompress_order_pe", "mcomh_decompress_order_pe_gpu", "mcomh_decompress_fastq_order_pe",
+                    "mcomh_decompress_fastq_order_pe_gpu", "mcomh_verify_order_pe_reads_gpu", "mcomh_verify_order_pe_parts_gpu", "mcomh_verify_order_pe_gpu",
+                    "mcomh_verify_quality_member_gpu", "mcomh_verify_names_member_gpu",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -365,6 +387,38 @@ def decompress_fastq_pe(folder: str, out_path1: str, out_path2: str, device: int
     return int(n.value)
 
 
+def decompress_order_pe(folder: str, out_path1: str, out_path2: str, device: int | None = None, fastq: bool = False) -> int:
+    """mcomh_decompress_order_pe(_gpu), with fastq=True mcomh_decompress_fastq_order_pe(_gpu): the stream files of a pair kept in input order
+    (`minicom -1 -2 -p [-Q [-N]]`) -> the two files in input order: reads one per line, or four-line records (with
+    name_1.mcn and name_2.mcn the two input files byte for byte).  Returns the number of pairs."""
+    n = C.c_uint64()
+    lib = load_host_library()
+    name = "mcomh_decompress_fastq_order_pe" if fastq else "mcomh_decompress_order_pe"
+    args = (os.fsencode(folder), os.fsencode(out_path1), os.fsencode(out_path2), C.byref(n))
+    rc = getattr(lib, name)(*args) if device is None else getattr(lib, name + "_gpu")(*args, int(device))
+    if rc:
+        raise McomError(f"cannot decode {folder} to two files in input order" + ("" if device is None else f" on GPU {device}") + ": not a complete, consistent archive of a pair kept in input order")
+    return int(n.value)
+
+
+def verify_order_pe(folder: str, fastq1: str, fastq2: str, device: int = 0) -> dict:
+    """mcomh_verify_order_pe_parts_gpu: a pair kept in input order against its two FASTQ files on GPU `device` -- the reads line against
+    line over both files, and per file the quality lines and the names and `+` lines where the archive holds their members.  "identical" is
+    true when every check made says so; "reads", "quality_1", "quality_2", "names_1", "names_2" are the checks made.  McomError when a
+    check could not be made or the archive holds one member of two."""
+    reps = (VerifyReport * 5)(); present = (C.c_int32 * 5)()
+    if load_host_library().mcomh_verify_order_pe_parts_gpu(os.fsencode(folder), os.fsencode(fastq1), os.fsencode(fastq2), int(device), reps, present):
+        raise McomError(f"cannot verify {folder} against {fastq1} and {fastq2} on GPU {device}")
+    out = {"identical": True}
+    for k, tag in enumerate(("reads", "quality_1", "quality_2", "names_1", "names_2")):
+        if present[k]:
+            r = reps[k]
+            out[tag] = {"identical": bool(r.identical), "n_input": int(r.n_input), "n_archive": int(r.n_archive), "differing": int(r.differing),
+                        "first_diff": None if r.first_diff == 2 ** 64 - 1 or not r.differing else int(r.first_diff)}
+            out["identical"] = out["identical"] and out[tag]["identical"]
+    return out
+
+
 def verify_records(folder: str, fastq: str, fastq2: str | None = None, device: int = 0) -> dict:
     """mcomh_verify_records_gpu: does a `minicom -q` archive give back exactly the (read, quality) records of `fastq` -- with fastq2 the
     (read 1, read 2, quality 1, quality 2) pairs -- as a multiset, duplicates counted?  Decided on GPU `device`, nothing is written.
@@ -465,62 +519,93 @@ def name_text(names, plus=None) -> bytes:
     return b"".join(bytes(a) + b"\n" + bytes(b) + b"\n" for a, b in zip(names, plus))
 
 
-def name_encode(text: bytes, n_records: int | None = None, device: int | None = None) -> bytes:
+def name_encode(text: bytes, n_records: int | None = None, device: int | None = None, mate: bytes | None = None) -> bytes:
     """A name text (name_text) -> a `.mcn` member.  device None: mcomh_name_encode, the host twin; an integer: mcom_name_encode on that
     GPU (the same bytes; an error, never the host twin, when there is none).  n_records None: half the number of lines.  McomError
-    for a text that is not two complete lines per record; for a line above 255 bytes it names the record."""
+    for a text that is not two complete lines per record; for a line above 255 bytes it names the record.
+    mate: the name text of the mate file, record for record: mcom[h]_name_encode_mate -- the member is coded
+    against it (kind 2) where that is strictly smaller, and is the member without a mate otherwise; McomError for a mate that is not two
+    lines for each of the text's records."""
     text = bytes(text)
     n = text.count(b"\n") // 2 if n_records is None else int(n_records)
     if device is not None:
         import torch
         ctx = _device_context(device)
         dev = f"cuda:{int(device)}"
-        raw = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(dev) if text else torch.empty(0, dtype=torch.uint8, device=dev)
-        return ctx.name_encode(raw, n).cpu().numpy().tobytes()
+        up = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) if b else torch.empty(0, dtype=torch.uint8, device=dev)
+        got = ctx.name_encode(up(text), n) if mate is None else ctx.name_encode_mate(up(text), n, up(bytes(mate)))
+        return got.cpu().numpy().tobytes()
     lib = load_host_library()
     cap = int(lib.mcomh_name_bound(len(text)))
     out = C.create_string_buffer(cap)
     got, bad = C.c_uint64(), C.c_uint64()
-    rc = lib.mcomh_name_encode((C.c_char * len(text)).from_buffer_copy(text) if text else None, len(text), n, out, cap, C.byref(got), C.byref(bad))
+    buf = (C.c_char * len(text)).from_buffer_copy(text) if text else None
+    if mate is None:
+        rc = lib.mcomh_name_encode(buf, len(text), n, out, cap, C.byref(got), C.byref(bad))
+    else:
+        mate = bytes(mate)
+        rc = lib.mcomh_name_encode_mate(buf, len(text), n, (C.c_char * len(mate)).from_buffer_copy(mate) if mate else None, len(mate), out, cap, C.byref(got), C.byref(bad))
     if rc:
         if bad.value != 0xFFFFFFFFFFFFFFFF:
             raise McomError(f"name_encode: record {bad.value + 1} has a name or a '+' text above 255 bytes")
-        raise McomError(f"name_encode: error {rc}: not the two lines of each of {n} records")
+        raise McomError(f"name_encode: error {rc}: not the two lines of each of {n} records" + ("" if mate is None else ", in the text or in its mate"))
     return out.raw[:got.value]
 
 
-def name_info(member: bytes) -> tuple[int, int]:
-    """mcomh_name_info: (n_records, text_len) a `.mcn` member's header states; McomError when the first 96 bytes are not such a header"""
+def name_info(member: bytes, mate: bool = False) -> tuple[int, int]:
+    """mcomh_name_info: (n_records, text_len) a `.mcn` member's header states; McomError when the first 96 bytes are not such a header.
+    mate=True: mcomh_name_info_mate, for which a kind-2 header (section 3.12) is one too."""
     n, t = C.c_uint64(), C.c_uint64()
     head = bytes(member[:96])
-    if load_host_library().mcomh_name_info((C.c_char * len(head)).from_buffer_copy(head) if head else None, len(member), C.byref(n), C.byref(t)):
+    lib = load_host_library()
+    if (lib.mcomh_name_info_mate if mate else lib.mcomh_name_info)((C.c_char * len(head)).from_buffer_copy(head) if head else None, len(member), C.byref(n), C.byref(t)):
         raise McomError("name_info: not a .mcn member")
     return int(n.value), int(t.value)
 
 
-def name_decode(member: bytes, device: int | None = None) -> bytes:
-    """A `.mcn` member -> the name text, on the host twin or on that GPU; McomError for every member section 3.10 refuses."""
+def name_decode(member: bytes, device: int | None = None, mate: bytes | None = None) -> bytes:
+    """A `.mcn` member -> the name text, on the host twin or on that GPU; McomError for every member section 3.10 refuses.
+    mate: the mate file's name text (mcom[h]_name_decode_mate): a kind-2 member is decoded against it and refused when it is not the
+    text the member was coded against; kinds 0 and 1 decode as without it.  Without mate a kind-2 member is refused."""
     member = bytes(member)
-    n, t = name_info(member)
+    n, t = name_info(member, mate is not None)
     if device is not None:
         import torch
         ctx = _device_context(device)
-        text, _ = ctx.name_decode(torch.frombuffer(bytearray(member), dtype=torch.uint8).to(f"cuda:{int(device)}"))
+        dev = f"cuda:{int(device)}"
+        d_member = torch.frombuffer(bytearray(member), dtype=torch.uint8).to(dev)
+        if mate is None:
+            text, _ = ctx.name_decode(d_member)
+        else:
+            mate = bytes(mate)
+            text = ctx.name_decode_mate(d_member, torch.frombuffer(bytearray(mate), dtype=torch.uint8).to(dev) if mate else torch.empty(0, dtype=torch.uint8, device=dev))
         return text.cpu().numpy().tobytes()
     out = C.create_string_buffer(max(t, 1))
     gt, gn = C.c_uint64(), C.c_uint64()
-    rc = load_host_library().mcomh_name_decode((C.c_char * len(member)).from_buffer_copy(member), len(member), out, t, C.byref(gt), C.byref(gn))
+    buf = (C.c_char * len(member)).from_buffer_copy(member)
+    if mate is None:
+        rc = load_host_library().mcomh_name_decode(buf, len(member), out, t, C.byref(gt), C.byref(gn))
+    else:
+        mate = bytes(mate)
+        rc = load_host_library().mcomh_name_decode_mate(buf, len(member), (C.c_char * len(mate)).from_buffer_copy(mate) if mate else None, len(mate), out, t, C.byref(gt), C.byref(gn))
     if rc:
-        raise McomError(f"name_decode: error {rc}: not a complete, intact .mcn member")
+        raise McomError(f"name_decode: error {rc}: not a complete, intact .mcn member" + ("" if mate is None else " of this mate"))
     return out.raw[:t]
 
 
-def fastq_name_member(fastq: str, out_path: str, device: int | None = None) -> int:
+def fastq_name_member(fastq: str, out_path: str, device: int | None = None, mate_path: str | None = None) -> int:
     """mcomh_fastq_name_member: the names and `+` texts of a four-line FASTQ file -> the `.mcn` member file out_path; returns the number
     of records.  device None: the host twin of the record rules and of the coder; an integer: that GPU (an error when there is none).
-    McomError names the first record that has no `@` or `+` line or more than 255 bytes behind either; no file is left then."""
+    McomError names the first record that has no `@` or `+` line or more than 255 bytes behind either; no file is left then.
+    mate_path: `fastq` is the second file of a pair and mate_path the first (mcomh_fastq_name_member_mate): the member is coded against
+    the first file's names where that is smaller; McomError when the two files differ in records."""
     n = C.c_uint64(); err = C.create_string_buffer(320)
-    if load_host_library().mcomh_fastq_name_member(os.fsencode(fastq), -1 if device is None else int(device), os.fsencode(out_path), C.byref(n), err, 320):
+    lib, dev = load_host_library(), -1 if device is None else int(device)
+    if mate_path is None:
+        rc = lib.mcomh_fastq_name_member(os.fsencode(fastq), dev, os.fsencode(out_path), C.byref(n), err, 320)
+    else:
+        rc = lib.mcomh_fastq_name_member_mate(os.fsencode(fastq), os.fsencode(mate_path), dev, os.fsencode(out_path), C.byref(n), err, 320)
+    if rc:
         raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the names'}")
     return int(n.value)
 
@@ -553,11 +638,16 @@ def verify_names(folder: str, fastq: str, device: int = 0) -> dict:
             "first_diff": None if r.first_diff == 2 ** 64 - 1 else int(r.first_diff)}
 
 
-def name_file(in_path: str, out_path: str, pack: bool, device: int | None = None) -> None:
-    """mcomh_name_pack_file / _unpack_file: a file of name text -> a `.mcn` member file or back; device None: the host twin."""
+def name_file(in_path: str, out_path: str, pack: bool, device: int | None = None, mate_path: str | None = None) -> None:
+    """mcomh_name_pack_file / _unpack_file: a file of name text -> a `.mcn` member file or back; device None: the host twin.
+    mate_path: a file holding the mate's name text (mcomh_name_pack_file_mate / _unpack_file_mate)."""
     lib = load_host_library()
-    fn = lib.mcomh_name_pack_file if pack else lib.mcomh_name_unpack_file
-    if fn(os.fsencode(in_path), os.fsencode(out_path), -1 if device is None else int(device)):
+    dev = -1 if device is None else int(device)
+    if mate_path is None:
+        rc = (lib.mcomh_name_pack_file if pack else lib.mcomh_name_unpack_file)(os.fsencode(in_path), os.fsencode(out_path), dev)
+    else:
+        rc = (lib.mcomh_name_pack_file_mate if pack else lib.mcomh_name_unpack_file_mate)(os.fsencode(in_path), os.fsencode(mate_path), os.fsencode(out_path), dev)
+    if rc:
         raise McomError(f"cannot {'pack' if pack else 'unpack'} {in_path}" + ("" if device is None else f" on GPU {device}"))
 
 
@@ -794,6 +884,11 @@ class Pipeline:
         the first file, rows [n/2, n) their mates)."""
         fn = self.lib.mcomh_cluster_dump_pe if paired else self.lib.mcomh_cluster_dump_order if order else self.lib.mcomh_cluster_dump
         self._check(fn(self._h, folder.encode()))
+
+    def cluster_dump_order_pe(self, folder: str):
+        """mcomh_cluster_dump_order_pe: a pipeline made of two files, dumped in input order -- the order-preserving file set of the 2 n rows
+        and pe_order.txt."""
+        self._check(self.lib.mcomh_cluster_dump_order_pe(self._h, folder.encode()))
 
     def prof_enable(self, on: bool = True): self._check(self.lib.mcomh_prof_enable(self._h, 1 if on else 0))
 
