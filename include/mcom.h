@@ -822,6 +822,30 @@ enum mcom_gather_flag {
 int mcom_qual_gather_rows(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_src, uint32_t L, uint64_t pitch_in, const uint32_t *d_order,
                           uint64_t n_rows, uint8_t *d_out, uint64_t pitch_out, uint32_t *d_flag);
 
+/* ---- lossy quality values (csrc/qual_lossy.hip; the transform and its host twin: DESIGN.md section 3.13, include/mcom_host.h) ----
+ * mcom_qual_transform rewrites a matrix of n_rows x L bytes in HBM in place (rows `pitch` >= L apart, any address, 1 <= L <= 256, below
+ * 2^32 rows), row by row and deterministically, between the gather of the rows and mcom_qual_encode.  The bytes between two rows
+ * (pitch > L) are never written.  The spec is one of
+ *   MCOM_QUAL_LOSSY_ILL8    the eight Illumina bins (p unused)
+ *   MCOM_QUAL_LOSSY_THR     p[0] = T, p[1] = LO, p[2] = HI (0 .. 93): Phred < T -> LO, otherwise HI
+ *   MCOM_QUAL_LOSSY_PBLOCK  p[0] = P (1 .. 47): P-block smoothing, no byte moves by more than P; NOT idempotent
+ *   MCOM_QUAL_LOSSY_LUT     a general byte map in lut[]
+ * A byte map that is not idempotent (lut[lut[v]] != lut[v] for some v: thr with LO >= T or HI < T, for one) and every value outside
+ * these ranges is MCOM_E_ARG; no byte and no word of the report is touched then.  *h_report (may be NULL) gets exact integers counted in
+ * the same pass: bytes that changed, the sum of |d|, the sum of d * d and the largest |d| over all bytes.  Synchronous.  The bytes and
+ * the report equal those of mcomh_qual_transform.                                                                                     */
+enum mcom_qual_lossy_kind { MCOM_QUAL_LOSSY_ILL8 = 1, MCOM_QUAL_LOSSY_THR = 2, MCOM_QUAL_LOSSY_PBLOCK = 3, MCOM_QUAL_LOSSY_LUT = 4 };
+typedef struct {
+	uint32_t kind;
+	uint32_t p[3];
+	uint8_t lut[256];
+} mcom_qual_lossy_spec;
+typedef struct {
+	uint64_t changed, sum_abs, sum_sq, max_abs;
+} mcom_qual_lossy_report;
+int mcom_qual_transform(mcom_ctx *ctx, uint8_t *d_rows, uint64_t n_rows, uint32_t L, uint64_t pitch, const mcom_qual_lossy_spec *spec,
+                        mcom_qual_lossy_report *h_report);
+
 /* ---- read names and '+' lines: `.mcn` members (csrc/names.hip; format and host twin: DESIGN.md section 3.10, include/mcom_host.h) ----
  * The name text of n records is 2 n lines: line 1 of a record without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at
  * most 255 bytes a line.  Names are cut into digit runs and other runs, every token coded against the same token of the record before

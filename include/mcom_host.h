@@ -350,6 +350,42 @@ int mcomh_decompress_fastq_pe(const char *folder, const char *out_path1, const c
 int mcomh_decompress_fastq_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device);
 int mcomh_verify_records_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep);
 
+/* ---- `minicom -b SPEC`: lossy quality values (host/mcom_qual_lossy.cpp) ----
+ * A row-local, deterministic transform of the quality matrix in front of the coder: `ill8` (the eight Illumina bins), `thr:T:LO:HI`
+ * (two values) and `pblock:P` (smoothing, no byte moves by more than P; NOT idempotent).  The `.mcq` format and the decoders do not
+ * change; the archive says so in the plain file qual_lossy.txt (the canonical spec and a newline), and the verifiers send the FASTQ
+ * file's quality rows through the same transform before they compare: the archive holds exactly T(file).
+ *   mcomh_qual_lossy_parse   the canonical text (decimal numbers, no leading zeros, nothing behind it) -> spec; -1 for anything else,
+ *                            a thr that is not idempotent (LO >= T or HI < T) included
+ *   mcomh_qual_lossy_print   spec -> text (at most 32 bytes with the NUL); -1 for a general map or a spec the transform refuses
+ *   mcomh_qual_transform     the host twin of mcom_qual_transform (include/mcom.h): the same arguments over host memory, the same bytes,
+ *                            the same report, the same specs refused (-1, nothing touched)
+ *   mcomh_qual_pack_file_lossy / mcomh_fastq_quality_member_lossy   mcomh_qual_pack_file and mcomh_fastq_quality_member[_ordered]
+ *                            (order_path NULL: input order) with the transform between the rows and the coder: on GPU `device`
+ *                            mcom_qual_transform, device = -1 the host twin; *report (may be NULL) gets the report.  A refused spec
+ *                            writes nothing.  spec NULL: the calls they are named after
+ *   mcomh_qual_lossy_marker  FOLDER/qual_lossy.txt: 0 = none (*spec untouched), 1 = read (spec and, when text is given, its canonical
+ *                            text), -1 = there but not a canonical spec and a newline -- the verifiers refuse such an archive           */
+#define MCOMH_QUAL_LOSSY_ILL8 1
+#define MCOMH_QUAL_LOSSY_THR 2
+#define MCOMH_QUAL_LOSSY_PBLOCK 3
+#define MCOMH_QUAL_LOSSY_LUT 4
+typedef struct {
+	uint32_t kind;                              /* MCOMH_QUAL_LOSSY_*                                                          */
+	uint32_t p[3];                              /* thr: T, LO, HI; pblock: P                                                    */
+	uint8_t lut[256];                           /* MCOMH_QUAL_LOSSY_LUT: the byte map (parse fills it for the named maps too)   */
+} mcomh_qual_lossy_spec;
+typedef struct {
+	uint64_t changed, sum_abs, sum_sq, max_abs; /* bytes that changed, sum of |d|, sum of d * d, largest |d|                    */
+} mcomh_qual_lossy_report;
+int mcomh_qual_lossy_parse(const char *text, mcomh_qual_lossy_spec *spec);
+int mcomh_qual_lossy_print(const mcomh_qual_lossy_spec *spec, char *text, size_t cap);
+int mcomh_qual_transform(uint8_t *rows, uint64_t n_rows, uint32_t L, uint64_t pitch, const mcomh_qual_lossy_spec *spec, mcomh_qual_lossy_report *report);
+int mcomh_qual_pack_file_lossy(const char *in_path, const char *out_path, int L, int device, const mcomh_qual_lossy_spec *spec, mcomh_qual_lossy_report *report);
+int mcomh_fastq_quality_member_lossy(const char *fastq, int L, int device, const char *order_path, const mcomh_qual_lossy_spec *spec, const char *out_path,
+                                     uint64_t *n, mcomh_qual_lossy_report *report, char *err, size_t err_cap);
+int mcomh_qual_lossy_marker(const char *folder, mcomh_qual_lossy_spec *spec, char *text, size_t cap);
+
 /* ---- read names and '+' lines: `.mcn` members (host/mcom_names.cpp) ----
  * The host twin of mcom_name_encode / mcom_name_decode (include/mcom.h).  The name text of n records is 2 n lines: line 1 of a record
  * without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at most 255 bytes a line.  Names are cut into tokens and coded

@@ -72,6 +72,9 @@ int mcom_test_qual_hist(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_rows, u
  * the same launches: with 2 or 0 bits nearly every run of equal hashes holds unequal records, so that a thousand rows walk the path
  * real data reaches once in 2^64 -- the run settled in full on the host.  Same verdict and counts at any width.                    */
 int mcom_set_verify_hash_bits(mcom_ctx *ctx, int bits);
+/* mcom_qual_transform's P-block kernel (csrc/qual_lossy.hip) stages tiles of whole rows in LDS, one lane per row: the rows of a tile,
+ * so that a test can put its rows on both sides of a tile's edge.                                                                     */
+uint32_t mcom_test_qual_pblock_tile_rows(void);
 
 
 /* ---- libmcom_host.so ---- */

@@ -45,6 +45,7 @@ REORDERED_MEMBERS = ("rqual.mcq", "rqual_1.mcq", "rqual_2.mcq")     # quality va
 READ_ORDER = "read_order.bin"     # temporary of compress_fastq(quality_reordered=True): never a member
 PAIR_ORDER = "pe_order.txt"       # marks a pair kept in input order: one line, the number of pairs; stored as it is
 PAIR_MEMBERS = ("qual_1.mcq", "qual_2.mcq", "name_1.mcn", "name_2.mcn")     # its quality values and names, file by file; name_2 is coded against name_1
+LOSSY_MARKER = "qual_lossy.txt"   # marks quality values stored with bounded loss: the canonical spec and a newline; stored as it is
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -157,7 +158,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
     if os.path.isfile(os.path.join(folder, NAME_MEMBER)):        # likewise (section 3.10)
         with open(os.path.join(folder, NAME_MEMBER), "rb") as f:
             packed.append((NAME_MEMBER, f.read()))
-    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS:   # likewise (sections 3.11 and 3.12)
+    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS + (LOSSY_MARKER,):   # likewise (sections 3.11, 3.12 and 3.13)
         if os.path.isfile(os.path.join(folder, m)):
             with open(os.path.join(folder, m), "rb") as f:
                 packed.append((m, f.read()))
@@ -179,7 +180,9 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
     {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334), and "quality": True for an archive
     that carries quality values (the member qual.mcq, left in the folder as it is), "quality_reordered": True for one that carries them
     in its own order (rqual.mcq, or rqual_1.mcq and rqual_2.mcq), "pair_order": True for a pair kept in input order (pe_order.txt; then
-    "quality" / "names" speak of qual_1.mcq + qual_2.mcq / name_1.mcn + name_2.mcn).
+    "quality" / "names" speak of qual_1.mcq + qual_2.mcq / name_1.mcn + name_2.mcn), "quality_lossy": the text of qual_lossy.txt for
+    an archive whose quality values went through a lossy transform (the file is left in the folder, where the
+    verifiers look for it).
     device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
@@ -188,7 +191,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS:
+        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS or name == LOSSY_MARKER:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -212,6 +215,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             kinds["quality_reordered"] = True
         if name == PAIR_ORDER:
             kinds["pair_order"] = True
+        if name == LOSSY_MARKER:
+            kinds["quality_lossy"] = data.decode("latin-1").rstrip("\n")      # (as stored: the verifiers judge whether it is a spec)
         if name in PAIR_MEMBERS:
             kinds["quality" if name.endswith(".mcq") else "names"] = True
         if name.startswith("idsbin.tar"):
@@ -234,7 +239,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, quality_reordered: bool = False,
-                   **params) -> dict:
+                   quality_lossy=None, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
@@ -243,10 +248,14 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     name.mcn, coded on `device`, and decompress_file then gives the input file back byte for byte.
     quality_reordered=True (`minicom -q`; not with order, quality or names; allowed with path2): the quality rows are put into the archive's
     own order on `device` and travel as rqual.mcq (rqual_1.mcq and rqual_2.mcq for a pair); decompress_file gives four-line records in that
-    order, named by their row.  Returns pack()'s member sizes plus the read count."""
+    order, named by their row.
+    quality_lossy (`minicom -b SPEC`; needs quality or quality_reordered): a lossy spec (`ill8`, `thr:T:LO:HI`,
+    `pblock:P`); the quality rows go through mcom_qual_transform on `device` in front of the coder, and the archive says so in
+    qual_lossy.txt.  Returns pack()'s member sizes plus the read count."""
     import tempfile
     from .hip import McomError
     from .pipeline import Pipeline
+    lossy = _lossy_spec(quality_lossy, quality or quality_reordered)
     if order and path2 is not None:
         raise ValueError("-p is a single-end option (reference minicom:439-476)")
     if quality and (not order or path2 is not None):
@@ -266,15 +275,16 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
                 from .pipeline import fastq_quality_member
                 order_path = os.path.join(td, READ_ORDER)
                 for fq, member in ((path, "rqual.mcq"),) if path2 is None else ((path, "rqual_1.mcq"), (path2, "rqual_2.mcq")):
-                    fastq_quality_member(fq, p.L, os.path.join(td, member), device=device, order_path=order_path)
+                    fastq_quality_member(fq, p.L, os.path.join(td, member), device=device, order_path=order_path, lossy=lossy)
                 os.remove(order_path)
             if quality:
-                _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER))
+                _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER), lossy)
             if names:
                 from .pipeline import fastq_name_member
                 n_names = fastq_name_member(path, os.path.join(td, NAME_MEMBER), device=device)
                 if n_names != p.n:
                     raise McomError("%s: %d names for %d reads" % (path, n_names, p.n))
+            _mark_lossy(td, lossy)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         return sizes
@@ -283,16 +293,18 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
 
 
 def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = False, names: bool = False, codec: str = "xz", device: int = 0,
-                        threads: int = 8, **params) -> dict:
+                        threads: int = 8, quality_lossy=None, **params) -> dict:
     """Two FASTQ files of a pair -> a `.minicom` archive that keeps both in input order (`minicom -1 A_1.fastq -2 A_2.fastq -p [-Q [-N]]`,
     DESIGN.md section 3.12): the order-preserving members of the second file's reads behind the first's, and pe_order.txt.  quality=True:
     qual_1.mcq and qual_2.mcq; names=True (needs quality=True): name_1.mcn and name_2.mcn, the second coded against the first file's names
-    -- decompress_file then gives both input files back byte for byte.  Returns pack()'s member sizes plus the number of pairs."""
+    -- decompress_file then gives both input files back byte for byte.  quality_lossy (needs quality=True): as for compress_fastq.
+    Returns pack()'s member sizes plus the number of pairs."""
     import tempfile
     from .hip import McomError
     from .pipeline import Pipeline, fastq_name_member
     if names and not quality:
         raise ValueError("names are kept beside the quality values only (quality=True)")
+    lossy = _lossy_spec(quality_lossy, quality)
     p = Pipeline.from_fastq(path1, device=device, path2=path2, host_threads=threads, **params)
     try:
         p.pre_process()
@@ -301,11 +313,12 @@ def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = F
             half = p.n // 2
             for k, fq in ((1, path1), (2, path2)):
                 if quality:
-                    _quality_member(fq, half, p.L, device, os.path.join(td, "qual_%d.mcq" % k))
+                    _quality_member(fq, half, p.L, device, os.path.join(td, "qual_%d.mcq" % k), lossy)
                 if names:
                     n_names = fastq_name_member(fq, os.path.join(td, "name_%d.mcn" % k), device=device, mate_path=path1 if k == 2 else None)
                     if n_names != half:
                         raise McomError("%s: %d names for %d reads" % (fq, n_names, half))
+            _mark_lossy(td, lossy)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_pairs"] = half
         return sizes
@@ -313,14 +326,37 @@ def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = F
         p.close()
 
 
-def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str) -> None:
-    """the quality lines of `fastq` -> rows on the device -> a `.mcq` member in out_path"""
+def _lossy_spec(quality_lossy, keeps_quality: bool):
+    """the canonical text of compress_fastq's quality_lossy (None: none); ValueError without quality values or for a spec the parser refuses"""
+    if quality_lossy is None:
+        return None
+    from .hip import McomError
+    from .pipeline import qual_lossy_text
+    if not keeps_quality:
+        raise ValueError("quality_lossy changes the quality values that quality / quality_reordered keep: without either there are none")
+    try:
+        return qual_lossy_text(quality_lossy)
+    except McomError as e:
+        raise ValueError(str(e)) from None
+
+
+def _mark_lossy(folder: str, lossy) -> None:
+    if lossy is not None:
+        with open(os.path.join(folder, LOSSY_MARKER), "wb") as f:
+            f.write(lossy.encode() + b"\n")
+
+
+def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str, lossy=None) -> None:
+    """the quality lines of `fastq` -> rows on the device [-> the lossy transform, in place] -> a `.mcq` member in out_path"""
     from .hip import Context, McomError
     from .pipeline import fastq_qualities
     rows = fastq_qualities(fastq, L, device=device)
     if int(rows.shape[0]) != n:
         raise McomError("%s: %d quality lines for %d reads" % (fastq, int(rows.shape[0]), n))
-    member = Context(device).qual_encode(rows)
+    ctx = Context(device)
+    if lossy is not None:
+        rows, _ = ctx.qual_transform(rows, lossy, in_place=True)
+    member = ctx.qual_encode(rows)
     with open(out_path, "wb") as f:
         f.write(member.cpu().numpy().tobytes())
 
@@ -360,7 +396,9 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
 def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int = 8, device: int = 0) -> dict:
     """`.minicom` against the FASTQ it was made from, on GPU `device`, without writing a read: pipeline.verify's report.  The mode comes
     from the members, as in decompress_file: a paired-end archive needs `fastq2`, a -p archive is held line against line, any other
-    one as a multiset of reads.  An archive with quality values is held against the quality lines as well: the report gets
+    one as a multiset of reads.  For an archive made with quality_lossy the FASTQ file's quality rows go through the transform that
+    qual_lossy.txt names before they are compared (the report gets "quality_lossy": its spec; McomError when the file holds no spec).
+    An archive with quality values is held against the quality lines as well: the report gets
     "quality" (pipeline.verify_quality's) and "identical" is true only when both checks say so; one with names likewise gets "names"
     (pipeline.verify_names's)."""
     import tempfile
@@ -370,17 +408,20 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
         raise McomError("no such archive: %s" % path)
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        from .pipeline import qual_lossy_marker
+        lossy = qual_lossy_marker(td)                                # (McomError for a marker that is no spec)
+        tag = lambda r: dict(r, quality_lossy=lossy) if lossy is not None else r
         if kinds.get("pair_order"):
             from .pipeline import verify_order_pe
             if fastq2 is None:
                 raise McomError("an archive of a pair is verified against two FASTQ files")
-            return verify_order_pe(td, fastq, fastq2, device=device)
+            return tag(verify_order_pe(td, fastq, fastq2, device=device))
         if kinds["paired"] != (fastq2 is not None):
             raise McomError("a paired-end archive is verified against two FASTQ files, any other against one")
         if kinds.get("quality_reordered"):
             from .pipeline import verify_records
-            return verify_records(td, fastq, fastq2, device=device)
-        rep = verify(td, fastq, fastq2, order=kinds["order"], device=device)
+            return tag(verify_records(td, fastq, fastq2, device=device))
+        rep = tag(verify(td, fastq, fastq2, order=kinds["order"], device=device))
         if kinds.get("quality"):
             rep["quality"] = verify_quality(td, fastq, device=device)
             rep["identical"] = rep["identical"] and rep["quality"]["identical"]

@@ -43,6 +43,28 @@ class VerifyReport(C.Structure):
                 ("n_missing_ex", C.c_uint32), ("n_extra_ex", C.c_uint32), ("identical", C.c_int)]
 
 
+class QualLossySpec(C.Structure):
+    """mcom_qual_lossy_spec of include/mcom.h = mcomh_qual_lossy_spec of include/mcom_host.h"""
+    ILL8, THR, PBLOCK, LUT = 1, 2, 3, 4
+    _fields_ = [("kind", C.c_uint32), ("p", C.c_uint32 * 3), ("lut", C.c_uint8 * 256)]
+
+    @classmethod
+    def from_lut(cls, lut):
+        """a general byte map: 256 values; the transform refuses one that is not idempotent"""
+        s = cls(); s.kind = cls.LUT
+        lut = np.asarray(lut, dtype=np.uint8).reshape(256)
+        C.memmove(s.lut, lut.ctypes.data, 256)
+        return s
+
+
+class QualLossyReport(C.Structure):
+    """mcom_qual_lossy_report of include/mcom.h"""
+    _fields_ = [("changed", C.c_uint64), ("sum_abs", C.c_uint64), ("sum_sq", C.c_uint64), ("max_abs", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"changed": int(self.changed), "sum_abs": int(self.sum_abs), "sum_sq": int(self.sum_sq), "max_abs": int(self.max_abs)}
+
+
 def rans_hint(model: int, stride: int = 1) -> int:
     """MCOM_RANS_HINT of include/mcom.h"""
     return 0x100 | (model << 4) | stride
@@ -182,6 +204,8 @@ def load_library():
     L.mcom_qual_gather_rows.restype = i32; L.mcom_qual_gather_rows.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, vp, u64, vp]
     L.mcom_dump_read_order.restype = i32; L.mcom_dump_read_order.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
     L.mcom_verify_multiset_parts.restype = i32; L.mcom_verify_multiset_parts.argtypes = [vp, C.POINTER(VerifyParts), C.POINTER(VerifyParts), i32, C.POINTER(VerifyReport)]
+    L.mcom_qual_transform.restype = i32; L.mcom_qual_transform.argtypes = [vp, vp, u64, C.c_uint32, u64, C.POINTER(QualLossySpec), C.POINTER(QualLossyReport)]
+    L.mcom_test_qual_pblock_tile_rows.restype = C.c_uint32; L.mcom_test_qual_pblock_tile_rows.argtypes = []
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_name_bound.restype = u64; L.mcom_name_bound.argtypes = [u64]
@@ -1032,6 +1056,31 @@ class Context:
         self._check(self.lib.mcom_qual_gather_rows(self._h, rows.data_ptr() if n_src else None, n_src, L, pitch_in, order.data_ptr() if n_rows else None, n_rows,
                                                    out.data_ptr() if n_rows else None, pitch_out, self._p(flag)))
         return out[:, :L], int(flag.item())
+
+    def qual_transform(self, rows, spec, in_place: bool = False):
+        """mcom_qual_transform.  rows: uint8 device matrix [n, L] with contiguous rows (any row stride >= L, any
+        address); spec: a QualLossySpec or the canonical text of one (`ill8`, `thr:T:LO:HI`, `pblock:P`).  Returns (the transformed
+        matrix, the report as a dict of exact integers: changed, sum_abs, sum_sq, max_abs).  The matrix is a copy unless in_place: then
+        rows itself is rewritten (the bytes between its rows stay) and returned.  McomError, with rows and nothing else touched, for a
+        spec the transform refuses (a byte map that is not idempotent)."""
+        torch = _torch()
+        if not isinstance(spec, QualLossySpec):
+            from .pipeline import qual_lossy_spec
+            spec = qual_lossy_spec(spec)
+        if rows.dim() != 2 or rows.dtype != torch.uint8 or (rows.shape[0] and rows.stride(1) != 1):
+            raise McomError("qual_transform: a uint8 matrix with contiguous rows")
+        n, L = int(rows.shape[0]), int(rows.shape[1])
+        if not in_place:
+            rows = rows.contiguous().clone()
+        pitch = int(rows.stride(0)) if n > 1 else L
+        rep = QualLossyReport()
+        self._check(self.lib.mcom_qual_transform(self._h, rows.data_ptr() if n else None, n, L, pitch, C.byref(spec), C.byref(rep)))
+        return rows, rep.as_dict()
+
+    @staticmethod
+    def qual_pblock_tile_rows() -> int:
+        """Test hook (mcom_test_qual_pblock_tile_rows): the rows of one tile of the P-block kernel"""
+        return int(load_library().mcom_test_qual_pblock_tile_rows())
 
     def dump_read_order(self, lists, mem, half: int = 0):
         """mcom_dump_read_order (DESIGN.md section 3.11).  lists: int32 device vector, the read ids of the eight lists in the decoder's order;

@@ -31,6 +31,16 @@ static void examples(const char *what, const uint64_t *ex, uint32_t n)
 	printf("\n");
 }
 
+// " under SPEC" for an archive made with `minicom -b SPEC` (qual_lossy.txt; the verifier has read it already, so it parses), "" otherwise
+static const char *under(const char *folder)
+{
+	static char text[48];
+	mcomh_qual_lossy_spec sp; char spec[40];
+	text[0] = 0;
+	if (mcomh_qual_lossy_marker(folder, &sp, spec, sizeof spec) == 1) snprintf(text, sizeof text, " under %s", spec);
+	return text;
+}
+
 static int verify(int argc, char **argv)
 {
 	if (argc < 6) { fprintf(stderr, "usage: decompress --verify DIR IN.fastq pe(true|false) order(true|false) nthr [IN_2.fastq]\n"); return 1; }
@@ -63,7 +73,7 @@ static int verify_quality(int argc, char **argv)
 	if (argc < 3) { fprintf(stderr, "usage: decompress --verify-quality DIR IN.fastq\n"); return 1; }
 	mcomh_verify_report r;
 	if (mcomh_verify_quality_gpu(argv[1], argv[2], 0, &r)) { fprintf(stderr, "decompress: the qualities of %s could not be verified against %s\n", argv[1], argv[2]); return 1; }
-	if (r.identical) { printf("verified: %llu quality lines identical\n", (unsigned long long)r.n_input); return 0; }
+	if (r.identical) { printf("verified: %llu quality lines identical%s\n", (unsigned long long)r.n_input, under(argv[1])); return 0; }
 	printf("DIFFERENT: the FASTQ holds %llu quality lines, the archive %llu\n  %llu lines differ", (unsigned long long)r.n_input, (unsigned long long)r.n_archive, (unsigned long long)r.differing);
 	if (r.differing) printf(", the first one is line %llu (from 0)", (unsigned long long)r.first_diff);
 	printf("\n");
@@ -116,7 +126,7 @@ static int verify_records(int argc, char **argv)
 	mcomh_verify_report r;
 	if (mcomh_verify_records_gpu(argv[1], pe ? 2 : 0, argv[2], pe ? argv[3] : nullptr, 0, &r)) { fprintf(stderr, "decompress: the records of %s could not be verified against %s\n", argv[1], argv[2]); return 1; }
 	const char *unit = pe ? "pairs with their quality lines" : "reads with their quality lines";
-	if (r.identical) { printf("verified: %llu %s identical\n", (unsigned long long)r.n_input, unit); return 0; }
+	if (r.identical) { printf("verified: %llu %s identical%s\n", (unsigned long long)r.n_input, unit, under(argv[1])); return 0; }
 	printf("DIFFERENT: the FASTQ holds %llu %s, the archive %llu\n", (unsigned long long)r.n_input, unit, (unsigned long long)r.n_archive);
 	printf("  %llu records of the FASTQ are missing from the archive, %llu records of the archive are not in the FASTQ\n", (unsigned long long)r.missing, (unsigned long long)r.extra);
 	examples("missing (numbered from 0 in the FASTQ)", r.missing_ex, r.n_missing_ex);
@@ -147,7 +157,7 @@ static int verify_order_pe(int argc, char **argv)
 	int rc = 0;
 	for (int k = 0; k < 5; ++k) {
 		if (!present[k]) continue;
-		if (r[k].identical) { printf("verified: %llu %s identical\n", (unsigned long long)r[k].n_input, what[k]); continue; }
+		if (r[k].identical) { printf("verified: %llu %s identical%s\n", (unsigned long long)r[k].n_input, what[k], k == 1 || k == 2 ? under(argv[1]) : ""); continue; }
 		rc = 2;
 		printf("DIFFERENT: %s: the FASTQ holds %llu, the archive %llu\n  %llu differ", what[k], (unsigned long long)r[k].n_input, (unsigned long long)r[k].n_archive, (unsigned long long)r[k].differing);
 		if (r[k].differing) printf(", the first one is %s %llu (from 0)", k >= 3 ? "record" : "line", (unsigned long long)r[k].first_diff);

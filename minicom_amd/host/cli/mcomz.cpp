@@ -11,6 +11,11 @@
 // mcomz e --fastq-qual L --order FILE [--gpu] IN.fastq OUT: the same with row j of the member = record order[j] of IN.fastq, FILE holding
 // one little-endian u32 per record (read_order.bin of `minicom -q`); exit status 1 and no member when FILE is
 // no permutation of the records (its size, its entry count, an entry beyond the last record, a record named twice).
+// mcomz e --qual L --lossy SPEC, mcomz e --fastq-qual L [--order FILE] --lossy SPEC: the rows go through the lossy transform SPEC (ill8,
+// thr:T:LO:HI or pblock:P in their canonical form) in front of the coder -- mcom_qual_transform with --gpu, its host
+// twin without, the same member either way.  The report goes to stderr in one line, `lossy SPEC: changed C sum_abs A sum_sq S max_abs M`;
+// a spec the parser refuses is exit status 1 and no member.  pblock is not idempotent: coding a decoded matrix again changes it again.
+// mcomz --lossy-spec SPEC: prints the canonical text of SPEC; exit status 1 when the parser refuses it (what `minicom -b` asks first).
 // mcomz e --names [--gpu] IN OUT: IN is a name text (per record its name and the text of its third line, a line each; DESIGN.md section
 // 3.10), OUT a `.mcn` member; a line above 255 bytes is refused and its record named.  d knows such a member by its magic.
 // mcomz e --fastq-names [--gpu] IN.fastq OUT: the names and '+' texts of a four-line FASTQ file (plain or .gz) -> a `.mcn` member; every
@@ -36,14 +41,21 @@ static bool has_magic(const char *path, const char *magic4)
 
 int main(int argc, char **argv)
 {
+	if (argc == 3 && !strcmp(argv[1], "--lossy-spec")) {
+		mcomh_qual_lossy_spec sp; char text[32];
+		if (mcomh_qual_lossy_parse(argv[2], &sp) || mcomh_qual_lossy_print(&sp, text, sizeof text)) return 1;
+		printf("%s\n", text);
+		return 0;
+	}
 	bool gpu = false, bwt = false, names = false, fastq_names = false;
 	int at = 2, qual_L = 0, fastq_L = 0;
-	const char *order_path = nullptr, *mate_path = nullptr;
+	const char *order_path = nullptr, *mate_path = nullptr, *lossy_text = nullptr;
 	for (; at < argc; ++at) {
 		if (!strcmp(argv[at], "--gpu") && !gpu) gpu = true;
 		else if (!strcmp(argv[at], "--qual") && !qual_L && at + 1 < argc) { qual_L = atoi(argv[++at]); if (qual_L < 1 || qual_L > 256) { fprintf(stderr, "mcomz: --qual takes the row length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--fastq-qual") && !fastq_L && at + 1 < argc) { fastq_L = atoi(argv[++at]); if (fastq_L < 1 || fastq_L > 256) { fprintf(stderr, "mcomz: --fastq-qual takes the read length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--order") && !order_path && at + 1 < argc) order_path = argv[++at];
+		else if (!strcmp(argv[at], "--lossy") && !lossy_text && at + 1 < argc) lossy_text = argv[++at];
 		else if (!strcmp(argv[at], "--mate") && !mate_path && at + 1 < argc) mate_path = argv[++at];
 		else if (!strcmp(argv[at], "--bwt") && !bwt) bwt = true;
 		else if (!strcmp(argv[at], "--names") && !names) names = true;
@@ -51,10 +63,26 @@ int main(int argc, char **argv)
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (lossy_text && !fastq_L && !qual_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--lossy SPEC] [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--lossy SPEC] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;
+	mcomh_qual_lossy_spec lossy; mcomh_qual_lossy_report lossy_rep = {0, 0, 0, 0};
+	if (lossy_text && mcomh_qual_lossy_parse(lossy_text, &lossy)) {
+		fprintf(stderr, "mcomz: --lossy takes ill8, thr:T:LO:HI (0 <= LO < T <= HI <= 93) or pblock:P (1 .. 47), decimal numbers without leading zeros; '%s' is none\n", lossy_text);
+		return 1;
+	}
+	auto report = [&]() {
+		fprintf(stderr, "lossy %s: changed %llu sum_abs %llu sum_sq %llu max_abs %llu\n", lossy_text, (unsigned long long)lossy_rep.changed, (unsigned long long)lossy_rep.sum_abs,
+		        (unsigned long long)lossy_rep.sum_sq, (unsigned long long)lossy_rep.max_abs);
+	};
+	if (fastq_L && lossy_text) {
+		char err[320] = ""; uint64_t n = 0;
+		if (mcomh_fastq_quality_member_lossy(in, fastq_L, device, order_path, &lossy, out, &n, &lossy_rep, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
+		report();
+		printf("%llu\n", (unsigned long long)n);
+		return 0;
+	}
 	if (fastq_L) {
 		char err[320] = ""; uint64_t n = 0;
 		if (order_path ? mcomh_fastq_quality_member_ordered(in, fastq_L, device, order_path, out, &n, err, sizeof err) : mcomh_fastq_quality_member(in, fastq_L, device, out, &n, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
@@ -75,7 +103,8 @@ int main(int argc, char **argv)
 		return rc ? 1 : 0;
 	}
 	if (qual_L || (dec && has_magic(in, "MCQV"))) {
-		rc = enc ? mcomh_qual_pack_file(in, out, qual_L, device) : mcomh_qual_unpack_file(in, out, device);
+		rc = !enc ? mcomh_qual_unpack_file(in, out, device) : lossy_text ? mcomh_qual_pack_file_lossy(in, out, qual_L, device, &lossy, &lossy_rep) : mcomh_qual_pack_file(in, out, qual_L, device);
+		if (!rc && enc && lossy_text) report();
 		if (rc) fprintf(stderr, enc ? "mcomz: cannot pack %s into %s%s\n" : "mcomz: %s is not a complete, intact .mcq member, or %s cannot be written%s\n", in, out, gpu ? " (or the GPU route is not available)" : "");
 		return rc ? 1 : 0;
 	}

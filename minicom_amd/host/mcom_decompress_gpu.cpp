@@ -13,6 +13,7 @@
 // No output file is left behind by a refused archive; there is no fall back to the host decoder.
 #include "../../include/mcom_host.h"
 #include "../../include/mcom.h"
+#include "mcom_fastq.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
@@ -571,6 +572,7 @@ int verify_records(const char *folder, int mode, const char *fastq1, const char 
 		if (L_in < 1 || mcomh_fastq_qualities_to_device(fq[k], device, L_in, 0, &qin[k].d, &nq[k], err, sizeof(err)) || nq[k] != n_rec) {
 			fprintf(stderr, "minicom verify: cannot read the qualities of %s: %s\n", fq[k], err[0] ? err : "another number of records than reads"); return -1;
 		}
+		if (mcom_qual_lossy_apply_marker(folder, device, qin[k].d, nq[k], L_in)) return -1;   // an archive made with -b holds T(file): row-local, so it commutes with the order
 	}
 	const double ingest = now_ms() - t_begin;
 	const int rr = run((Mode)mode, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L) {

@@ -15,3 +15,7 @@ int mcom_fastq_stream_len(const McomFastqStream *st);
 // the pieces: provisional first row and number of rows of each (arrays of the returned size; NULL: just the size)
 size_t mcom_fastq_stream_pieces(const McomFastqStream *st, size_t *prov, size_t *count);
 void mcom_fastq_stream_free(McomFastqStream *st);
+// mcom_qual_gpu.cpp: FOLDER/qual_lossy.txt, when there, applied to the n x L quality rows at d_rows on GPU `device` by
+// mcom_qual_transform -- what a verifier does to the FASTQ file's rows before it compares.  0 = no marker, or applied; -1 = a marker that
+// is not a spec, or a device error (the message is printed)
+int mcom_qual_lossy_apply_marker(const char *folder, int device, uint8_t *d_rows, size_t n, int L);

@@ -7,8 +7,11 @@
 // card mcom_decode_line_index finds the lines and mcom_fastq_quality_rows checks every record and gathers its quality line.  A file
 // the kernel flags is an error that names the first bad record; it is not handed to another parser.
 // mcomh_verify_quality_gpu: qual.mcq decoded by mcom_qual_decode, the file's rows as above, mcom_verify_ordered over both.
+// `minicom -b SPEC`: the `_lossy` file calls send the rows through mcom_qual_transform (device -1: its host twin,
+// host/mcom_qual_lossy.cpp) in front of the coder, and the verifiers send the file's rows through it when the folder holds qual_lossy.txt.
 #include "../../include/mcom_host.h"
 #include "../../include/mcom.h"
+#include "mcom_fastq.hpp"
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 #include <chrono>
@@ -45,6 +48,13 @@ int fail(char *err, size_t cap, const char *fmt, unsigned long long a = 0, unsig
 {
 	if (err && cap) snprintf(err, cap, fmt, a, b);
 	return -1;
+}
+
+// is it a spec the transform takes?  Asked before a file is read: a refused spec does no work and writes nothing
+bool spec_ok(const mcomh_qual_lossy_spec *spec)
+{
+	uint8_t none = 0;
+	return mcomh_qual_transform(&none, 0, 1, 1, spec, nullptr) == 0;
 }
 
 void record_message(char *err, size_t cap, unsigned long long record1, int L, uint32_t bits)
@@ -170,6 +180,7 @@ int verify_quality(const char *folder, const char *member_name, const char *fast
 	size_t n_in = 0;
 	char err[320] = "";
 	if (qualities(fastq, device, (int)qL, 0, &in.d, &n_in, err, sizeof err)) { fprintf(stderr, "minicom verify: cannot read the qualities of %s: %s\n", fastq, err); return -1; }
+	if (mcom_qual_lossy_apply_marker(folder, device, in.d, n_in, (int)qL)) return -1;   // an archive made with -b holds T(file): section 3.13
 	const double ingest = now_ms() - t_begin;
 	struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d_member = nullptr, *d_rows = nullptr; ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d_member) (void)hipFree(d_member); if (d_rows) (void)hipFree(d_rows); if (ctx) mcom_destroy(ctx); } } D;
 	if (mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; return -1; }
@@ -260,7 +271,7 @@ bool open_device(DevBuf &D, int device, size_t bytes_a, size_t bytes_b)
 	return hipMalloc((void**)&D.a, bytes_a + 16) == hipSuccess && hipMalloc((void**)&D.b, bytes_b + 16) == hipSuccess;
 }
 
-int qual_file(const char *in_path, const char *out_path, int L, int device, bool pack)
+int qual_file(const char *in_path, const char *out_path, int L, int device, bool pack, const mcomh_qual_lossy_spec *spec = nullptr, mcomh_qual_lossy_report *rep = nullptr)
 {
 	if (!in_path || !out_path) return -1;
 	std::vector<uint8_t> in, out;
@@ -270,11 +281,15 @@ int qual_file(const char *in_path, const char *out_path, int L, int device, bool
 		const uint64_t n = in.size() / (size_t)L, cap = mcomh_qual_bound(n, (uint32_t)L);
 		uint64_t len = 0;
 		out.resize(cap);
-		if (device < 0) { if (mcomh_qual_encode(in.data(), n, (uint32_t)L, (uint64_t)L, out.data(), cap, &len, 0)) return -1; }
-		else {
+		if (spec && !spec_ok(spec)) { fprintf(stderr, "mcomz: not a lossy spec the transform takes\n"); return -1; }
+		if (device < 0) {
+			if (spec && mcomh_qual_transform(in.data(), n, (uint32_t)L, (uint64_t)L, spec, rep)) return -1;
+			if (mcomh_qual_encode(in.data(), n, (uint32_t)L, (uint64_t)L, out.data(), cap, &len, 0)) return -1;
+		} else {
 			DevBuf D;
 			if (!open_device(D, device, in.size(), cap)) return -1;
 			if (hipMemcpy(D.a, in.data(), in.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+			if (spec && mcom_qual_transform(D.ctx, D.a, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)spec, (mcom_qual_lossy_report*)rep)) { fprintf(stderr, "mcomz: %s\n", mcom_last_error(D.ctx)); return -1; }
 			if (mcom_qual_encode(D.ctx, D.a, n, (uint32_t)L, (uint64_t)L, D.b, cap, &len, 0)) { fprintf(stderr, "mcomz: %s\n", mcom_last_error(D.ctx)); return -1; }
 			if (hipMemcpy(out.data(), D.b, len, hipMemcpyDeviceToHost) != hipSuccess) return -1;
 		}
@@ -296,14 +311,16 @@ int qual_file(const char *in_path, const char *out_path, int L, int device, bool
 
 // FASTQ file -> `.mcq` member file (bin/mcomz e --fastq-qual L): on GPU `device` the quality lines are gathered by
 // mcomh_fastq_qualities_to_device and coded by mcom_qual_encode; device -1 is the host twin of both.  The same bytes either way.
-int fastq_member(const char *fastq, int L, int device, const char *out_path, uint64_t *n_out, char *err, size_t err_cap)
+int fastq_member(const char *fastq, int L, int device, const char *out_path, uint64_t *n_out, char *err, size_t err_cap, const mcomh_qual_lossy_spec *spec = nullptr, mcomh_qual_lossy_report *rep = nullptr)
 {
 	if (!fastq || !out_path) return fail(err, err_cap, "null pointer");
+	if (spec && !spec_ok(spec)) return fail(err, err_cap, "not a lossy spec the transform takes");
 	std::vector<uint8_t> out;
 	uint64_t len = 0; size_t n = 0;
 	if (device < 0) {
 		std::vector<uint8_t> rows;
 		if (host_qualities(fastq, L, rows, n, err, err_cap)) return -1;
+		if (spec && mcomh_qual_transform(rows.data(), n, (uint32_t)L, (uint64_t)L, spec, rep)) return fail(err, err_cap, "the lossy transform failed");
 		out.resize(mcomh_qual_bound(n, (uint32_t)L));
 		if (mcomh_qual_encode(rows.data(), n, (uint32_t)L, (uint64_t)L, out.data(), out.size(), &len, 0)) return fail(err, err_cap, "the quality coder failed");
 	} else {
@@ -313,6 +330,7 @@ int fastq_member(const char *fastq, int L, int device, const char *out_path, uin
 		struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d_out = nullptr; ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d_out) (void)hipFree(d_out); if (ctx) mcom_destroy(ctx); } } D;
 		if (mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
 		if (hipMalloc((void**)&D.d_out, cap + 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
+		if (spec && mcom_qual_transform(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)spec, (mcom_qual_lossy_report*)rep)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		if (mcom_qual_encode(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, D.d_out, cap, &len, 0)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		out.resize(len);
 		if (len && hipMemcpy(out.data(), D.d_out, len, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "download failed");
@@ -327,9 +345,11 @@ int fastq_member(const char *fastq, int L, int device, const char *out_path, uin
 // The ingest and its per-record checks are those above; then mcom_qual_gather_rows (host: its twin), which is also the check that the
 // order is a permutation of the records; then the coder.  No member is written when the order's size is no multiple of 4, its entry
 // count differs from the record count, or a flag is raised.  On the GPU the matrix is held twice: refused when the card has no room.
-int fastq_member_ordered(const char *fastq, int L, int device, const char *order_path, const char *out_path, uint64_t *n_out, char *err, size_t err_cap)
+int fastq_member_ordered(const char *fastq, int L, int device, const char *order_path, const char *out_path, uint64_t *n_out, char *err, size_t err_cap, const mcomh_qual_lossy_spec *spec = nullptr,
+                         mcomh_qual_lossy_report *rep = nullptr)
 {
 	if (!fastq || !out_path || !order_path) return fail(err, err_cap, "null pointer");
+	if (spec && !spec_ok(spec)) return fail(err, err_cap, "not a lossy spec the transform takes");
 	std::vector<uint8_t> ob;
 	if (!slurp_file(order_path, ob)) return fail(err, err_cap, "cannot read the order file");
 	if (ob.size() % 4) return fail(err, err_cap, "the order file holds %llu bytes: not a multiple of 4", (unsigned long long)ob.size());
@@ -351,6 +371,7 @@ int fastq_member_ordered(const char *fastq, int L, int device, const char *order
 		std::vector<uint8_t> sorted(rows.size() + 1);
 		if (mcomh_qual_gather_rows(rows.data(), n, (uint32_t)L, (uint64_t)L, order.data(), n, sorted.data(), (uint64_t)L, &flag)) return fail(err, err_cap, "the row gather failed");
 		if (flag) return flagged();
+		if (spec && mcomh_qual_transform(sorted.data(), n, (uint32_t)L, (uint64_t)L, spec, rep)) return fail(err, err_cap, "the lossy transform failed");
 		out.resize(mcomh_qual_bound(n, (uint32_t)L));
 		if (mcomh_qual_encode(sorted.data(), n, (uint32_t)L, (uint64_t)L, out.data(), out.size(), &len, 0)) return fail(err, err_cap, "the quality coder failed");
 	} else {
@@ -374,6 +395,7 @@ int fastq_member_ordered(const char *fastq, int L, int device, const char *order
 		if (mcom_qual_gather_rows(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, D.d_order, n, D.d_sorted, (uint64_t)L, d_flag)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "cannot read the flag word");
 		if (flag) return flagged();
+		if (spec && mcom_qual_transform(D.ctx, D.d_sorted, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)spec, (mcom_qual_lossy_report*)rep)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		if (mcom_qual_encode(D.ctx, D.d_sorted, n, (uint32_t)L, (uint64_t)L, D.d_out, cap, &len, 0)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		out.resize(len);
 		if (len && hipMemcpy(out.data(), D.d_out, len, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "download failed");
@@ -395,6 +417,30 @@ extern "C" int mcomh_fastq_quality_member(const char *fastq, int L, int device, 
 {
 	if (err && err_cap) err[0] = 0;
 	try { return fastq_member(fastq, L, device, out_path, n, err, err_cap); } catch (...) { return -1; }
+}
+extern "C" int mcomh_fastq_quality_member_lossy(const char *fastq, int L, int device, const char *order_path, const mcomh_qual_lossy_spec *spec, const char *out_path, uint64_t *n,
+                                                mcomh_qual_lossy_report *report, char *err, size_t err_cap)
+{
+	if (err && err_cap) err[0] = 0;
+	try {
+		return order_path ? fastq_member_ordered(fastq, L, device, order_path, out_path, n, err, err_cap, spec, report) : fastq_member(fastq, L, device, out_path, n, err, err_cap, spec, report);
+	} catch (...) { return -1; }
+}
+extern "C" int mcomh_qual_pack_file_lossy(const char *in_path, const char *out_path, int L, int device, const mcomh_qual_lossy_spec *spec, mcomh_qual_lossy_report *report)
+{
+	try { return qual_file(in_path, out_path, L, device, true, spec, report); } catch (...) { return -1; }
+}
+// FOLDER/qual_lossy.txt, when there, applied to the n x L rows at d_rows (mcom_fastq.hpp)
+int mcom_qual_lossy_apply_marker(const char *folder, int device, uint8_t *d_rows, size_t n, int L)
+{
+	mcomh_qual_lossy_spec spec;
+	const int have = mcomh_qual_lossy_marker(folder, &spec, nullptr, 0);
+	if (have < 0) { fprintf(stderr, "minicom verify: %s/qual_lossy.txt does not hold a lossy spec (ill8, thr:T:LO:HI, pblock:P) and a newline\n", folder); return -1; }
+	if (!have) return 0;
+	struct Ctx { mcom_ctx *ctx = nullptr; ~Ctx() { if (ctx) { (void)mcom_sync(ctx); mcom_destroy(ctx); } } } C;
+	if (hipSetDevice(device) != hipSuccess || mcom_create(&C.ctx, device, nullptr) != MCOM_OK) { C.ctx = nullptr; fprintf(stderr, "minicom verify: cannot create a context on the GPU\n"); return -1; }
+	if (mcom_qual_transform(C.ctx, d_rows, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)&spec, nullptr)) { fprintf(stderr, "minicom verify: %s\n", mcom_last_error(C.ctx)); return -1; }
+	return 0;
 }
 extern "C" int mcomh_device_copy(void *d_dst, const void *d_src, size_t bytes)
 {

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from .hip import McomError, load_library
+from .hip import McomError, QualLossyReport, QualLossySpec, load_library
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -115,6 +115,13 @@ def load_host_library():
     L.mcomh_keep_read_order.restype = i32; L.mcomh_keep_read_order.argtypes = [vp, i32]
     L.mcomh_qual_gather_rows.restype = i32; L.mcomh_qual_gather_rows.argtypes = [vp, u64, u32, u64, vp, u64, vp, u64, C.POINTER(u32)]
     L.mcomh_fastq_quality_member_ordered.restype = i32; L.mcomh_fastq_quality_member_ordered.argtypes = [cp, i32, i32, cp, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_qual_lossy_parse.restype = i32; L.mcomh_qual_lossy_parse.argtypes = [cp, C.POINTER(QualLossySpec)]
+    L.mcomh_qual_lossy_print.restype = i32; L.mcomh_qual_lossy_print.argtypes = [C.POINTER(QualLossySpec), C.c_char_p, sz]
+    L.mcomh_qual_transform.restype = i32; L.mcomh_qual_transform.argtypes = [vp, u64, u32, u64, C.POINTER(QualLossySpec), C.POINTER(QualLossyReport)]
+    L.mcomh_qual_pack_file_lossy.restype = i32; L.mcomh_qual_pack_file_lossy.argtypes = [cp, cp, i32, i32, C.POINTER(QualLossySpec), C.POINTER(QualLossyReport)]
+    L.mcomh_fastq_quality_member_lossy.restype = i32
+    L.mcomh_fastq_quality_member_lossy.argtypes = [cp, i32, i32, cp, C.POINTER(QualLossySpec), cp, C.POINTER(u64), C.POINTER(QualLossyReport), C.c_char_p, sz]
+    L.mcomh_qual_lossy_marker.restype = i32; L.mcomh_qual_lossy_marker.argtypes = [cp, C.POINTER(QualLossySpec), C.c_char_p, sz]
     L.mcomh_decompress_fastq_reordered.restype = i32; L.mcomh_decompress_fastq_reordered.argtypes = [cp, cp, C.POINTER(u64)]
     L.mcomh_decompress_fastq_reordered_gpu.restype = i32; L.mcomh_decompress_fastq_reordered_gpu.argtypes = [cp, cp, C.POINTER(u64), i32]
     L.mcomh_decompress_fastq_pe.restype = i32; L.mcomh_decompress_fastq_pe.argtypes = [cp, cp, cp, C.POINTER(u64)]
@@ -179,6 +186,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_cluster_dump_order_pe", "mcomh_decompress_order_pe", "mcomh_decompress_order_pe_gpu", "mcomh_decompress_fastq_order_pe",
                     "mcomh_decompress_fastq_order_pe_gpu", "mcomh_verify_order_pe_reads_gpu", "mcomh_verify_order_pe_parts_gpu", "mcomh_verify_order_pe_gpu",
                     "mcomh_verify_quality_member_gpu", "mcomh_verify_names_member_gpu",
+                    # lossy quality values (`minicom -b`, host/mcom_qual_lossy.cpp)
+                    "mcomh_qual_lossy_parse", "mcomh_qual_lossy_print", "mcomh_qual_transform", "mcomh_qual_pack_file_lossy", "mcomh_fastq_quality_member_lossy",
+                    "mcomh_qual_lossy_marker",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -287,13 +297,74 @@ def fastq_qualities(path: str, L: int, device: int = 0, piece_bytes: int = 0):
     return out
 
 
-def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None = None, order_path: str | None = None) -> int:
+def qual_lossy_spec(spec) -> QualLossySpec:
+    """mcomh_qual_lossy_parse: the canonical text of a lossy spec (`ill8`, `thr:T:LO:HI`, `pblock:P`) -> the
+    structure the C calls take.  A QualLossySpec passes through (a general byte map is made with QualLossySpec.from_lut).  McomError for
+    anything else: another spelling, leading zeros, trailing text, a thr that is not idempotent."""
+    if isinstance(spec, QualLossySpec):
+        return spec
+    s = QualLossySpec()
+    text = spec.encode() if isinstance(spec, str) else bytes(spec)
+    if b"\0" in text or load_host_library().mcomh_qual_lossy_parse(text, C.byref(s)):
+        raise McomError("not a lossy spec: %r (ill8, thr:T:LO:HI with 0 <= LO < T <= HI <= 93, pblock:P with 1 <= P <= 47; decimal, no leading zeros)" % (spec,))
+    return s
+
+
+def qual_lossy_text(spec) -> str:
+    """mcomh_qual_lossy_print: the canonical text of a spec (what qual_lossy.txt holds in front of its newline)"""
+    out = C.create_string_buffer(32)
+    if load_host_library().mcomh_qual_lossy_print(C.byref(qual_lossy_spec(spec)), out, 32):
+        raise McomError("qual_lossy_text: a general byte map has no text")
+    return out.value.decode()
+
+
+def qual_transform(rows, spec, device: int | None = None):
+    """The lossy transform of a quality matrix: rows, a uint8 matrix [n, L] with contiguous rows (any row stride
+    >= L), is left alone; returns (the transformed matrix [n, L], the report {"changed", "sum_abs", "sum_sq", "max_abs"}).  device=None:
+    mcomh_qual_transform, the host twin; an integer: mcom_qual_transform on that GPU -- the same bytes and the same report.  McomError
+    for a spec the transform refuses."""
+    s = qual_lossy_spec(spec)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.dtype != np.uint8 or (rows.size and rows.strides[1] != 1):
+        raise McomError("qual_transform: a uint8 matrix with contiguous rows")
+    n, L = rows.shape
+    if device is not None:
+        import torch
+        from .hip import Context
+        out, rep = Context(int(device)).qual_transform(torch.from_numpy(np.ascontiguousarray(rows)).to(f"cuda:{int(device)}"), s)
+        return out.cpu().numpy(), rep
+    out = np.array(rows, dtype=np.uint8, order="C")
+    r = QualLossyReport()
+    if load_host_library().mcomh_qual_transform(out.ctypes.data if n else None, n, L, L, C.byref(s), C.byref(r)):
+        raise McomError("qual_transform: rows of %d bytes, or a spec the transform refuses (a byte map that is not idempotent)" % L)
+    return out, r.as_dict()
+
+
+def qual_lossy_marker(folder: str):
+    """mcomh_qual_lossy_marker: the canonical spec text of FOLDER/qual_lossy.txt, None without the file; McomError when the file holds
+    anything but a canonical spec and a newline."""
+    s = QualLossySpec(); out = C.create_string_buffer(40)
+    rc = load_host_library().mcomh_qual_lossy_marker(os.fsencode(folder), C.byref(s), out, 40)
+    if rc < 0:
+        raise McomError(f"{folder}/qual_lossy.txt does not hold a lossy spec and a newline")
+    return out.value.decode() if rc else None
+
+
+def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None = None, order_path: str | None = None, lossy=None):
     """mcomh_fastq_quality_member: the quality lines of a four-line FASTQ file -> the `.mcq` member file out_path; returns the number of
     records.  device=None: the host twin (same record rules, same member); an integer: gathered and coded on that GPU.
     order_path (mcomh_fastq_quality_member_ordered): a read_order.bin; row j of the member is then record order[j]
-    of the file.  McomError, and no member, when it is not a permutation of the records."""
+    of the file.  McomError, and no member, when it is not a permutation of the records.
+    lossy (mcomh_fastq_quality_member_lossy): a lossy spec; the rows go through the transform in front of the coder
+    and the call returns (records, report) instead."""
     err = C.create_string_buffer(320)
     n = C.c_uint64()
+    if lossy is not None:
+        s = qual_lossy_spec(lossy); r = QualLossyReport()
+        if load_host_library().mcomh_fastq_quality_member_lossy(os.fsencode(fastq), int(L), -1 if device is None else int(device), None if order_path is None else os.fsencode(order_path),
+                                                                C.byref(s), os.fsencode(out_path), C.byref(n), C.byref(r), err, 320):
+            raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
+        return int(n.value), r.as_dict()
     if order_path is not None:
         if load_host_library().mcomh_fastq_quality_member_ordered(os.fsencode(fastq), int(L), -1 if device is None else int(device), os.fsencode(order_path), os.fsencode(out_path),
                                                                   C.byref(n), err, 320):

@@ -9,7 +9,15 @@ four-line FASTQ file of one read length -- the way to learn what real instrument
 cache included) and `--repeats` times measured: wall clock around the child process, median and spread (max - min).  Also reported:
 the `.rans` member and bz2 -9 of the same bytes (sizes only), the model the coder chose, whether the host twin and the GPU wrote the
 same member and whether every route gave the bytes back.  One JSON line (also written to --out).  Exit status 1 when a route fails, a
-decoded file differs from its source, or the two routes' members differ.  Nothing is retried."""
+decoded file differs from its source, or the two routes' members differ.  Nothing is retried.
+
+  python tools/qual_bench.py --rows 2000000 --len 150 --lossy ill8 pblock:2 [--repeats 3] [--dir DIR] [--out FILE]
+
+measures the lossy transform instead (`minicom -b`), per SPEC: mcom_qual_transform on GPU 0 over the matrix in HBM
+(wall clock around the synchronous call -- its fill, its launch, the 32 bytes of the report coming back and the wait -- against the byte
+model of 2 n L bytes moved), the report, and the member step `mcomz e --fastq-qual L --gpu` over a FASTQ file of the same qualities with
+and without `--lossy SPEC` (wall clock around the child process, sizes of the members, whether the host twin writes the same member
+where --host-check is given).  Median and spread (max - min) of --repeats runs after one warm-up."""
 import argparse
 import bz2
 import filecmp
@@ -50,6 +58,73 @@ def timed(cmd, stdout=None):
     return ms
 
 
+def fastq_file(path, quals):
+    """four-line records of one width (names @0000001 ..., reads of A) around the quality rows, built as one matrix"""
+    n, L = quals.shape
+    rec = np.empty((n, 2 * L + 13), np.uint8)
+    rec[:, 0] = ord("@")
+    idx = np.arange(1, n + 1)
+    for k in range(7):
+        rec[:, 7 - k] = 48 + idx // 10 ** k % 10
+    rec[:, 8] = 10; rec[:, 9:9 + L] = ord("A"); rec[:, 9 + L] = 10; rec[:, 10 + L] = ord("+"); rec[:, 11 + L] = 10
+    rec[:, 12 + L:12 + 2 * L] = quals; rec[:, 12 + 2 * L] = 10
+    with open(path, "wb") as f:
+        f.write(rec.tobytes())
+
+
+def lossy_main(a):
+    import torch
+    import minicom_amd
+    from minicom_amd import pipeline
+    work = tempfile.mkdtemp(prefix="qual_bench_", dir=a.dir)
+    try:
+        L, rows = a.L, a.rows
+        q = synth_quals(5, rows, L, a.binned)
+        fq = os.path.join(work, "q.fastq")
+        fastq_file(fq, q)
+        ctx = minicom_amd.Context(0)
+        d = torch.from_numpy(q).cuda()
+        res = {"rows": rows, "L": L, "repeats": a.repeats, "bytes_moved_model": 2 * rows * L, "specs": {}}
+
+        def member(extra, out):
+            return timed([MCOMZ, "e", "--fastq-qual", str(L)] + extra + ["--gpu", fq, out], stdout=subprocess.DEVNULL)
+        plain = os.path.join(work, "plain.mcq")
+        member([], plain)
+        t = [member([], plain) for _ in range(a.repeats)]
+        res["member_plain"] = {"bytes": os.path.getsize(plain), "ms": round(statistics.median(t), 1), "spread_ms": round(max(t) - min(t), 1)}
+        ok = True
+        for spec in a.lossy:
+            work_rows = d.clone()
+            ctx.qual_transform(work_rows, spec, in_place=True)             # warm-up
+            ms = []
+            for _ in range(max(a.repeats, 3)):
+                work_rows.copy_(d); torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                _, report = ctx.qual_transform(work_rows, spec, in_place=True)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            med = statistics.median(ms)
+            out = os.path.join(work, "lossy.mcq")
+            member(["--lossy", spec], out)
+            t = [member(["--lossy", spec], out) for _ in range(a.repeats)]
+            r = {"transform_call_ms": round(med, 3), "transform_call_spread_ms": round(max(ms) - min(ms), 3), "model_GB_per_s": round(2 * rows * L / med / 1e6, 1),
+                 "report": report, "member_bytes": os.path.getsize(out), "member_ms": round(statistics.median(t), 1), "member_spread_ms": round(max(t) - min(t), 1)}
+            if a.host_check:
+                host = os.path.join(work, "host.mcq")
+                timed([MCOMZ, "e", "--fastq-qual", str(L), "--lossy", spec, fq, host], stdout=subprocess.DEVNULL)
+                r["same_bytes_as_host"] = filecmp.cmp(out, host, shallow=False)
+                ok = ok and r["same_bytes_as_host"]
+            res["specs"][spec] = r
+        res["ok"] = ok
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return 0 if ok else 1
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -59,7 +134,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lossy", nargs="+", default=None, metavar="SPEC")
+    ap.add_argument("--host-check", action="store_true")
     a = ap.parse_args()
+    if a.lossy:
+        return lossy_main(a)
     from minicom_amd import pipeline
     work = tempfile.mkdtemp(prefix="qual_bench_", dir=a.dir)
     try:
