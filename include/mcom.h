@@ -846,6 +846,19 @@ typedef struct {
 int mcom_qual_transform(mcom_ctx *ctx, uint8_t *d_rows, uint64_t n_rows, uint32_t L, uint64_t pitch, const mcom_qual_lossy_spec *spec,
                         mcom_qual_lossy_report *h_report);
 
+/* ---- BGZF output: gzip members of 65280 bytes of text each (csrc/bgzf.hip; format, parse and host twin: DESIGN.md section 3.14) ----
+ * n bytes at d_in become a sequence of BGZF members at d_out: member k holds the bytes [65280 k, 65280 (k + 1)), only the last one is
+ * shorter; each is one DEFLATE block, dynamic Huffman where that is strictly smaller than stored.  One workgroup per member.  Device
+ * pointers at any address, work on the context's stream, synchronous.  The bytes equal those of mcomh_bgzf_encode.
+ *   mcom_bgzf_bound   n + 31 ceil(n / 65280) + 28: always enough room
+ *   mcom_bgzf_encode  flags & MCOM_BGZF_EOF appends the 28-byte empty member that ends a file (n = 0 gives that member alone).  Without
+ *                     it the call serves a piece of a longer stream: n is then expected to be a multiple of 65280, or the next piece's
+ *                     members no longer start where those of the whole text would.  MCOM_E_OVERFLOW when cap is too small (nothing
+ *                     valid in d_out)                                                                                                  */
+#define MCOM_BGZF_EOF 1
+uint64_t mcom_bgzf_bound(uint64_t n);
+int mcom_bgzf_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, int flags);
+
 /* ---- read names and '+' lines: `.mcn` members (csrc/names.hip; format and host twin: DESIGN.md section 3.10, include/mcom_host.h) ----
  * The name text of n records is 2 n lines: line 1 of a record without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at
  * most 255 bytes a line.  Names are cut into digit runs and other runs, every token coded against the same token of the record before

@@ -386,6 +386,19 @@ int mcomh_fastq_quality_member_lossy(const char *fastq, int L, int device, const
                                      uint64_t *n, mcomh_qual_lossy_report *report, char *err, size_t err_cap);
 int mcomh_qual_lossy_marker(const char *folder, mcomh_qual_lossy_spec *spec, char *text, size_t cap);
 
+/* ---- BGZF output (host/mcom_bgzf.cpp) ----
+ * The host twin of mcom_bgzf_encode (include/mcom.h): a plain loop over csrc/deflate_model.hpp, the same bytes as the device call.
+ * Any gzip reader takes the result; the member-parallel ingest (host/mcom_fastq_gz.cpp) finds the members by their BC field.
+ *   mcomh_bgzf_bound   n + 31 ceil(n / 65280) + 28
+ *   mcomh_bgzf_encode  0, -1 for bad arguments, -4 when cap is too small; flags & MCOMH_BGZF_EOF appends the empty last member
+ *   mcomh_bgzf_file    in_path -> out_path, closed with the empty member: device = -1 the twin, otherwise mcom_bgzf_encode on that GPU
+ *                      in pieces of whole blocks (an error, never the twin, when there is no such GPU).  No output file is left by a
+ *                      call that fails.                                                                                              */
+#define MCOMH_BGZF_EOF 1
+uint64_t mcomh_bgzf_bound(uint64_t n);
+int mcomh_bgzf_encode(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, int flags);
+int mcomh_bgzf_file(const char *in_path, const char *out_path, int device);
+
 /* ---- read names and '+' lines: `.mcn` members (host/mcom_names.cpp) ----
  * The host twin of mcom_name_encode / mcom_name_decode (include/mcom.h).  The name text of n records is 2 n lines: line 1 of a record
  * without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at most 255 bytes a line.  Names are cut into tokens and coded

@@ -98,6 +98,12 @@ long mcomh_test_gz_items(void);
  * out[0 .. out_cap).  0 = decoded (*in_used bytes were the member, *out_n bytes came out, CRC-32 and ISIZE checked), 1 = out is too
  * small, < 0 = truncated (-1) / not a valid member (-2).  For tests that hold it against zlib.                                        */
 int  mcomh_test_gunzip(const uint8_t *in, size_t in_n, uint8_t *out, size_t out_cap, size_t *in_used, size_t *out_n);
+/* The GPU decoders (host/mcom_decompress_gpu.cpp) bring their output down in pieces of 64 MiB; with a `.gz` path the text below one BGZF
+ * block at a piece's end is carried in front of the next piece.  The piece size in bytes (0 = the default, otherwise at least 4096) for the
+ * calls that follow: a test of a few thousand records then crosses many pieces.  The files written never depend on it.  A piece has to
+ * hold one record: the FASTQ tails refuse an archive whose records (2 L + 17 bytes, a name in place of the number up to 512 more) do not
+ * fit, so the smallest size serves reads up to about 1700 bases.                                                                     */
+int  mcomh_test_decoder_piece_bytes(size_t bytes);
 
 #ifdef __cplusplus
 }

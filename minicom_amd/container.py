@@ -361,15 +361,27 @@ def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str, loss
         f.write(member.cpu().numpy().tobytes())
 
 
-def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None) -> int:
+def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None, gzip: bool = False) -> int:
     """`.minicom` -> reads, one per line: the original order for an archive written with -p, two files (line i of both a
     pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
     integer: `.rans` and `.bwt` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
     are host code either way.  An archive with quality values (compress_fastq(quality=True)) gives FASTQ instead: four-line records
     `@<i+1>`, read, `+`, qualities -- or, for an archive that carries name.mcn (compress_fastq(names=True)), the records with their names
-    and `+` texts: the input file."""
+    and `+` texts: the input file.  gzip=True: the output file(s) are BGZF (gzip members of 65280 bytes of text
+    each) -- compressed on the GPU by the decoders' tails when `device` is given and the paths end in `.gz` (on that route the suffix
+    alone decides, with or without the keyword), otherwise the plain file is written beside the archive's members first and
+    pipeline.bgzf_file turns it into the same bytes."""
     import tempfile
     from .pipeline import decompress, decompress_fastq, decompress_pe
+    outs = [o for o in (out_path, out_path2) if o is not None]
+    if gzip and not (device is not None and all(o.endswith(".gz") for o in outs)):
+        from .pipeline import bgzf_file
+        with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as plain:
+            tmp = [os.path.join(plain, "out_%d" % k) for k in range(len(outs))]
+            n = decompress_file(path, tmp[0], tmp[1] if len(tmp) > 1 else None, threads=threads, device=device)
+            for t, o in zip(tmp, outs):
+                bgzf_file(t, o, device=device)
+        return n
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
         if kinds.get("pair_order"):                                  # seen first: its other members are those of a -p archive

@@ -205,6 +205,8 @@ def load_library():
     L.mcom_dump_read_order.restype = i32; L.mcom_dump_read_order.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
     L.mcom_verify_multiset_parts.restype = i32; L.mcom_verify_multiset_parts.argtypes = [vp, C.POINTER(VerifyParts), C.POINTER(VerifyParts), i32, C.POINTER(VerifyReport)]
     L.mcom_qual_transform.restype = i32; L.mcom_qual_transform.argtypes = [vp, vp, u64, C.c_uint32, u64, C.POINTER(QualLossySpec), C.POINTER(QualLossyReport)]
+    L.mcom_bgzf_bound.restype = u64; L.mcom_bgzf_bound.argtypes = [u64]
+    L.mcom_bgzf_encode.restype = i32; L.mcom_bgzf_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
     L.mcom_test_qual_pblock_tile_rows.restype = C.c_uint32; L.mcom_test_qual_pblock_tile_rows.argtypes = []
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
@@ -971,6 +973,19 @@ class Context:
             out = torch.empty(cap, dtype=torch.uint8, device=self.device)
         got = C.c_uint64()
         self._check(self.lib.mcom_rans_encode(self._h, self._p(raw, torch.uint8) if n else None, n, self._p(out), cap, C.byref(got), hint))
+        return out[:got.value]
+
+    def bgzf_encode(self, raw, eof=True, out=None):
+        """mcom_bgzf_encode.  raw: uint8 device tensor at any address.  Returns the BGZF members of its bytes, one
+        per 65280, as a uint8 device tensor; eof=True closes them with the empty member a file ends with.  out: a uint8 device tensor to
+        write into (its length is the room offered: McomError when it is too small) instead of a fresh one of mcom_bgzf_bound bytes."""
+        torch = _torch()
+        n = int(raw.shape[0])
+        cap = int(out.shape[0]) if out is not None else int(self.lib.mcom_bgzf_bound(n))
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        got = C.c_uint64()
+        self._check(self.lib.mcom_bgzf_encode(self._h, raw.data_ptr() if n else None, n, out.data_ptr(), cap, C.byref(got), 1 if eof else 0))
         return out[:got.value]
 
     def rans_decode(self, member, cap=None, out=None):

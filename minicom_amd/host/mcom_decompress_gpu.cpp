@@ -20,13 +20,15 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace {
 
 enum Mode { DEFAULT = 0, ORDER = 1, PE = 2 };
-const size_t PIECE_BYTES = (size_t)64 << 20;          // one page-locked buffer; two of them bound the host memory of the download
+size_t PIECE_BYTES = (size_t)64 << 20;                // one page-locked buffer; two of them bound the host memory of the download
+                                                        // (mcomh_test_decoder_piece_bytes, include/mcom_test.h, lets a test cross pieces with a few thousand records)
 
 double g_times[8];                                      // ms: read files | upload + indices + destinations | decode, wall | decode, device events |
                                                         //     download + write, wall | of that inside fwrite | whole call | unused
@@ -79,6 +81,45 @@ struct Seg {
 	mcom_decode_src src;
 	uint64_t n = 0;
 	const uint64_t *d_dest = nullptr; uint64_t dest0 = 0;
+};
+
+// An output path that ends in `.gz` is written as BGZF: the pieces of text never leave the card, their members do.
+// The whole blocks of (carry + piece) go through mcom_bgzf_encode, what is left below one block is carried in front of the next piece and
+// the last piece is closed with the empty member -- so block k of the file holds its bytes [65280 k, ...) whatever the piece size, and
+// the file equals mcomh_bgzf_encode of the plain output byte for byte.
+bool gz_path(const char *path) { const size_t n = path ? strlen(path) : 0; return n >= 3 && !strcmp(path + n - 3, ".gz"); }
+struct GzSink {
+	enum { BLOCK = 65280 };
+	Arena &A;
+	uint8_t *d_text = nullptr, *d_members = nullptr, *pin = nullptr;
+	size_t room = 0, cap = 0, carry = 0;
+	explicit GzSink(Arena &a) : A(a)
+	{
+		room = PIECE_BYTES + BLOCK; cap = (size_t)mcom_bgzf_bound(room);
+		d_text = A.alloc<uint8_t>(room); d_members = A.alloc<uint8_t>(cap);
+		void *p = nullptr;
+		if (hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"};
+		A.pinned.push_back(p); pin = (uint8_t*)p;
+	}
+	// `bytes` (at most a piece) of text on the device, the file's last ones when `last`; false when a call or the write failed
+	bool feed(const uint8_t *d_piece, size_t bytes, bool last, FILE *out)
+	{
+		if (bytes > PIECE_BYTES || carry >= BLOCK) return false;
+		if (bytes && hipMemcpy(d_text + carry, d_piece, bytes, hipMemcpyDeviceToDevice) != hipSuccess) return false;
+		if (hipDeviceSynchronize() != hipSuccess) return false;
+		const size_t have = carry + bytes, whole = last ? have : have - have % BLOCK;
+		uint64_t len = 0;
+		if (whole || last) {
+			if (mcom_bgzf_encode(A.ctx, d_text, whole, d_members, cap, &len, last ? MCOM_BGZF_EOF : 0)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); return false; }
+			if (hipMemcpy(pin, d_members, (size_t)len, hipMemcpyDeviceToHost) != hipSuccess) return false;
+		}
+		carry = have - whole;
+		if (carry && whole && (hipMemcpy(d_text, d_text + whole, carry, hipMemcpyDeviceToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) return false;   // (carry < BLOCK <= whole: the two do not overlap)
+		const double tw = now_ms();
+		const bool wrote = fwrite(pin, 1, (size_t)len, out) == len;
+		g_times[5] += now_ms() - tw;
+		return wrote;
+	}
 };
 
 void ok(mcom_ctx *ctx, int rc) { if (rc) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(ctx)); throw Refuse{"a device call failed"}; } }
@@ -342,9 +383,14 @@ int write_files(Mode mode, Arena &A, const uint8_t *table, uint64_t n_rows, uint
 	const uint64_t row = (uint64_t)L + 1, table_bytes = n_rows * row;
 	const double t0 = now_ms();
 	uint8_t *pin[2] = {nullptr, nullptr};
-	for (int b = 0; b < 2; ++b) { void *p = nullptr; if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"}; A.pinned.push_back(p); pin[b] = (uint8_t*)p; }
 	const int n_files = mode == PE ? 2 : 1;
 	const char *paths[2] = {out_path1, out_path2};
+	// everything that can be refused for want of memory is made before a file is opened: the plain route's two page-locked buffers and the
+	// .gz route's sink, one for both files of a pair
+	bool any_plain = false, any_gz = false;
+	for (int fi = 0; fi < n_files; ++fi) (gz_path(paths[fi]) ? any_gz : any_plain) = true;
+	for (int b = 0; b < 2 && any_plain; ++b) { void *p = nullptr; if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"}; A.pinned.push_back(p); pin[b] = (uint8_t*)p; }
+	std::unique_ptr<GzSink> Z(any_gz ? new GzSink(A) : nullptr);
 	bool wrote_ok = true;
 	for (int fi = 0; fi < n_files && wrote_ok; ++fi) {
 		const uint64_t first = mode == PE ? (uint64_t)fi * (uint64_t)half * row : 0, bytes = mode == PE ? (uint64_t)half * row : table_bytes;
@@ -352,6 +398,13 @@ int write_files(Mode mode, Arena &A, const uint8_t *table, uint64_t n_rows, uint
 		if (!out) { wrote_ok = false; break; }
 		const uint64_t pieces = (bytes + PIECE_BYTES - 1) / PIECE_BYTES;
 		auto piece_bytes = [&](uint64_t i) { const uint64_t at = i * PIECE_BYTES; return (size_t)(bytes - at < PIECE_BYTES ? bytes - at : PIECE_BYTES); };
+		if (gz_path(paths[fi])) {                                              // each file of a pair starts afresh
+			Z->carry = 0;
+			for (uint64_t i = 0; i < pieces && wrote_ok; ++i) wrote_ok = Z->feed(table + first + i * PIECE_BYTES, piece_bytes(i), i + 1 == pieces, out);
+			if (!pieces && wrote_ok) wrote_ok = Z->feed(nullptr, 0, true, out);
+			if (fclose(out) != 0) wrote_ok = false;
+			continue;
+		}
 		if (pieces && hipMemcpyAsync(pin[0], table + first, piece_bytes(0), hipMemcpyDeviceToHost, nullptr) != hipSuccess) wrote_ok = false;
 		for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
 			if (hipStreamSynchronize(nullptr) != hipSuccess) { wrote_ok = false; break; }
@@ -430,6 +483,7 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	const uint64_t rec_max = 2 * (uint64_t)L + 17, per_piece = PIECE_BYTES / rec_max;
 	// where every piece begins: a fixed number of records without names; with names the most records whose bytes fit a piece (bisection
 	// in the offset array: record r of a piece from `first` ends at (2 L + 4)(r + 1 - first) + off[r + 1] - off[first])
+	if (!named && !per_piece) throw Refuse{"a record does not fit a piece"};
 	std::vector<uint64_t> piece_at(1, 0);
 	while (piece_at.back() < n_rows) {
 		const uint64_t first = piece_at.back();
@@ -453,10 +507,27 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	uint8_t *const *pin = E.pin, *const *d_out = E.d_out;
 	struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } arrived;   // piece i is in pin[i & 1]
 	for (int b = 0; b < 2; ++b) if (hipEventCreateWithFlags(&arrived.e[b], hipEventDisableTiming) != hipSuccess) throw Refuse{"no events"};
+	std::unique_ptr<GzSink> sink(gz_path(out_path) ? new GzSink(A) : nullptr);     // made before the file is opened: a refusal leaves no file
 	FILE *out = fopen(out_path, "wb");
 	if (!out) return -1;
 	bool wrote_ok = true;
 	uint64_t bytes[2] = {0, 0};
+	if (sink) {
+		GzSink &Z = *sink;
+		for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
+			const uint64_t first = piece_at[i], count = piece_at[i + 1] - first;
+			const int rc = named ? mcom_fastq_emit_named(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, d_names, names_bytes, d_off + first, count,
+			                                             (uint32_t)L, d_out[0], &bytes[0])
+			                     : mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, first, count, (uint32_t)L, d_out[0], &bytes[0]);
+			wrote_ok = !rc && bytes[0] <= PIECE_BYTES && Z.feed(d_out[0], (size_t)bytes[0], i + 1 == pieces, out);
+		}
+		if (!pieces && wrote_ok) wrote_ok = Z.feed(nullptr, 0, true, out);
+		if (fclose(out) != 0) wrote_ok = false;
+		if (!wrote_ok) { remove(out_path); return -1; }
+		g_times[4] = now_ms() - t0;
+		if (n_out) *n_out = n_rows;
+		return 0;
+	}
 	for (uint64_t i = 0; i <= pieces && wrote_ok; ++i) {
 		if (i < pieces) {
 			const uint64_t first = piece_at[i], count = piece_at[i + 1] - first;
@@ -748,6 +819,12 @@ extern "C" int mcomh_verify_records_gpu(const char *folder, int mode, const char
 	}
 	memset(rep, 0, sizeof(*rep));
 	try { return verify_records(folder, mode, fastq1, fastq2, device, rep); } catch (...) { return -1; }
+}
+extern "C" int mcomh_test_decoder_piece_bytes(size_t bytes)
+{
+	if (bytes && bytes < 4096) return -1;
+	PIECE_BYTES = bytes ? bytes : (size_t)64 << 20;
+	return 0;
 }
 extern "C" void mcomh_decompress_gpu_times(double *ms8) { if (ms8) memcpy(ms8, g_times, sizeof(g_times)); }
 extern "C" int mcomh_verify_gpu(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)

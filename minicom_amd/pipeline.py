@@ -89,6 +89,9 @@ def load_host_library():
     L.mcomh_rans_estimate.restype = i32; L.mcomh_rans_estimate.argtypes = [vp, u64, C.POINTER(u64)]
     L.mcomh_rans_encode.restype = i32; L.mcomh_rans_encode.argtypes = [vp, u64, vp, u64, C.POINTER(u64), i32]
     L.mcomh_rans_decode.restype = i32; L.mcomh_rans_decode.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcomh_bgzf_bound.restype = u64; L.mcomh_bgzf_bound.argtypes = [u64]
+    L.mcomh_bgzf_encode.restype = i32; L.mcomh_bgzf_encode.argtypes = [vp, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcomh_bgzf_file.restype = i32; L.mcomh_bgzf_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_pack_file.restype = i32; L.mcomh_entropy_pack_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_unpack_file.restype = i32; L.mcomh_entropy_unpack_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_times.restype = None; L.mcomh_entropy_times.argtypes = [C.POINTER(C.c_double)]
@@ -189,6 +192,8 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     # lossy quality values (`minicom -b`, host/mcom_qual_lossy.cpp)
                     "mcomh_qual_lossy_parse", "mcomh_qual_lossy_print", "mcomh_qual_transform", "mcomh_qual_pack_file_lossy", "mcomh_fastq_quality_member_lossy",
                     "mcomh_qual_lossy_marker",
+                    # BGZF output (`minicom -d -z`, host/mcom_bgzf.cpp)
+                    "mcomh_bgzf_bound", "mcomh_bgzf_encode", "mcomh_bgzf_file",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -258,6 +263,34 @@ def rans_encode(data: bytes, model: int | None = None, stride: int = 1) -> bytes
     if rc:
         raise McomError(f"rans_encode: error {rc}")
     return out.raw[:got.value]
+
+
+def bgzf_encode(data: bytes, device: int | None = None, eof: bool = True) -> bytes:
+    """The bytes of `data` as BGZF members of 65280 bytes of text each, closed with the empty member a file ends
+    with unless eof=False.  device None: mcomh_bgzf_encode, the host twin; an integer: mcom_bgzf_encode on that GPU -- the same bytes."""
+    n = len(data)
+    if device is not None:
+        import numpy as np
+        import torch
+        from .hip import Context
+        raw = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to(f"cuda:{int(device)}") if n else torch.empty(0, dtype=torch.uint8, device=f"cuda:{int(device)}")
+        return bytes(Context(int(device)).bgzf_encode(raw, eof=eof).cpu().numpy())
+    lib = load_host_library()
+    cap = int(lib.mcomh_bgzf_bound(n))
+    out = C.create_string_buffer(cap)
+    got = C.c_uint64()
+    src = (C.c_char * n).from_buffer_copy(data) if n else None
+    rc = lib.mcomh_bgzf_encode(src, n, out, cap, C.byref(got), 1 if eof else 0)
+    if rc:
+        raise McomError(f"bgzf_encode: error {rc}")
+    return out.raw[:got.value]
+
+
+def bgzf_file(in_path: str, out_path: str, device: int | None = None) -> None:
+    """mcomh_bgzf_file: a file -> the BGZF file of its bytes (what `mcomz z` runs).  device None: the host twin; an integer: that GPU (an
+    error, never the twin, when there is no such GPU).  No output file is left by a call that fails."""
+    if load_host_library().mcomh_bgzf_file(os.fsencode(in_path), os.fsencode(out_path), -1 if device is None else int(device)):
+        raise McomError(f"cannot write {in_path} as BGZF to {out_path}" + ("" if device is None else f" on GPU {device}"))
 
 
 def rans_decode(member: bytes, cap: int | None = None) -> bytes:
