@@ -859,6 +859,30 @@ int mcom_qual_transform(mcom_ctx *ctx, uint8_t *d_rows, uint64_t n_rows, uint32_
 uint64_t mcom_bgzf_bound(uint64_t n);
 int mcom_bgzf_encode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, int flags);
 
+/* ---- gzip members inflated on the GPU (csrc/inflate.hip; model and host twin: DESIGN.md section 3.15) ----
+ * A member is the DEFLATE payload of one gzip member (header and trailer stripped) with the ISIZE and CRC-32 of its trailer and the
+ * place of its text.
+ *   mcom_gzip_walk     plain host code: the members of a BGZF buffer, header by header -- gzip headers that carry the `BC` subfield,
+ *                      with further FEXTRA subfields, FNAME, FCOMMENT and FHCRC skipped as RFC 1952 lays them out.  out_off is the
+ *                      running sum of the ISIZEs.  h_members NULL: counts only (cap is ignored); otherwise the walk ends quietly
+ *                      when cap members are filled.  MCOM_E_ARG at the first member without `BC`, with reserved flag bits, or of a
+ *                      size that leaves the buffer or is below header plus trailer.  In every case *n_members, *text_bytes and
+ *                      *used describe the whole members in front of the stop: a caller walks a file piece by piece from *used.
+ *   mcom_gzip_inflate  nothing BGZF-specific: members of any size, distances up to 32768, one workgroup per member.  Device pointers
+ *                      at any address, work on the context's stream, synchronous.  MCOM_OK when the kernel ran: d_status[m] is one
+ *                      of MCOM_GZIP_*, *h_bad the number of members that are not OK and *h_first_bad the smallest of them
+ *                      (n_members: none).  A member that is not OK may leave anything inside its own slot [out_off, out_off +
+ *                      isize) and writes nothing outside it.  MCOM_E_ARG, and no launch, when a payload leaves d_in, a slot leaves
+ *                      d_out, or slots overlap or are out of order (checked on a host copy of the table).  n_members = 0 is legal.
+ *                      The bytes and statuses equal those of mcomh_gzip_inflate.                                                      */
+typedef struct { uint64_t in_off, in_bytes;   /* the DEFLATE payload inside d_in (header and trailer stripped) */
+                 uint64_t out_off;            /* where its text goes inside d_out */
+                 uint32_t isize, crc; } mcom_gzip_member;
+enum { MCOM_GZIP_OK = 0, MCOM_GZIP_CORRUPT = 1, MCOM_GZIP_TRUNCATED = 2, MCOM_GZIP_ROOM = 3, MCOM_GZIP_CHECK = 4 /* CRC-32 or ISIZE differ */ };
+int mcom_gzip_walk(const uint8_t *h_file, uint64_t bytes, mcom_gzip_member *h_members, uint64_t cap, uint64_t *n_members, uint64_t *text_bytes, uint64_t *used);
+int mcom_gzip_inflate(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_bytes, const mcom_gzip_member *d_members, uint64_t n_members,
+                      uint8_t *d_out, uint64_t out_bytes, uint8_t *d_status, uint64_t *h_bad, uint64_t *h_first_bad);
+
 /* ---- read names and '+' lines: `.mcn` members (csrc/names.hip; format and host twin: DESIGN.md section 3.10, include/mcom_host.h) ----
  * The name text of n records is 2 n lines: line 1 of a record without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at
  * most 255 bytes a line.  Names are cut into digit runs and other runs, every token coded against the same token of the record before

@@ -399,6 +399,29 @@ uint64_t mcomh_bgzf_bound(uint64_t n);
 int mcomh_bgzf_encode(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, int flags);
 int mcomh_bgzf_file(const char *in_path, const char *out_path, int device);
 
+/* ---- BGZF input inflated on the GPU (host/mcom_gzip_gpu.cpp) ----
+ * The host twin of mcom_gzip_inflate (include/mcom.h): a plain loop over csrc/inflate_model.hpp, the same bytes and the same status per
+ * member as the device call.  mcomh_gzip_member has the layout of mcom_gzip_member, the statuses are MCOM_GZIP_* (0 OK, 1 corrupt,
+ * 2 truncated, 3 room, 4 CRC-32 or ISIZE differ).
+ *   mcomh_gzip_inflate_members  the twin of the device call over a table of members: 0 when the loop ran (status[m], *bad, *first_bad
+ *                               as there; status may be NULL), -1 for a table whose payloads or slots leave the buffers or whose slots
+ *                               overlap or are out of order (nothing is written)
+ *   mcomh_gzip_inflate          a BGZF buffer to its text: 0, -1 when the buffer is not BGZF members to its end, -4 when cap is too
+ *                               small (*out_len = the room needed), otherwise the status (1 .. 4) of the first member that is not OK
+ *   mcomh_gunzip_file           a BGZF file to its text (what `mcomz u` runs): device = -1 the twin, otherwise runs of whole members are
+ *                               uploaded, inflated by mcom_gzip_inflate on that GPU and the text brought down (an error, never the twin,
+ *                               when there is no such GPU).  -1 and no output file when a member is refused or the file is not BGZF
+ *                               members (of at most 65536 bytes of text each) to its end.
+ * The FASTQ passes mcomh_fastq_qualities_to_device and mcomh_fastq_names_to_device take a file whose first member carries the `BC` field
+ * by this route: the members go up compressed and are inflated on the card.  The moment anything is off -- a member without `BC`, one the
+ * device refuses, a walk that leaves the file, a record the kernels flag -- the file is started again from its beginning through zlib,
+ * which words the error if there is one: what the two calls return does not depend on the route.                                      */
+typedef struct { uint64_t in_off, in_bytes, out_off; uint32_t isize, crc; } mcomh_gzip_member;
+int mcomh_gzip_inflate_members(const uint8_t *in, uint64_t in_bytes, const mcomh_gzip_member *members, uint64_t n_members,
+                               uint8_t *out, uint64_t out_bytes, uint8_t *status, uint64_t *bad, uint64_t *first_bad);
+int mcomh_gzip_inflate(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int mcomh_gunzip_file(const char *in_path, const char *out_path, int device);
+
 /* ---- read names and '+' lines: `.mcn` members (host/mcom_names.cpp) ----
  * The host twin of mcom_name_encode / mcom_name_decode (include/mcom.h).  The name text of n records is 2 n lines: line 1 of a record
  * without its '@', '\n', line 3 without its '+', '\n'; any byte but '\n', at most 255 bytes a line.  Names are cut into tokens and coded

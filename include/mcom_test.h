@@ -104,6 +104,9 @@ int  mcomh_test_gunzip(const uint8_t *in, size_t in_n, uint8_t *out, size_t out_
  * hold one record: the FASTQ tails refuse an archive whose records (2 L + 17 bytes, a name in place of the number up to 512 more) do not
  * fit, so the smallest size serves reads up to about 1700 bases.                                                                     */
 int  mcomh_test_decoder_piece_bytes(size_t bytes);
+/* The FASTQ passes over a BGZF file inflate its members on the card (host/mcom_gzip_gpu.cpp): members inflated on the device by the last
+ * call of mcomh_fastq_qualities_to_device or mcomh_fastq_names_to_device, 0 when zlib's reader took the file.                         */
+long mcomh_test_gz_device_members(void);
 
 #ifdef __cplusplus
 }

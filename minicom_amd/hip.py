@@ -65,6 +65,14 @@ class QualLossyReport(C.Structure):
         return {"changed": int(self.changed), "sum_abs": int(self.sum_abs), "sum_sq": int(self.sum_sq), "max_abs": int(self.max_abs)}
 
 
+def _gzip_member_dtype():
+    import numpy as np
+    return np.dtype([("in_off", "<u8"), ("in_bytes", "<u8"), ("out_off", "<u8"), ("isize", "<u4"), ("crc", "<u4")])
+
+
+GZIP_MEMBER_DTYPE = _gzip_member_dtype()     # mcom_gzip_member of include/mcom.h
+
+
 def rans_hint(model: int, stride: int = 1) -> int:
     """MCOM_RANS_HINT of include/mcom.h"""
     return 0x100 | (model << 4) | stride
@@ -207,6 +215,8 @@ def load_library():
     L.mcom_qual_transform.restype = i32; L.mcom_qual_transform.argtypes = [vp, vp, u64, C.c_uint32, u64, C.POINTER(QualLossySpec), C.POINTER(QualLossyReport)]
     L.mcom_bgzf_bound.restype = u64; L.mcom_bgzf_bound.argtypes = [u64]
     L.mcom_bgzf_encode.restype = i32; L.mcom_bgzf_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
+    L.mcom_gzip_walk.restype = i32; L.mcom_gzip_walk.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_gzip_inflate.restype = i32; L.mcom_gzip_inflate.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_test_qual_pblock_tile_rows.restype = C.c_uint32; L.mcom_test_qual_pblock_tile_rows.argtypes = []
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
@@ -987,6 +997,34 @@ class Context:
         got = C.c_uint64()
         self._check(self.lib.mcom_bgzf_encode(self._h, raw.data_ptr() if n else None, n, out.data_ptr(), cap, C.byref(got), 1 if eof else 0))
         return out[:got.value]
+
+    def gzip_inflate(self, members_tensor, table, out=None):
+        """mcom_gzip_inflate (DESIGN.md section 3.15).  members_tensor: uint8 device tensor at any address that holds the DEFLATE payloads;
+        table: numpy array of GZIP_MEMBER_DTYPE (what pipeline.gzip_walk returns), or a uint8 device tensor of the same bytes.  out: a
+        uint8 device tensor to inflate into (its length is the room offered) instead of a fresh one that ends with the last slot.
+        Returns (text, statuses): two uint8 device tensors, the statuses MCOM_GZIP_* per member.  McomError for a table whose payloads or
+        slots leave the buffers or whose slots overlap or are out of order."""
+        torch = _torch()
+        import numpy as np
+        if isinstance(table, np.ndarray):
+            tab = np.ascontiguousarray(table, dtype=GZIP_MEMBER_DTYPE)
+            n = int(tab.shape[0])
+            room = int((tab["out_off"] + tab["isize"]).max()) if n else 0
+            d_tab = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy()).to(self.device) if n else torch.empty(0, dtype=torch.uint8, device=self.device)
+        else:
+            d_tab = table
+            n = int(d_tab.shape[0]) // GZIP_MEMBER_DTYPE.itemsize
+            room = None
+        if out is None:
+            if room is None:
+                raise McomError("gzip_inflate: a table on the device needs `out`")
+            out = torch.empty(room, dtype=torch.uint8, device=self.device)
+        status = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        bad, first = C.c_uint64(), C.c_uint64()
+        nin, nout = int(members_tensor.shape[0]), int(out.shape[0])
+        self._check(self.lib.mcom_gzip_inflate(self._h, members_tensor.data_ptr() if nin else None, nin, d_tab.data_ptr() if n else None, n,
+                                               out.data_ptr() if nout else None, nout, status.data_ptr(), C.byref(bad), C.byref(first)))
+        return out, status[:n]
 
     def rans_decode(self, member, cap=None, out=None):
         """mcom_rans_decode.  member: uint8 device tensor.  Returns the raw bytes as a uint8 device tensor; McomError for a member that is

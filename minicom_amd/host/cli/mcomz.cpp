@@ -26,6 +26,8 @@
 // coder: --mate has no meaning there).  d without --mate refuses a kind-2 member.
 // mcomz z [--gpu] IN OUT.gz: IN as a BGZF file (gzip members of 65280 bytes of text each and the empty last member, DESIGN.md section
 // 3.14) -- mcom_bgzf_encode with --gpu, its host twin without, the same file either way.  What `minicom -d -z` runs without -G.
+// mcomz u [--gpu] IN.gz OUT: the inverse of z, a BGZF file to its text -- mcom_gzip_inflate with --gpu, its host
+// twin without.  Exit status 1 and no OUT when a member is refused or IN.gz is not BGZF members to its end.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +61,16 @@ int main(int argc, char **argv)
 		}
 		return 0;
 	}
+	if (argc > 1 && !strcmp(argv[1], "u")) {
+		const bool u_gpu = argc == 5 && !strcmp(argv[2], "--gpu");
+		if (argc != (u_gpu ? 5 : 4)) { fprintf(stderr, "usage: mcomz u [--gpu] IN.gz OUT\n"); return 1; }
+		const char *u_in = argv[argc - 2], *u_out = argv[argc - 1];
+		if (mcomh_gunzip_file(u_in, u_out, u_gpu ? 0 : -1)) {
+			fprintf(stderr, "mcomz: %s is not a BGZF file of intact members, or %s cannot be written%s\n", u_in, u_out, u_gpu ? " (or the GPU route is not available)" : "");
+			return 1;
+		}
+		return 0;
+	}
 	bool gpu = false, bwt = false, names = false, fastq_names = false;
 	int at = 2, qual_L = 0, fastq_L = 0;
 	const char *order_path = nullptr, *mate_path = nullptr, *lossy_text = nullptr;
@@ -75,7 +87,7 @@ int main(int argc, char **argv)
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (lossy_text && !fastq_L && !qual_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--lossy SPEC] [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--lossy SPEC] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n       mcomz z [--gpu] IN OUT.gz\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (lossy_text && !fastq_L && !qual_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--lossy SPEC] [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--lossy SPEC] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n       mcomz z [--gpu] IN OUT.gz\n       mcomz u [--gpu] IN.gz OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;

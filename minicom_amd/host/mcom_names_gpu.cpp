@@ -5,12 +5,15 @@
 // mcomh_fastq_qualities_to_device (host/mcom_qual_gpu.cpp): the next piece is read while one travels, the unfinished record of a piece
 // is carried in front of the next; on the card mcom_decode_line_index finds the lines and mcom_fastq_name_text checks every record and
 // gathers its two lines.  This is a pass of its own over the file: `minicom -Q -N` reads the file once for qual.mcq and once for name.mcn.
+// A BGZF file goes up compressed and is inflated on the card (mcom_gz_device_route, host/mcom_gzip_gpu.cpp);
+// whatever is off there starts the file again through zlib's reader.
 // mcomh_fastq_name_member: that and mcom_name_encode; device = -1 a host twin of the record rules and mcomh_name_encode.
 // The _mate forms: the same drivers with a second name text, the mate, beside the first -- mcom[h]_name_encode_mate
 // and mcom[h]_name_decode_mate stand where the calls without a mate stood.
 // mcomh_verify_names_gpu: name.mcn decoded on the device against the file's name text, record against record (mcom_name_compare).
 #include "../../include/mcom_host.h"
 #include "../../include/mcom.h"
+#include "mcom_gzip_gpu.hpp"
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 #include <cstdio>
@@ -98,9 +101,6 @@ int names_to_device(const char *path, int device, size_t piece_bytes, uint8_t **
 	if (!J.f) return fail(err, err_cap, "cannot open the file");
 	if (mcom_create(&J.ctx, device, nullptr) != MCOM_OK) { J.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
 	if (hipStreamCreate(&J.copy) != hipSuccess) return fail(err, err_cap, "no stream");
-	for (int k = 0; k < 2; ++k)
-		if (hipHostMalloc((void**)&J.pin[k], piece + 1, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&J.d_text[k], piece + 16) != hipSuccess ||
-		    hipEventCreateWithFlags(&J.ev[k], hipEventDisableTiming) != hipSuccess) return fail(err, err_cap, "no room for the pieces");
 	if (hipMalloc((void**)&J.d_flag, 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
 	size_t cap_bytes = 0, n = 0, cap_lines = 0; uint64_t used = 0;
 	auto room_for = [&](uint64_t bytes) {                                  // the text grows by doubling: its length is not known in advance
@@ -130,6 +130,34 @@ int names_to_device(const char *path, int device, size_t piece_bytes, uint8_t **
 		const uint8_t *p = buf, *const e = buf + len;
 		while (p < e) { const uint8_t *q = (const uint8_t*)memchr(p, '\n', (size_t)(e - p)); if (!q) break; p = q + 1; if ((++lines & 3) == 0) { bytes = (size_t)(p - buf); records = lines / 4; } }
 	};
+	// A BGZF file goes up compressed and is inflated on the card (mcom_gzip_gpu.cpp): the same kernels over the same
+	// records.  Whatever is off there -- also a record the kernel flags -- sends the file to zlib's reader below, from its beginning.
+	size_t cap_off = 0;
+	const bool on_device = mcom_gz_device_route(path, J.ctx, piece, [&](const uint8_t *d_text, uint64_t bytes, uint64_t records, const uint64_t *d_line_start) {
+		if (n + records >= ((size_t)1 << 32) || !room_for(used + bytes)) return false;
+		if (records + 1 > cap_off) {
+			if (J.d_piece_off) (void)hipFree(J.d_piece_off);
+			J.d_piece_off = nullptr; cap_off = 0;
+			if (hipMalloc((void**)&J.d_piece_off, (records + 1) * 8 + 16) != hipSuccess) return false;
+			cap_off = records + 1;
+		}
+		const uint32_t init[4] = {0, 0xFFFFFFFFu, 0, 0};
+		uint32_t fl[4]; uint64_t got_bytes = 0;
+		if (hipMemcpy(J.d_flag, init, 16, hipMemcpyHostToDevice) != hipSuccess ||
+		    mcom_fastq_name_text(J.ctx, d_text, bytes, d_line_start, n, records, J.d_names + used, cap_bytes - used, &got_bytes, J.d_piece_off, J.d_flag) ||
+		    hipMemcpy(fl, J.d_flag, 16, hipMemcpyDeviceToHost) != hipSuccess || fl[0] || fl[2]) return false;
+		used += got_bytes; n += records;
+		return true;
+	});
+	if (!on_device) {
+		n = 0; used = 0;
+		if (J.d_piece_off) (void)hipFree(J.d_piece_off);              // (the zlib route sizes it with its line index)
+		J.d_piece_off = nullptr;
+	}
+	auto zlib_route = [&]() -> int {
+	for (int k = 0; k < 2; ++k)
+		if (hipHostMalloc((void**)&J.pin[k], piece + 1, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&J.d_text[k], piece + 16) != hipSuccess ||
+		    hipEventCreateWithFlags(&J.ev[k], hipEventDisableTiming) != hipSuccess) return fail(err, err_cap, "no room for the pieces");
 	size_t len = 0; bool eof = false;
 	if (!fill(J.pin[0], 0, len, eof)) return fail(err, err_cap, "cannot read the file (a damaged gzip stream?)");
 	for (int k = 0; ; k ^= 1) {
@@ -169,6 +197,9 @@ int names_to_device(const char *path, int device, size_t piece_bytes, uint8_t **
 		if (eof) break;
 		len = next_len; eof = next_eof;
 	}
+	return 0;
+	};
+	if (!on_device) { const int rc = zlib_route(); if (rc) return rc; }
 	if (!room_for(1)) return fail(err, err_cap, "no room on the card");
 	*d_names_out = J.d_names; J.d_names = nullptr;
 	*bytes_out = used; *n_out = n;

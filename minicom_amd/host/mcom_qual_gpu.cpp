@@ -6,12 +6,15 @@
 // next piece: the host counts the piece's newlines for that (four lines are a record), nothing else is parsed on the host.  On the
 // card mcom_decode_line_index finds the lines and mcom_fastq_quality_rows checks every record and gathers its quality line.  A file
 // the kernel flags is an error that names the first bad record; it is not handed to another parser.
+// A BGZF file is not inflated on the host at all: its members go up compressed and mcom_gz_device_route (mcom_gzip_gpu.cpp, DESIGN.md section
+// 3.15) inflates them on the card in front of the same two kernels; whatever is off there starts the file again through the route above.
 // mcomh_verify_quality_gpu: qual.mcq decoded by mcom_qual_decode, the file's rows as above, mcom_verify_ordered over both.
 // `minicom -b SPEC`: the `_lossy` file calls send the rows through mcom_qual_transform (device -1: its host twin,
 // host/mcom_qual_lossy.cpp) in front of the coder, and the verifiers send the file's rows through it when the folder holds qual_lossy.txt.
 #include "../../include/mcom_host.h"
 #include "../../include/mcom.h"
 #include "mcom_fastq.hpp"
+#include "mcom_gzip_gpu.hpp"
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 #include <chrono>
@@ -80,9 +83,6 @@ int qualities(const char *path, int device, int L, size_t piece_bytes, uint8_t *
 	if (!J.f) return fail(err, err_cap, "cannot open the file");
 	if (mcom_create(&J.ctx, device, nullptr) != MCOM_OK) { J.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
 	if (hipStreamCreate(&J.copy) != hipSuccess) return fail(err, err_cap, "no stream");
-	for (int k = 0; k < 2; ++k)
-		if (hipHostMalloc((void**)&J.pin[k], piece + 1, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&J.d_text[k], piece + 16) != hipSuccess ||
-		    hipEventCreateWithFlags(&J.ev[k], hipEventDisableTiming) != hipSuccess) return fail(err, err_cap, "no room for the pieces");
 	if (hipMalloc((void**)&J.d_flag, 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
 	size_t cap_rows = 0, n = 0, cap_lines = 0;
 	auto room_for = [&](size_t rows) {                                     // the table grows by doubling: the number of records is not known in advance
@@ -114,6 +114,23 @@ int qualities(const char *path, int device, int L, size_t piece_bytes, uint8_t *
 		const uint8_t *p = buf, *const e = buf + len;
 		while (p < e) { const uint8_t *q = (const uint8_t*)memchr(p, '\n', (size_t)(e - p)); if (!q) break; p = q + 1; if ((++lines & 3) == 0) { bytes = (size_t)(p - buf); records = lines / 4; } }
 	};
+	// A BGZF file goes up compressed and is inflated on the card (mcom_gzip_gpu.cpp): the same kernels over the same
+	// records.  Whatever is off there -- also a record the kernel flags -- sends the file to zlib's reader below, from its beginning.
+	const bool on_device = mcom_gz_device_route(path, J.ctx, piece, [&](const uint8_t *d_text, uint64_t bytes, uint64_t records, const uint64_t *d_line_start) {
+		if (n + records >= ((size_t)1 << 32) || !room_for(n + records)) return false;
+		const uint32_t init[4] = {0, 0xFFFFFFFFu, 0, 0};
+		uint32_t fl[4];
+		if (hipMemcpy(J.d_flag, init, 16, hipMemcpyHostToDevice) != hipSuccess ||
+		    mcom_fastq_quality_rows(J.ctx, d_text, bytes, d_line_start, n, records, (uint32_t)L, J.d_rows, (uint64_t)L, J.d_flag) ||
+		    hipMemcpy(fl, J.d_flag, 16, hipMemcpyDeviceToHost) != hipSuccess || fl[0] || fl[2]) return false;
+		n += records;
+		return true;
+	});
+	if (!on_device) n = 0;
+	auto zlib_route = [&]() -> int {
+	for (int k = 0; k < 2; ++k)
+		if (hipHostMalloc((void**)&J.pin[k], piece + 1, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&J.d_text[k], piece + 16) != hipSuccess ||
+		    hipEventCreateWithFlags(&J.ev[k], hipEventDisableTiming) != hipSuccess) return fail(err, err_cap, "no room for the pieces");
 	size_t len = 0; bool eof = false;
 	if (!fill(J.pin[0], 0, len, eof)) return fail(err, err_cap, "cannot read the file (a damaged gzip stream?)");
 	for (int k = 0; ; k ^= 1) {
@@ -156,6 +173,9 @@ int qualities(const char *path, int device, int L, size_t piece_bytes, uint8_t *
 		if (eof) break;
 		len = next_len; eof = next_eof;
 	}
+	return 0;
+	};
+	if (!on_device) { const int rc = zlib_route(); if (rc) return rc; }
 	if (!n && !room_for(1)) return fail(err, err_cap, "no room on the card");
 	*d_rows_out = J.d_rows; J.d_rows = nullptr;
 	*n_out = n;

@@ -92,6 +92,9 @@ def load_host_library():
     L.mcomh_bgzf_bound.restype = u64; L.mcomh_bgzf_bound.argtypes = [u64]
     L.mcomh_bgzf_encode.restype = i32; L.mcomh_bgzf_encode.argtypes = [vp, u64, vp, u64, C.POINTER(u64), i32]
     L.mcomh_bgzf_file.restype = i32; L.mcomh_bgzf_file.argtypes = [cp, cp, i32]
+    L.mcomh_gzip_inflate_members.restype = i32; L.mcomh_gzip_inflate_members.argtypes = [vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.mcomh_gzip_inflate.restype = i32; L.mcomh_gzip_inflate.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
+    L.mcomh_gunzip_file.restype = i32; L.mcomh_gunzip_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_pack_file.restype = i32; L.mcomh_entropy_pack_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_unpack_file.restype = i32; L.mcomh_entropy_unpack_file.argtypes = [cp, cp, i32]
     L.mcomh_entropy_times.restype = None; L.mcomh_entropy_times.argtypes = [C.POINTER(C.c_double)]
@@ -194,6 +197,8 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_qual_lossy_marker",
                     # BGZF output (`minicom -d -z`, host/mcom_bgzf.cpp)
                     "mcomh_bgzf_bound", "mcomh_bgzf_encode", "mcomh_bgzf_file",
+                    # BGZF input inflated on the GPU (host/mcom_gzip_gpu.cpp)
+                    "mcomh_gzip_inflate_members", "mcomh_gzip_inflate", "mcomh_gunzip_file",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -291,6 +296,68 @@ def bgzf_file(in_path: str, out_path: str, device: int | None = None) -> None:
     error, never the twin, when there is no such GPU).  No output file is left by a call that fails."""
     if load_host_library().mcomh_bgzf_file(os.fsencode(in_path), os.fsencode(out_path), -1 if device is None else int(device)):
         raise McomError(f"cannot write {in_path} as BGZF to {out_path}" + ("" if device is None else f" on GPU {device}"))
+
+
+def gzip_walk(data: bytes):
+    """mcom_gzip_walk over a BGZF buffer: (table, text_bytes, used, ok).  table: numpy array of hip.GZIP_MEMBER_DTYPE with the whole
+    members in front of the first stop, text_bytes the sum of their ISIZEs, used the bytes they take; ok False when the walk stopped at
+    a member without a `BC` field, with reserved flag bits or of a size that leaves the buffer."""
+    import numpy as np
+    from .hip import GZIP_MEMBER_DTYPE, load_library
+    lib = load_library()
+    n = len(data)
+    src = (C.c_char * n).from_buffer_copy(data) if n else None
+    cnt, text, used = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.mcom_gzip_walk(src, n, None, 0, C.byref(cnt), C.byref(text), C.byref(used))
+    tab = np.zeros(cnt.value, dtype=GZIP_MEMBER_DTYPE)
+    rc = lib.mcom_gzip_walk(src, n, tab.ctypes.data if cnt.value else None, cnt.value, C.byref(cnt), C.byref(text), C.byref(used)) if cnt.value else \
+        lib.mcom_gzip_walk(src, n, None, 0, C.byref(cnt), C.byref(text), C.byref(used))
+    return tab[:cnt.value], int(text.value), int(used.value), rc == 0 and used.value == n
+
+
+def gzip_inflate_members(data: bytes, table, out_bytes: int | None = None, device: int | None = None, fill: int = 0):
+    """The members `table` (hip.GZIP_MEMBER_DTYPE) of `data` into a buffer of out_bytes (default: the end of the last slot) that starts
+    out filled with `fill`: (buffer, statuses), both bytes.  device None: mcomh_gzip_inflate_members, the host twin; an integer:
+    mcom_gzip_inflate on that GPU -- the same bytes in every slot of a member that is OK and the same statuses."""
+    import numpy as np
+    from .hip import GZIP_MEMBER_DTYPE
+    tab = np.ascontiguousarray(table, dtype=GZIP_MEMBER_DTYPE)
+    n, nin = int(tab.shape[0]), len(data)
+    if out_bytes is None:
+        out_bytes = int((tab["out_off"] + tab["isize"]).max()) if n else 0
+    if device is not None:
+        import torch
+        from .hip import Context
+        dev = f"cuda:{int(device)}"
+        raw = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to(dev) if nin else torch.empty(0, dtype=torch.uint8, device=dev)
+        out = torch.full((out_bytes,), fill, dtype=torch.uint8, device=dev)
+        out, status = Context(int(device)).gzip_inflate(raw, tab, out=out)
+        return bytes(out.cpu().numpy()), bytes(status.cpu().numpy())
+    lib = load_host_library()
+    src = (C.c_char * nin).from_buffer_copy(data) if nin else None
+    out = (C.c_char * max(out_bytes, 1)).from_buffer_copy(bytes([fill]) * max(out_bytes, 1))
+    status = C.create_string_buffer(max(n, 1))
+    bad, first = C.c_uint64(), C.c_uint64()
+    if lib.mcomh_gzip_inflate_members(src, nin, tab.ctypes.data if n else None, n, out, out_bytes, status, C.byref(bad), C.byref(first)):
+        raise McomError("gzip_inflate: a member's payload or slot leaves its buffer, or slots overlap or are out of order")
+    return out.raw[:out_bytes], status.raw[:n]
+
+
+def gzip_inflate(data: bytes, device: int | None = None):
+    """A BGZF buffer to (text, statuses): its members by mcom_gzip_walk, inflated by the host twin (device None) or by mcom_gzip_inflate
+    on that GPU.  statuses: one MCOM_GZIP_* byte per member; the text of a member that is not OK is unspecified inside its own slot.
+    McomError when the buffer is not BGZF members to its end."""
+    tab, text, used, ok = gzip_walk(data)
+    if not ok:
+        raise McomError(f"gzip_inflate: no BGZF member at byte {used}")
+    return gzip_inflate_members(data, tab, text, device)
+
+
+def gunzip_file(in_path: str, out_path: str, device: int | None = None) -> None:
+    """mcomh_gunzip_file: a BGZF file -> its text (what `mcomz u` runs).  device None: the host twin; an integer: that GPU (an error, never
+    the twin, when there is no such GPU).  No output file is left when a member is refused or the file is not BGZF to its end."""
+    if load_host_library().mcomh_gunzip_file(os.fsencode(in_path), os.fsencode(out_path), -1 if device is None else int(device)):
+        raise McomError(f"cannot inflate {in_path} to {out_path}" + ("" if device is None else f" on GPU {device}"))
 
 
 def rans_decode(member: bytes, cap: int | None = None) -> bytes:
