@@ -173,7 +173,8 @@ def _case_one_kept(L, k, e, seed, kept):
 
 
 SIZES = [33, 2, 64, 31, 8, 40, 3, 32, 9, 65, 30, 41]          # around BS_NMAX = 31 and around the 32 members k_group_consensus_reg holds; interleaved
-GROUP_SHAPES = [(100, 31, 4), (33, 11, 1), (256, 31, 4), (16, 11, 0), (17, 11, 1), (32, 11, 2), (255, 31, 4)]
+GROUP_SHAPES = [(100, 31, 4), (33, 11, 1), (256, 31, 4), (16, 11, 0), (17, 11, 1), (32, 11, 2), (255, 31, 4),
+                (65, 17, 2), (96, 31, 4), (129, 31, 4), (160, 31, 4), (161, 31, 4), (192, 31, 4), (193, 31, 4), (224, 31, 4)]   # NU = 3, 5, 6, 7 at both ends
 
 
 def _assemble(L, k, e, cases, vectorised=False):

@@ -113,7 +113,7 @@ def test_reference_streams_decode_to_the_host_routes_bytes(golden_dir, tmp_path,
 
 
 # ---- 2. round trips no fixture covers ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("L", [40, 100, 150, 256])
+@pytest.mark.parametrize("L", [40, 100, 150, 256, 176])
 @pytest.mark.parametrize("stream_sets", [1, 5])
 def test_round_trips_equal_the_host_route(tmp_path, L, stream_sets):
     from minicom_amd import synth

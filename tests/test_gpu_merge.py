@@ -69,7 +69,7 @@ def _make_groups(rng, n_groups, L, k, e):
     return reads, pack_nt4(reads), np.array(members, dtype=np.uint64), np.array(goff, dtype=np.int32)
 
 
-@pytest.mark.parametrize("L,k,e", [(100, 31, 4), (150, 31, 4), (64, 17, 2), (250, 31, 4), (40, 17, 2), (33, 11, 1)])
+@pytest.mark.parametrize("L,k,e", [(100, 31, 4), (150, 31, 4), (64, 17, 2), (250, 31, 4), (40, 17, 2), (33, 11, 1), (176, 31, 4)])
 def test_group_consensus_and_groups_to_contigs(ctx, L, k, e):
     rng = np.random.default_rng(L + e)
     reads, packed, members, goff = _make_groups(rng, 400, L, k, e)
@@ -131,7 +131,7 @@ def _random_set(rng, n, L):
     return refs, mems, reads, pack_nt4(reads)
 
 
-@pytest.mark.parametrize("L", [100, 150, 250, 40, 16, 32, 33, 256])
+@pytest.mark.parametrize("L", [100, 150, 250, 40, 16, 32, 33, 256, 96, 176, 192])
 def test_merge_round_pieces_against_numpy(ctx, L):
     """One merge round on a random set: member merge, consensus (every column, and overlap only), carry of the rest.
     L = 16, 32, 33 and 256 are the read-length edges of the consensus kernels: reads shorter than a 32-column unit, exactly one unit,

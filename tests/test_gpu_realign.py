@@ -174,7 +174,7 @@ def test_realign_high_threshold_uses_cost_filter_on_reverse_strand(ctx):
     assert total > 0 and rev_hi >= 0
 
 
-@pytest.mark.parametrize("L,maxsearch", [(150, 500), (150, 3), (150, 1), (100, 2), (64, 2), (200, 4)])
+@pytest.mark.parametrize("L,maxsearch", [(150, 500), (150, 3), (150, 1), (100, 2), (64, 2), (200, 4), (32, 2), (96, 2), (161, 4), (192, 3)])
 def test_read_driven_pass_equals_window_scan_also_with_bins_above_maxsearch(ctx, L, maxsearch):
     """Random contigs, singletons cut from them (both strands, substitutions, many duplicates so that bins exceed
     maxsearch): mcom_realign_pass_reads + mcom_dicts_eligible give the claims of the window scan."""
@@ -300,7 +300,7 @@ def test_index_keeps_heavy_repeats_in_runs_of_their_own(ctx):
     dicts.close()
 
 
-@pytest.mark.parametrize("L,ranks,heavy", [(150, 2, False), (150, 3, False), (150, 8, False), (100, 8, True), (100, 5, True), (64, 16, False), (200, 8, False)])
+@pytest.mark.parametrize("L,ranks,heavy", [(150, 2, False), (150, 3, False), (150, 8, False), (100, 8, True), (100, 5, True), (64, 16, False), (200, 8, False), (176, 3, False)])
 def test_lookups_over_shares_of_the_keys_min_reduced_equal_the_whole_index(ctx, L, ranks, heavy):
     """Several GPUs share the ONE contig index out BY KEY (mcom_cindex_plan_shared; host/mcom_pipeline.cpp "Stage 2"): rank q places the
     entries whose keys hash into share q and looks up, for every singleton, only the keys it owns; the claim keys are MIN-reduced
