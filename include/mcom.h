@@ -802,7 +802,8 @@ enum mcom_fastq_flag {
 	MCOM_FASTQ_F_PLUS = 2,      /* line 4r + 2 is empty or does not start with '+'                                      */
 	MCOM_FASTQ_F_LENGTH = 4,    /* line 4r + 1 or line 4r + 3 is not exactly L bytes long                               */
 	MCOM_FASTQ_F_CHAR = 8,      /* a quality byte outside 33 .. 126                                                     */
-	MCOM_FASTQ_F_LONG = 16      /* mcom_fastq_name_text: more than 255 bytes behind the '@' or the '+'                  */
+	MCOM_FASTQ_F_LONG = 16,     /* mcom_fastq_name_text: more than 255 bytes behind the '@' or the '+'                  */
+	MCOM_FASTQ_F_BASE = 32      /* mcom_fastq_lengths, mcom_fastq_ragged_rows: a sequence byte outside ACGTN            */
 };
 int mcom_fastq_quality_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
                             uint64_t n_records, uint32_t L, uint8_t *d_rows, uint64_t pitch, uint32_t *d_flag);
@@ -940,6 +941,47 @@ int mcom_fastq_name_text(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes,
 int mcom_fastq_emit_named(mcom_ctx *ctx, const uint8_t *d_reads, uint64_t read_pitch, const uint8_t *d_quals, uint64_t qual_pitch,
                           const uint8_t *d_names, uint64_t names_bytes, const uint64_t *d_rec_off, uint64_t count, uint32_t L,
                           uint8_t *d_out, uint64_t *bytes);
+
+/* ---- reads of differing lengths (csrc/ragged.hip) ----
+ * L is the modal sequence length of a file (ties: the larger length).  A record whose sequence is L bases long is EVEN, every other
+ * record ODD.  Even records are rows of an n_even x L table, numbered among themselves in input order; the lines of the odd records
+ * lie back to back, without newlines, in an odd text.  d_len holds one byte per record, its length - 1 (len.bin).  d_slot holds one
+ * 64-bit word per record: the rank among the even records, or MCOM_RAGGED_ODD | the offset into the odd text.  All four calls work
+ * from the line index of mcom_decode_line_index, are synchronous and take fewer than 2^32 records; text and tables are untrusted: what
+ * disagrees is flagged and skipped.
+ *   mcom_fastq_lengths      record r of this call is lines 4r .. 4r + 3 of the index.  Checked: '@', '+', both lengths equal and in
+ *                           1 .. 256, quality bytes in 33 .. 126, sequence bytes in ACGTN (MCOM_FASTQ_F_BASE).  d_len[first_record + r] =
+ *                           length - 1 of an unflagged record, and d_hist (256 counters that the caller cleared before the first piece)
+ *                           counts it in bin length - 1.  d_flag: the two words of mcom_fastq_quality_rows.
+ *   mcom_ragged_index       d_slot[r] for the n records of d_len; *n_even, *n_odd, *odd_bytes = the two counts and the odd text's length
+ *   mcom_fastq_ragged_rows  line 4r + which (1: sequence, 3: quality) of every record of the piece to row `slot` of d_rows (cap_rows
+ *                           rows, `pitch` apart) or to d_odd + offset (odd_cap bytes).  d_len / d_slot: the tables of all n_total records
+ *                           (record r of the piece is entry first_record + r).  A line whose length is not the table's, a slot outside
+ *                           its table (MCOM_FASTQ_F_LENGTH) or a byte outside its class (_BASE, _CHAR) is flagged, the byte not copied.
+ *   mcom_fastq_emit_ragged  records first .. first + count - 1 back to back into d_out (cap bytes; MCOM_E_OVERFLOW when too few).  With
+ *                           d_quals: `@<name>\n<read>\n+<text>\n<qualities>\n` from the name text d_names and the offsets of ALL its
+ *                           records d_rec_off (n + 1 entries), or `@<i+1>` and a bare `+` when d_names is NULL.  Without d_quals: the
+ *                           read and a newline.  *bytes = their length, also when d_out is NULL (the way to size d_out).  Tables that
+ *                           disagree with one another or with the sizes given are MCOM_E_ARG and nothing valid is in d_out.              */
+#define MCOM_RAGGED_ODD 0x8000000000000000ull
+typedef struct {
+	const uint8_t *d_reads; uint64_t read_pitch;         /* the even reads, n_even rows                                           */
+	const uint8_t *d_quals; uint64_t qual_pitch;         /* their quality rows; NULL: reads only                                  */
+	uint64_t n_even;
+	const uint8_t *d_odd_seq, *d_odd_qual; uint64_t odd_bytes;   /* the odd texts, one length (d_odd_qual unused without d_quals) */
+	const uint64_t *d_slot; const uint8_t *d_len; uint64_t n;    /* one entry per record                                          */
+	const uint8_t *d_names; uint64_t names_bytes; const uint64_t *d_rec_off;   /* what mcom_name_decode gives, or NULL            */
+	uint32_t L;
+} mcom_ragged_src;
+int mcom_fastq_lengths(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
+                       uint64_t n_records, uint8_t *d_len, uint64_t *d_hist, uint32_t *d_flag);
+int mcom_ragged_index(mcom_ctx *ctx, const uint8_t *d_len, uint64_t n, uint32_t L, uint64_t *d_slot, uint64_t *n_even, uint64_t *n_odd,
+                      uint64_t *odd_bytes);
+int mcom_fastq_ragged_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
+                           uint64_t n_records, int which, uint32_t L, const uint8_t *d_len, const uint64_t *d_slot, uint64_t n_total,
+                           uint8_t *d_rows, uint64_t pitch, uint64_t cap_rows, uint8_t *d_odd, uint64_t odd_cap, uint32_t *d_flag);
+int mcom_fastq_emit_ragged(mcom_ctx *ctx, const mcom_ragged_src *src, uint64_t first, uint64_t count, uint8_t *d_out, uint64_t cap,
+                           uint64_t *bytes);
 
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,

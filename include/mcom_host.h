@@ -504,6 +504,52 @@ int mcomh_fastq_names_to_device(const char *path, int device, size_t piece_bytes
 int mcomh_fastq_name_member(const char *fastq, int device, const char *out_path, uint64_t *n, char *err, size_t err_cap);
 int mcomh_verify_names_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report *rep);
 
+/* ---- `minicom -p -V`: a FASTQ file whose reads differ in length (host/mcom_ragged.cpp) ----
+ * L is the modal sequence length of the file (ties: the larger length).  A record whose sequence is L bases long is even: it goes to the
+ * core, to qual.mcq and through the decoders' row kernels as ever.  Every other record is odd: its sequence and quality lines go to the
+ * side members odd.seq and odd.qual, back to back in input order without newlines.  len.bin holds one byte per record, its length - 1;
+ * its presence marks a ragged archive.  name.mcn covers all records and does not change.  A record is refused when its sequence is empty,
+ * longer than 256 bases or of another length than its quality line, when a base is outside ACGTN or a quality byte outside 33 .. 126; the
+ * message names the first such record, from 1.  device = -1: the plain C++ twin of every call -- the same files refused, the same first
+ * bad record named, the same bytes written; otherwise that GPU (an error, never the twin, when there is no such GPU): the text goes up in
+ * pieces of piece_bytes (0 = 32 MiB; at least 2304 bytes, a smaller request is raised to that), a BGZF file is inflated on the card.
+ * No output file is left by a call that fails.
+ *   mcomh_fastq_lengths_file           one pass over the file: len.bin to out_path, *n records, *L, *n_odd records of another length
+ *   mcomh_fastq_ragged_files           line `which` (1 sequence, 3 quality) of every record: the even rows raw ([n_even][L]) to out_rows,
+ *                                      the odd text to out_odd; len_path: the file the call above wrote
+ *   mcomh_fastq_to_device_ragged       the even reads in HBM as [n_even][L] for mcomh_create (release with mcomh_device_free), odd.seq
+ *                                      written.  The one place where the read ingest parses on the card; used under -V only.
+ *   mcomh_fastq_quality_member_ragged  qual.mcq over the even rows by the unchanged quality coder, and odd.qual
+ *   mcomh_fastq_emit_ragged            the twin of mcom_fastq_emit_ragged (include/mcom.h) over host memory: records first .. first +
+ *                                      count - 1 into out (cap bytes; NULL: *bytes only).  -1: the tables disagree; -2: cap too small.
+ * The decoders pick folder/len.bin up by themselves as they pick up name.mcn (mcomh_decompress_order[_gpu]: one read per line;
+ * mcomh_decompress_fastq[_gpu]: four-line records) and refuse, leaving no output file, a folder whose parts disagree: the bytes of
+ * len.bin equal to L - 1 do not number the core's reads; the other lengths do not add up to the size of odd.seq, or of odd.qual;
+ * qual.mcq or name.mcn states another record count; odd.qual without qual.mcq, or the reverse.
+ *   mcomh_verify_ragged_gpu            `minicom -d -c` for such an archive: the file is split again on the GPU and len.bin, the even reads,
+ *                                      the even quality rows (when the archive has them) and the two odd texts are compared with what the
+ *                                      archive gives back, exactly.  rep: five reports in that order (mode 1; for the odd texts `differing`
+ *                                      counts bytes and first_diff is the first differing byte), present[k]: part k was compared.
+ *                                      Returns 0 when the comparisons were made.                                                         */
+typedef struct {                               /* mcom_ragged_src of include/mcom.h, every pointer in host memory */
+	const uint8_t *reads; uint64_t read_pitch;
+	const uint8_t *quals; uint64_t qual_pitch;
+	uint64_t n_even;
+	const uint8_t *odd_seq, *odd_qual; uint64_t odd_bytes;
+	const uint64_t *slot; const uint8_t *len; uint64_t n;
+	const uint8_t *names; uint64_t names_bytes; const uint64_t *rec_off;
+	uint32_t L;
+} mcomh_ragged_src;
+int mcomh_fastq_lengths_file(const char *fastq, int device, size_t piece_bytes, const char *out_path, uint64_t *n, int *L, uint64_t *n_odd, char *err, size_t err_cap);
+int mcomh_fastq_ragged_files(const char *fastq, int which, int L, int device, const char *len_path, size_t piece_bytes, const char *out_rows, const char *out_odd,
+                             uint64_t *n_even, char *err, size_t err_cap);
+int mcomh_fastq_to_device_ragged(const char *path, int device, int L, const char *len_path, size_t piece_bytes, uint8_t **d_reads, size_t *n_even, const char *odd_seq_path,
+                                 char *err, size_t err_cap);
+int mcomh_fastq_quality_member_ragged(const char *fastq, int L, int device, const char *len_path, const char *out_mcq, const char *out_odd_qual, uint64_t *n_even, char *err,
+                                      size_t err_cap);
+int mcomh_fastq_emit_ragged(const mcomh_ragged_src *src, uint64_t first, uint64_t count, uint8_t *out, uint64_t cap, uint64_t *bytes);
+int mcomh_verify_ragged_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report rep[5], int present[5]);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

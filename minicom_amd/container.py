@@ -46,6 +46,7 @@ READ_ORDER = "read_order.bin"     # temporary of compress_fastq(quality_reordere
 PAIR_ORDER = "pe_order.txt"       # marks a pair kept in input order: one line, the number of pairs; stored as it is
 PAIR_MEMBERS = ("qual_1.mcq", "qual_2.mcq", "name_1.mcn", "name_2.mcn")     # its quality values and names, file by file; name_2 is coded against name_1
 LOSSY_MARKER = "qual_lossy.txt"   # marks quality values stored with bounded loss: the canonical spec and a newline; stored as it is
+RAGGED_MEMBERS = ("len.bin", "odd.seq", "odd.qual")   # reads of differing lengths: through the codec like the singles; len.bin marks the archive
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -133,7 +134,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
         names = sorted({os.path.basename(p) for pat in patterns for p in glob.glob(os.path.join(folder, pat))})
         if names:
             members.append((group + ".tar", _inner_tar(folder, names)))
-    for s in SINGLES:
+    for s in SINGLES + RAGGED_MEMBERS:
         p = os.path.join(folder, s)
         if os.path.isfile(p):
             with open(p, "rb") as f:
@@ -180,7 +181,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
     {"order": bool, "paired": bool} as the reference's script decides them (minicom:326-334), and "quality": True for an archive
     that carries quality values (the member qual.mcq, left in the folder as it is), "quality_reordered": True for one that carries them
     in its own order (rqual.mcq, or rqual_1.mcq and rqual_2.mcq), "pair_order": True for a pair kept in input order (pe_order.txt; then
-    "quality" / "names" speak of qual_1.mcq + qual_2.mcq / name_1.mcn + name_2.mcn), "quality_lossy": the text of qual_lossy.txt for
+    "quality" / "names" speak of qual_1.mcq + qual_2.mcq / name_1.mcn + name_2.mcn), "ragged": True for an archive of reads of differing
+    lengths (len.bin), "quality_lossy": the text of qual_lossy.txt for
     an archive whose quality values went through a lossy transform (the file is left in the folder, where the
     verifiers look for it).
     device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
@@ -215,6 +217,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             kinds["quality_reordered"] = True
         if name == PAIR_ORDER:
             kinds["pair_order"] = True
+        if name == RAGGED_MEMBERS[0]:
+            kinds["ragged"] = True
         if name == LOSSY_MARKER:
             kinds["quality_lossy"] = data.decode("latin-1").rstrip("\n")      # (as stored: the verifiers judge whether it is a spec)
         if name in PAIR_MEMBERS:
@@ -239,7 +243,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, quality_reordered: bool = False,
-                   quality_lossy=None, **params) -> dict:
+                   quality_lossy=None, ragged: bool = False, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
@@ -251,7 +255,11 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     order, named by their row.
     quality_lossy (`minicom -b SPEC`; needs quality or quality_reordered): a lossy spec (`ill8`, `thr:T:LO:HI`,
     `pblock:P`); the quality rows go through mcom_qual_transform on `device` in front of the coder, and the archive says so in
-    qual_lossy.txt.  Returns pack()'s member sizes plus the read count."""
+    qual_lossy.txt.
+    ragged=True (`minicom -p -V`; needs order=True; not with path2, quality_reordered or quality_lossy): the
+    reads may differ in length.  Those of the modal length are the archive's reads, the others travel in len.bin, odd.seq and odd.qual;
+    a file of one length gives the archive made without it.  Returns pack()'s member sizes plus the read count (with ragged: "n_reads"
+    counts the reads of the modal length, "n_records" all)."""
     import tempfile
     from .hip import McomError
     from .pipeline import Pipeline
@@ -264,6 +272,13 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         raise ValueError("names are kept beside the quality values of an order-preserving archive only (order=True, quality=True)")
     if quality_reordered and (order or quality or names):
         raise ValueError("quality_reordered keeps the quality values in the archive's own order: not with order, quality or names")
+    if ragged and (not order or path2 is not None or quality_reordered or lossy is not None):
+        raise ValueError("ragged keeps reads of differing lengths of one file in its input order: order=True, no path2, no quality_reordered, no quality_lossy")
+    if ragged:
+        with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
+            sizes = _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params)
+        if sizes is not None:
+            return sizes                                             # (None: one length after all -- on as without ragged)
     p = Pipeline.from_fastq(path, device=device, path2=path2, host_threads=threads, **params)
     try:
         p.pre_process()
@@ -287,6 +302,35 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
             _mark_lossy(td, lossy)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
+        return sizes
+    finally:
+        p.close()
+
+
+def _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params):
+    """compress_fastq(ragged=True) in the order of `minicom -p -V`: lengths, the core over the reads of the modal length, the quality
+    values, the names, the container.  None when every read has one length."""
+    from .hip import McomError
+    from .pipeline import Pipeline, fastq_lengths, fastq_name_member, fastq_quality_member_ragged
+    len_path = os.path.join(td, RAGGED_MEMBERS[0])
+    n, L, n_odd = fastq_lengths(path, len_path, device=device)
+    if not n_odd:
+        return None
+    p = Pipeline.from_fastq_ragged(path, L, len_path, os.path.join(td, RAGGED_MEMBERS[1]), device=device, host_threads=threads, **params)
+    try:
+        p.pre_process()
+        p.cluster_dump(td, order=True, paired=False)
+        if quality:
+            n_rows = fastq_quality_member_ragged(path, L, len_path, os.path.join(td, QUALITY_MEMBER), os.path.join(td, RAGGED_MEMBERS[2]), device=device)
+            if n_rows != p.n:
+                raise McomError("%s: %d quality lines for %d reads" % (path, n_rows, p.n))
+        if names:
+            n_names = fastq_name_member(path, os.path.join(td, NAME_MEMBER), device=device)
+            if n_names != n:
+                raise McomError("%s: %d names for %d records" % (path, n_names, n))
+        sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
+        sizes["n_reads"] = p.n
+        sizes["n_records"] = n
         return sizes
     finally:
         p.close()
@@ -433,6 +477,14 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
         if kinds.get("quality_reordered"):
             from .pipeline import verify_records
             return tag(verify_records(td, fastq, fastq2, device=device))
+        if kinds.get("ragged"):                                      # part by part, then the names as ever
+            from .pipeline import verify_ragged
+            rep = verify_ragged(td, fastq, device=device)
+            if kinds.get("names"):
+                from .pipeline import verify_names
+                rep["names"] = verify_names(td, fastq, device=device)
+                rep["identical"] = rep["identical"] and rep["names"]["identical"]
+            return rep
         rep = tag(verify(td, fastq, fastq2, order=kinds["order"], device=device))
         if kinds.get("quality"):
             rep["quality"] = verify_quality(td, fastq, device=device)

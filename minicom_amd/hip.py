@@ -65,6 +65,13 @@ class QualLossyReport(C.Structure):
         return {"changed": int(self.changed), "sum_abs": int(self.sum_abs), "sum_sq": int(self.sum_sq), "max_abs": int(self.max_abs)}
 
 
+class RaggedSrc(C.Structure):
+    """mcom_ragged_src of include/mcom.h"""
+    _fields_ = [("d_reads", C.c_void_p), ("read_pitch", C.c_uint64), ("d_quals", C.c_void_p), ("qual_pitch", C.c_uint64), ("n_even", C.c_uint64),
+                ("d_odd_seq", C.c_void_p), ("d_odd_qual", C.c_void_p), ("odd_bytes", C.c_uint64), ("d_slot", C.c_void_p), ("d_len", C.c_void_p), ("n", C.c_uint64),
+                ("d_names", C.c_void_p), ("names_bytes", C.c_uint64), ("d_rec_off", C.c_void_p), ("L", C.c_uint32)]
+
+
 def _gzip_member_dtype():
     import numpy as np
     return np.dtype([("in_off", "<u8"), ("in_bytes", "<u8"), ("out_off", "<u8"), ("isize", "<u4"), ("crc", "<u4")])
@@ -231,6 +238,10 @@ def load_library():
     L.mcom_name_compare.restype = i32; L.mcom_name_compare.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_fastq_name_text.restype = i32; L.mcom_fastq_name_text.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp]
     L.mcom_fastq_emit_named.restype = i32; L.mcom_fastq_emit_named.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
+    L.mcom_fastq_lengths.restype = i32; L.mcom_fastq_lengths.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, vp]
+    L.mcom_ragged_index.restype = i32; L.mcom_ragged_index.argtypes = [vp, vp, u64, C.c_uint32, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.mcom_fastq_ragged_rows.restype = i32; L.mcom_fastq_ragged_rows.argtypes = [vp, vp, u64, vp, u64, u64, i32, C.c_uint32, vp, vp, u64, vp, u64, u64, vp, u64, vp]
+    L.mcom_fastq_emit_ragged.restype = i32; L.mcom_fastq_emit_ragged.argtypes = [vp, C.POINTER(RaggedSrc), u64, u64, vp, u64, C.POINTER(u64)]
     L.mcom_bwt_bound.restype = u64; L.mcom_bwt_bound.argtypes = [u64]
     L.mcom_bwt_encode.restype = i32; L.mcom_bwt_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.mcom_bwt_decode.restype = i32; L.mcom_bwt_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -1307,6 +1318,98 @@ class Context:
         out = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=self.device)
         self._check(self.lib.mcom_fastq_emit_named(self._h, reads.data_ptr() if count else None, rp, quals.data_ptr() if count else None, qp, self._p(names, torch.uint8),
                                                    int(names.shape[0]), self._p(off), count, L, self._p(out), C.byref(nb)))
+        return out[:nb.value]
+
+    # ---- reads of differing lengths (csrc/ragged.hip) ----
+    def fastq_lengths(self, text, first_record: int = 0, lens=None, hist=None):
+        """mcom_decode_line_index + mcom_fastq_lengths.  text: uint8 device tensor holding whole four-line records.  lens: a uint8 device
+        vector of at least first_record + n_records entries to write into (a fresh one otherwise); hist: the int64 device vector of 256
+        counters that runs across the pieces of a file (a cleared one otherwise).  Returns (lens, hist, flag bits of MCOM_FASTQ_F_*, the
+        first flagged record or None); the entry of a flagged record holds nothing valid."""
+        torch = _torch()
+        start, _ = self.decode_line_index(text)
+        n_rec = (int(start.shape[0]) - 1) // 4
+        if lens is None:
+            lens = torch.zeros(max(first_record + n_rec, 1), dtype=torch.uint8, device=self.device)
+        if hist is None:
+            hist = torch.zeros(256, dtype=torch.int64, device=self.device)
+        if lens.dtype != torch.uint8 or int(lens.shape[0]) < first_record + n_rec or hist.dtype != torch.int64 or int(hist.shape[0]) != 256:
+            raise McomError("fastq_lengths: lens must hold %d bytes, hist 256 int64 counters" % (first_record + n_rec))
+        flag = torch.tensor([0, -1], dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_fastq_lengths(self._h, self._p(text, torch.uint8) if n_rec else None, int(text.shape[0]), self._p(start), first_record, n_rec,
+                                                self._p(lens), self._p(hist), self._p(flag)))
+        f = flag.cpu().numpy().view(np.uint32)
+        return lens, hist, int(f[0]), (None if f[1] == 0xFFFFFFFF else int(f[1]))
+
+    def ragged_index(self, lens, L: int):
+        """mcom_ragged_index.  lens: uint8 device vector, byte r = length of record r - 1.  Returns (slots int64 [n]: the rank among the
+        even records, or bit 63 | the offset into the odd text -- negative as int64 --, n_even, n_odd, odd_bytes)."""
+        torch = _torch()
+        n = int(lens.shape[0])
+        slot = torch.zeros(max(n, 1), dtype=torch.int64, device=self.device)
+        ne, no, ob = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mcom_ragged_index(self._h, self._p(lens, torch.uint8) if n else None, n, int(L), self._p(slot), C.byref(ne), C.byref(no), C.byref(ob)))
+        return slot[:n], int(ne.value), int(no.value), int(ob.value)
+
+    def fastq_ragged_rows(self, text, which: int, L: int, lens, slot, rows, odd, first_record: int = 0):
+        """mcom_decode_line_index + mcom_fastq_ragged_rows.  text: uint8 device tensor holding whole four-line records, records
+        first_record .. of the file; which: 1 the sequence lines, 3 the quality lines; lens, slot: the tables of ALL records (fastq_lengths,
+        ragged_index); rows: uint8 device matrix [n_even, >= L] with contiguous rows, odd: uint8 device vector of odd_bytes -- both are
+        written into.  Returns (flag bits of MCOM_FASTQ_F_*, the first flagged record or None)."""
+        torch = _torch()
+        start, _ = self.decode_line_index(text)
+        n_rec = (int(start.shape[0]) - 1) // 4
+        n_total = int(lens.shape[0])
+        if lens.dtype != torch.uint8 or slot.dtype != torch.int64 or int(slot.shape[0]) != n_total or rows.dtype != torch.uint8 or odd.dtype != torch.uint8 or rows.dim() != 2 or \
+                (int(rows.shape[0]) and (rows.stride(1) != 1 or int(rows.shape[1]) < L)):
+            raise McomError("fastq_ragged_rows: lens uint8 and slot int64 of one length, rows a uint8 matrix of at least L columns, odd uint8")
+        cap_rows, odd_cap = int(rows.shape[0]), int(odd.shape[0])
+        pitch = int(rows.stride(0)) if cap_rows > 1 else max(L, int(rows.shape[1]) if cap_rows else L)
+        flag = torch.tensor([0, -1], dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_fastq_ragged_rows(self._h, self._p(text, torch.uint8) if n_rec else None, int(text.shape[0]), self._p(start), first_record, n_rec, int(which), int(L),
+                                                    self._p(lens) if n_total else None, self._p(slot) if n_total else None, n_total, rows.data_ptr() if cap_rows else None, pitch, cap_rows,
+                                                    odd.data_ptr() if odd_cap else None, odd_cap, self._p(flag)))
+        f = flag.cpu().numpy().view(np.uint32)
+        return int(f[0]), (None if f[1] == 0xFFFFFFFF else int(f[1]))
+
+    def fastq_emit_ragged(self, L: int, lens, slot, reads, odd_seq, quals=None, odd_qual=None, names=None, rec_off=None, first: int = 0, count=None):
+        """mcom_fastq_emit_ragged.  lens, slot: the tables of all n records; reads (and quals): uint8 device matrices [n_even, >= L] with
+        contiguous rows; odd_seq (and odd_qual): the odd texts; names, rec_off: a name text and the int64 offsets of all its records (what
+        name_decode returns).  Returns records first .. first + count - 1 (to the last one by default) as one uint8 device tensor: four
+        lines each with quals, else the read and a newline."""
+        torch = _torch()
+        n = int(lens.shape[0])
+        count = n - first if count is None else int(count)
+        S = RaggedSrc()
+        n_even = int(reads.shape[0])
+        for t in (reads, quals):
+            if t is not None and (t.dtype != torch.uint8 or t.dim() != 2 or int(t.shape[0]) != n_even or (n_even and (t.stride(1) != 1 or int(t.shape[1]) < L))):
+                raise McomError("fastq_emit_ragged: reads and qualities uint8 matrices of one row count and at least L columns, rows contiguous")
+        if (quals is None) != (odd_qual is None) or (odd_qual is not None and int(odd_qual.shape[0]) != int(odd_seq.shape[0])) or (names is None) != (rec_off is None):
+            raise McomError("fastq_emit_ragged: quality rows and odd quality text come together and match the reads', names and offsets come together")
+        if lens.dtype != torch.uint8 or slot.dtype != torch.int64 or int(slot.shape[0]) != n or (rec_off is not None and (rec_off.dtype != torch.int64 or int(rec_off.shape[0]) != n + 1)):
+            raise McomError("fastq_emit_ragged: lens uint8 [n], slot int64 [n], rec_off int64 [n + 1]")
+        keep = [t.contiguous() if t is not None else None for t in (odd_seq, odd_qual, names, rec_off, lens, slot)]
+        S.d_reads = reads.data_ptr() if n_even else None
+        S.read_pitch = int(reads.stride(0)) if n_even > 1 else max(L, int(reads.shape[1]))
+        nothing = torch.zeros(16, dtype=torch.uint8, device=self.device)      # an empty table still says "with qualities" / "with names"
+        S.d_quals = (quals.data_ptr() if n_even else nothing.data_ptr()) if quals is not None else None
+        S.qual_pitch = (int(quals.stride(0)) if n_even > 1 else max(L, int(quals.shape[1]))) if quals is not None else 0
+        S.n_even = n_even
+        S.odd_bytes = int(keep[0].shape[0])
+        S.d_odd_seq = keep[0].data_ptr() if S.odd_bytes else None
+        S.d_odd_qual = keep[1].data_ptr() if (quals is not None and S.odd_bytes) else None
+        S.d_slot = keep[5].data_ptr() if n else None
+        S.d_len = keep[4].data_ptr() if n else None
+        S.n = n
+        S.d_names = (keep[2].data_ptr() if int(keep[2].shape[0]) else nothing.data_ptr()) if names is not None else None
+        S.names_bytes = int(keep[2].shape[0]) if names is not None else 0
+        S.d_rec_off = keep[3].data_ptr() if rec_off is not None else None
+        S.L = int(L)
+        nb = C.c_uint64()
+        self._check(self.lib.mcom_fastq_emit_ragged(self._h, C.byref(S), int(first), count, None, 0, C.byref(nb)))
+        out = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.mcom_fastq_emit_ragged(self._h, C.byref(S), int(first), count, self._p(out), int(out.shape[0]), C.byref(nb)))
         return out[:nb.value]
 
     # ---- the block-sorting coder (csrc/bwt.hip) ----

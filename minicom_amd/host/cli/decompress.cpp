@@ -19,6 +19,9 @@
 // with qual_1.mcq / qual_2.mcq as four-line records, and with name_1.mcn / name_2.mcn the two input files byte for byte.
 // decompress --verify-order-pe DIR IN_1.fastq IN_2.fastq: reads, quality lines and names of such an archive against the two files, each
 // check the members allow, on GPU 0; exit status as --verify (1 before 2 before 0).
+// decompress --verify-ragged DIR IN.fastq: an archive made with -V (DIR holds len.bin): the file is split again on
+// GPU 0 and its lengths, its reads of the modal length, their quality lines and the two texts of the other reads are set against the
+// archive's, part by part; exit status as --verify.  The plain decoder and --fastq pick DIR/len.bin up by themselves.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
@@ -166,8 +169,27 @@ static int verify_order_pe(int argc, char **argv)
 	return rc;
 }
 
+static int verify_ragged(int argc, char **argv)
+{
+	if (argc < 3) { fprintf(stderr, "usage: decompress --verify-ragged DIR IN.fastq\n"); return 1; }
+	mcomh_verify_report r[5]; int present[5];
+	if (mcomh_verify_ragged_gpu(argv[1], argv[2], 0, r, present)) { fprintf(stderr, "decompress: %s could not be verified against %s\n", argv[1], argv[2]); return 1; }
+	static const char *what[5] = {"record lengths", "reads of the modal length", "quality lines of the reads of the modal length", "bases of the other reads", "quality values of the other reads"};
+	int rc = 0;
+	for (int k = 0; k < 5; ++k) {
+		if (!present[k]) continue;
+		if (r[k].identical) { printf("verified: %llu %s identical\n", (unsigned long long)r[k].n_input, what[k]); continue; }
+		rc = 2;
+		printf("DIFFERENT: %s: the FASTQ holds %llu, the archive %llu\n  %llu differ", what[k], (unsigned long long)r[k].n_input, (unsigned long long)r[k].n_archive, (unsigned long long)r[k].differing);
+		if (r[k].first_diff != ~(uint64_t)0) printf(", the first one %s %llu (from 0)", k == 1 || k == 2 ? "is row" : "lies in record", (unsigned long long)r[k].first_diff);
+		printf("\n");
+	}
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc > 1 && !strcmp(argv[1], "--verify-ragged")) return verify_ragged(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--order-pe")) return order_pe(argc - 1, argv + 1, false);
 	if (argc > 1 && !strcmp(argv[1], "--fastq-order-pe")) return order_pe(argc - 1, argv + 1, true);
 	if (argc > 1 && !strcmp(argv[1], "--verify-order-pe")) return verify_order_pe(argc - 1, argv + 1);

@@ -28,6 +28,10 @@
 // 3.14) -- mcom_bgzf_encode with --gpu, its host twin without, the same file either way.  What `minicom -d -z` runs without -G.
 // mcomz u [--gpu] IN.gz OUT: the inverse of z, a BGZF file to its text -- mcom_gzip_inflate with --gpu, its host
 // twin without.  Exit status 1 and no OUT when a member is refused or IN.gz is not BGZF members to its end.
+// mcomz e --fastq-lengths [--gpu] IN.fastq OUT: the first pass of `minicom -p -V`: OUT is len.bin, one byte
+// (length - 1) per record; prints `n L n_odd` -- the records, the modal length, the records of another length.
+// mcomz e --fastq-qual L --ragged LENFILE [--gpu] IN.fastq OUT.mcq OUT.oddqual: the `.mcq` member over the records of L bases and the
+// quality lines of the others back to back; prints the number of rows of the member.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +73,26 @@ int main(int argc, char **argv)
 			fprintf(stderr, "mcomz: %s is not a BGZF file of intact members, or %s cannot be written%s\n", u_in, u_out, u_gpu ? " (or the GPU route is not available)" : "");
 			return 1;
 		}
+		return 0;
+	}
+	// the two passes of `minicom -p -V` that are not the core's
+	if (argc > 2 && !strcmp(argv[1], "e") && !strcmp(argv[2], "--fastq-lengths")) {
+		const bool l_gpu = argc == 6 && !strcmp(argv[3], "--gpu");
+		if (argc != (l_gpu ? 6 : 5)) { fprintf(stderr, "usage: mcomz e --fastq-lengths [--gpu] IN.fastq OUT\n"); return 1; }
+		char err[320] = ""; uint64_t n = 0, n_odd = 0; int L = 0;
+		if (mcomh_fastq_lengths_file(argv[argc - 2], l_gpu ? 0 : -1, 0, argv[argc - 1], &n, &L, &n_odd, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", argv[argc - 2], err[0] ? err : "cannot take the lengths"); return 1; }
+		printf("%llu %d %llu\n", (unsigned long long)n, L, (unsigned long long)n_odd);
+		return 0;
+	}
+	if (argc > 5 && !strcmp(argv[1], "e") && !strcmp(argv[2], "--fastq-qual") && !strcmp(argv[4], "--ragged")) {
+		const bool r_gpu = argc == 10 && !strcmp(argv[6], "--gpu");
+		const int r_L = atoi(argv[3]);
+		if (argc != (r_gpu ? 10 : 9) || r_L < 1 || r_L > 256) { fprintf(stderr, "usage: mcomz e --fastq-qual L --ragged LENFILE [--gpu] IN.fastq OUT.mcq OUT.oddqual\n"); return 1; }
+		char err[320] = ""; uint64_t n_even = 0;
+		if (mcomh_fastq_quality_member_ragged(argv[argc - 3], r_L, r_gpu ? 0 : -1, argv[5], argv[argc - 2], argv[argc - 1], &n_even, err, sizeof err)) {
+			fprintf(stderr, "mcomz: %s: %s\n", argv[argc - 3], err[0] ? err : "cannot code the qualities"); return 1;
+		}
+		printf("%llu\n", (unsigned long long)n_even);
 		return 0;
 	}
 	bool gpu = false, bwt = false, names = false, fastq_names = false;

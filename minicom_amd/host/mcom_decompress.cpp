@@ -5,6 +5,7 @@
 // :612, decompress_nonorder :495, helpers :40-100) so that losslessness (parity level P2) can be
 // proven on a machine where the reference does not exist.  Plain host code, no GPU.
 #include "../../include/mcom_host.h"
+#include "mcom_ragged.hpp"
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -389,10 +390,59 @@ extern "C" int mcomh_decompress(const char *folder, const char *out_path, uint64
 	try { return decompress_impl(folder, out_path, n_reads); } catch (...) { return -1; }
 }
 
+// ---- a ragged archive (`minicom -p -V`): folder/len.bin says which records are the core's reads of L bases and
+// which lie in odd.seq / odd.qual.  The core's reads (and qual.mcq's rows) are decoded as ever, then the records are laid out in input
+// order by mcomh_fastq_emit_ragged: one read per line, or -- fastq -- four-line records named by name.mcn or `@<i+1>`.  A folder whose
+// parts disagree is refused and no file is written.
+static int decompress_ragged_impl(const char *folder, const char *out_path, uint64_t *n_reads, bool fastq)
+{
+	if (!folder || !out_path) return -1;
+	std::vector<char> reads; int L = 0; uint64_t n_even = 0;
+	if (decompress_order_impl(folder, nullptr, &n_even, &reads, &L)) return -1;
+	std::vector<uint8_t> qmember, nmember, quals, names;
+	const bool has_qual = slurp(std::string(folder) + "/qual.mcq", qmember), named = slurp(std::string(folder) + "/name.mcn", nmember);
+	if (fastq && !has_qual) return -1;
+	McomRaggedParts P;
+	std::string why;
+	if (!mcom_ragged_load(folder, L, n_even, has_qual, P, why)) { fprintf(stderr, "minicom decoder: %s\n", why.c_str()); return -1; }
+	uint64_t qn = 0, nn = 0, tl = 0; uint32_t qL = 0;
+	if (has_qual && (mcomh_qual_info(qmember.data(), qmember.size(), &qn, &qL) || qn != n_even || (int)qL != L)) { fprintf(stderr, "minicom decoder: qual.mcq does not state the number and length of the reads of the modal length\n"); return -1; }
+	if (named && (mcomh_name_info(nmember.data(), nmember.size(), &nn, &tl) || nn != P.n)) { fprintf(stderr, "minicom decoder: name.mcn does not state the records' number\n"); return -1; }
+	mcomh_ragged_src S;
+	memset(&S, 0, sizeof S);
+	S.reads = (const uint8_t*)reads.data(); S.read_pitch = (uint64_t)L; S.n_even = n_even; S.L = (uint32_t)L;
+	S.odd_seq = P.odd_seq.data(); S.odd_bytes = P.odd_seq.size(); S.slot = P.slot.data(); S.len = P.len.data(); S.n = P.n;
+	std::vector<uint64_t> rec_off;
+	if (fastq) {
+		quals.resize((size_t)n_even * (size_t)L + 1);
+		if (mcomh_qual_decode(qmember.data(), qmember.size(), quals.data(), (uint64_t)L, n_even, &qn, &qL) || qn != n_even || (int)qL != L) return -1;
+		S.quals = quals.data(); S.qual_pitch = (uint64_t)L; S.odd_qual = P.odd_qual.data();
+		if (named) {
+			names.resize(tl + 1);
+			if (mcomh_name_decode(nmember.data(), nmember.size(), names.data(), tl, &tl, &nn) || nn != P.n) return -1;
+			rec_off.reserve(P.n + 1); rec_off.push_back(0);
+			uint64_t lines = 0;
+			for (uint64_t i = 0; i < tl; ++i) if (names[i] == '\n' && (++lines & 1) == 0) rec_off.push_back(i + 1);
+			if (lines != 2 * P.n || rec_off.size() != P.n + 1) return -1;
+			S.names = names.data(); S.names_bytes = tl; S.rec_off = rec_off.data();
+		}
+	}
+	uint64_t bytes = 0;
+	if (mcomh_fastq_emit_ragged(&S, 0, P.n, nullptr, 0, &bytes)) { fprintf(stderr, "minicom decoder: the parts of the ragged archive disagree\n"); return -1; }
+	std::vector<uint8_t> out((size_t)bytes + 1);
+	if (mcomh_fastq_emit_ragged(&S, 0, P.n, out.data(), bytes, &bytes)) return -1;
+	FILE *f = fopen(out_path, "wb");
+	if (!f) return -1;
+	const bool ok = !bytes || fwrite(out.data(), 1, (size_t)bytes, f) == bytes;
+	if (fclose(f) != 0 || !ok) { remove(out_path); return -1; }
+	if (n_reads) *n_reads = P.n;
+	return 0;
+}
+
 // no C++ exception crosses the C boundary (a corrupt info.txt can ask for more memory than there is)
 extern "C" int mcomh_decompress_order(const char *folder, const char *out_path, uint64_t *n_reads)
 {
-	try { return decompress_order_impl(folder, out_path, n_reads); } catch (...) { return -1; }
+	try { return folder && mcom_ragged_present(folder) ? decompress_ragged_impl(folder, out_path, n_reads, false) : decompress_order_impl(folder, out_path, n_reads); } catch (...) { return -1; }
 }
 
 // no C++ exception crosses the C boundary (a corrupt info.txt can ask for more memory than there is)
@@ -448,7 +498,7 @@ static int decompress_fastq_impl(const char *folder, const char *out_path, uint6
 
 extern "C" int mcomh_decompress_fastq(const char *folder, const char *out_path, uint64_t *n_reads)
 {
-	try { return decompress_fastq_impl(folder, out_path, n_reads); } catch (...) { return -1; }
+	try { return folder && mcom_ragged_present(folder) ? decompress_ragged_impl(folder, out_path, n_reads, true) : decompress_fastq_impl(folder, out_path, n_reads); } catch (...) { return -1; }
 }
 
 // ---- `minicom -q` archives back to FASTQ on the host: the rows of the default / paired-end decoder in memory,

@@ -14,6 +14,7 @@
 #include "../../include/mcom_host.h"
 #include "../../include/mcom.h"
 #include "mcom_fastq.hpp"
+#include "mcom_ragged.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
@@ -554,6 +555,97 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	return 0;
 }
 
+// ---- a ragged archive (`minicom -p -V`): the fourth tail.  The table holds the n_even reads of the modal length;
+// folder/len.bin says where they stand among all records, odd.seq / odd.qual hold the lines of the others.  The side members are checked
+// against one another by the rules the host decoder applies (mcom_ragged_load), the slots are made by mcom_ragged_index, and
+// mcom_fastq_emit_ragged lays the records out a piece at a time: one read per line, or -- fastq -- four-line records.
+struct RaggedDev {
+	McomRaggedParts P;
+	mcom_ragged_src S;
+	std::vector<uint64_t> off;                              // record offsets of the name text, on the host (empty: no names)
+};
+// the side members and, for fastq, the quality rows and the names, on the device; S ready for the emit call
+void load_ragged(Arena &A, const char *folder, const uint8_t *table, uint64_t n_even, int L, bool fastq, RaggedDev &R)
+{
+	std::vector<uint8_t> qhead, nmember;
+	const bool has_qual = slurp(std::string(folder) + "/qual.mcq", qhead), named = slurp(std::string(folder) + "/name.mcn", nmember);
+	if (fastq && !has_qual) refuse_member("no qual.mcq: not a -Q archive");
+	std::string why;
+	if (!mcom_ragged_load(folder, L, n_even, has_qual, R.P, why)) refuse_member(why);
+	uint64_t qn = 0, nn = 0, names_bytes = 0; uint32_t qL = 0;
+	if (has_qual && (mcom_qual_info(qhead.data(), qhead.size(), &qn, &qL) || qn != n_even || (int)qL != L)) refuse_member("qual.mcq does not state the number and length of the reads of the modal length");
+	if (named && (mcom_name_info(nmember.data(), nmember.size(), &nn, &names_bytes) || nn != R.P.n)) refuse_member("name.mcn does not state the records' number");
+	mcom_ragged_src &S = R.S;
+	memset(&S, 0, sizeof S);
+	S.d_reads = table; S.read_pitch = (uint64_t)L + 1; S.n_even = n_even; S.L = (uint32_t)L; S.n = R.P.n;
+	S.d_odd_seq = A.upload(R.P.odd_seq.data(), R.P.odd_seq.size()); S.odd_bytes = R.P.odd_seq.size();
+	const uint8_t *d_len = A.upload(R.P.len.data(), R.P.len.size());
+	uint64_t *d_slot = A.alloc<uint64_t>(R.P.n);
+	uint64_t ne = 0, no = 0, ob = 0;
+	ok(A.ctx, mcom_ragged_index(A.ctx, d_len, R.P.n, (uint32_t)L, d_slot, &ne, &no, &ob));
+	if (ne != n_even || ob != S.odd_bytes) throw Refuse{"the slots do not match the side members"};
+	S.d_len = d_len; S.d_slot = d_slot;
+	if (!fastq) return;
+	S.d_quals = load_quals(A, folder, "qual.mcq", "-Q", n_even, L, (uint64_t)L); S.qual_pitch = (uint64_t)L;
+	S.d_odd_qual = A.upload(R.P.odd_qual.data(), R.P.odd_qual.size());
+	if (named) {
+		const uint8_t *d_nm = A.upload(nmember.data(), nmember.size());
+		uint8_t *dn = A.alloc<uint8_t>(names_bytes); uint64_t *dof = A.alloc<uint64_t>(R.P.n + 1);
+		if (mcom_name_decode(A.ctx, d_nm, nmember.size(), dn, names_bytes, &names_bytes, &nn, dof) || nn != R.P.n) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"name.mcn is refused"}; }
+		S.d_names = dn; S.names_bytes = names_bytes; S.d_rec_off = dof;
+		R.off.resize(R.P.n + 1);
+		if (hipMemcpy(R.off.data(), dof, (R.P.n + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+	}
+}
+
+int write_ragged(Arena &A, const char *folder, const uint8_t *table, uint64_t n_even, int L, const char *out_path, uint64_t *n_out, bool fastq)
+{
+	RaggedDev R;
+	load_ragged(A, folder, table, n_even, L, fastq, R);
+	const uint64_t n = R.P.n;
+	const double t0 = now_ms();
+	// where every piece begins: the most records whose bytes fit a piece, counted on the host from len.bin and the name offsets
+	std::vector<uint64_t> piece_at(1, 0);
+	{
+		uint64_t held = 0, digits = 1, next_pow = 10;
+		for (uint64_t i = 0; i < n; ++i) {
+			if (i + 1 >= next_pow) { ++digits; next_pow *= 10; }
+			const uint64_t l = (uint64_t)R.P.len[i] + 1;
+			uint64_t sz = !fastq ? l + 1 : R.off.empty() ? 2 * l + 6 + digits : 2 * l + 4 + (R.off[i + 1] >= R.off[i] ? R.off[i + 1] - R.off[i] : 0);
+			if (sz > PIECE_BYTES) throw Refuse{"a record does not fit a piece"};
+			if (held + sz > PIECE_BYTES) { piece_at.push_back(i); held = 0; }
+			held += sz;
+		}
+		if (n) piece_at.push_back(n);
+	}
+	const uint64_t pieces = piece_at.size() - 1;
+	void *p = nullptr;
+	if (hipHostMalloc(&p, PIECE_BYTES, hipHostMallocDefault) != hipSuccess) throw Refuse{"no page-locked memory"};
+	A.pinned.push_back(p);
+	uint8_t *pin = (uint8_t*)p, *d_out = A.alloc<uint8_t>(PIECE_BYTES);
+	std::unique_ptr<GzSink> sink(gz_path(out_path) ? new GzSink(A) : nullptr);     // made before the file is opened: a refusal leaves no file
+	FILE *out = fopen(out_path, "wb");
+	if (!out) return -1;
+	bool wrote_ok = true;
+	for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
+		uint64_t bytes = 0;
+		if (mcom_fastq_emit_ragged(A.ctx, &R.S, piece_at[i], piece_at[i + 1] - piece_at[i], d_out, PIECE_BYTES, &bytes)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); wrote_ok = false; break; }
+		if (sink) wrote_ok = sink->feed(d_out, (size_t)bytes, i + 1 == pieces, out);
+		else {
+			wrote_ok = hipMemcpy(pin, d_out, (size_t)bytes, hipMemcpyDeviceToHost) == hipSuccess;
+			const double tw = now_ms();
+			wrote_ok = wrote_ok && fwrite(pin, 1, (size_t)bytes, out) == bytes;
+			g_times[5] += now_ms() - tw;
+		}
+	}
+	if (sink && !pieces && wrote_ok) wrote_ok = sink->feed(nullptr, 0, true, out);
+	if (fclose(out) != 0) wrote_ok = false;
+	if (!wrote_ok) { remove(out_path); return -1; }
+	g_times[4] = now_ms() - t0;
+	if (n_out) *n_out = n;
+	return 0;
+}
+
 // ---- verification: the rows of phase B against the reads of the FASTQ file(s), both in HBM (csrc/verify.hip) ----
 // Side a is the input, side b the archive: `missing` are reads of the input that the archive does not give back.
 int compare_rows(Mode mode, Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L, const uint8_t *d_in, uint64_t n_in, int L_in, mcomh_verify_report *rep)
@@ -685,13 +777,24 @@ int verify_records(const char *folder, int mode, const char *fastq1, const char 
 } // namespace
 
 extern "C" int mcomh_decompress_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(DEFAULT, folder, out_path, nullptr, n_reads, device); }
-extern "C" int mcomh_decompress_order_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device) { return guarded(ORDER, folder, out_path, nullptr, n_reads, device); }
+extern "C" int mcomh_decompress_order_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device)
+{
+	if (folder && out_path && mcom_ragged_present(folder)) {                   // `minicom -p -V`: the records in input order, one read per line
+		try {
+			return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) { return write_ragged(A, folder, table, n_rows, L, out_path, n_reads, false); });
+		} catch (...) { return -1; }
+	}
+	return guarded(ORDER, folder, out_path, nullptr, n_reads, device);
+}
 extern "C" int mcomh_decompress_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device) { return guarded(PE, folder, out_path1, out_path2, n_pairs, device); }
 extern "C" int mcomh_decompress_fastq_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device)
 {
 	if (!folder || !out_path) return -1;
 	try {
-		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) { return write_fastq(A, folder, table, n_rows, L, out_path, n_reads); });
+		const bool ragged = mcom_ragged_present(folder);                        // `minicom -p -V -Q`: the fourth tail
+		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			return ragged ? write_ragged(A, folder, table, n_rows, L, out_path, n_reads, true) : write_fastq(A, folder, table, n_rows, L, out_path, n_reads);
+		});
 	} catch (...) { return -1; }
 }
 // ---- `minicom -q` archives: the default / paired-end decoder's rows, the quality rows of rqual*.mcq (stored in
@@ -820,6 +923,89 @@ extern "C" int mcomh_verify_records_gpu(const char *folder, int mode, const char
 	memset(rep, 0, sizeof(*rep));
 	try { return verify_records(folder, mode, fastq1, fastq2, device, rep); } catch (...) { return -1; }
 }
+// ---- `minicom -d -c` for a ragged archive: the file is split again -- its lengths, then its sequence lines and, when
+// the archive keeps them, its quality lines -- and every part is set against what the archive gives back: len.bin and the odd texts byte for
+// byte on the host (they are read from the folder as they are), the even reads and the even quality rows by mcom_verify_ordered in HBM.
+// Exact.  rep[0 .. 4]: len.bin, even reads, even quality rows, odd.seq, odd.qual; for the byte-wise parts `differing` counts bytes and
+// first_diff is the first record whose byte differs (~0: none, or a byte behind the shorter side's end).
+namespace {
+void bytes_report(const std::vector<uint8_t> &a, const std::vector<uint8_t> &b, mcomh_verify_report *r, const std::vector<uint8_t> *len_of_a, int L)
+{
+	memset(r, 0, sizeof *r);
+	r->mode = 1; r->n_input = a.size(); r->n_archive = b.size(); r->first_diff = ~(uint64_t)0;
+	const size_t m = a.size() < b.size() ? a.size() : b.size();
+	size_t first = m;
+	for (size_t i = 0; i < m; ++i) if (a[i] != b[i]) { if (!r->differing) first = i; ++r->differing; }
+	r->identical = !r->differing && a.size() == b.size();
+	if (r->identical) return;
+	if (!len_of_a) { r->first_diff = first; return; }                       // len.bin: byte r is record r
+	uint64_t at = 0;                                                       // an odd text: the odd record of the input that holds byte `first`
+	for (size_t rec = 0; rec < len_of_a->size(); ++rec) {
+		const uint64_t l = (uint64_t)(*len_of_a)[rec] + 1;
+		if ((int)l == L) continue;
+		if (first < at + l) { r->first_diff = rec; return; }
+		at += l;
+	}
+}
+void rows_report(const mcom_verify_report &r, mcomh_verify_report *rep)
+{
+	memset(rep, 0, sizeof *rep);
+	rep->mode = 1;
+	rep->identical = r.identical; rep->n_input = r.n_a; rep->n_archive = r.n_b;
+	rep->missing = r.missing; rep->extra = r.extra; rep->differing = r.differing; rep->first_diff = r.first_diff; rep->exact_runs = r.exact_runs;
+}
+}  // namespace
+
+extern "C" int mcomh_verify_ragged_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report rep[5], int present[5])
+{
+	if (!folder || !fastq || !rep || !present) return -1;
+	for (int k = 0; k < 5; ++k) present[k] = 0;
+	try {
+		const double t_begin = now_ms();
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { fprintf(stderr, "minicom verify: no GPU %d (%d visible); there is no host route\n", device, n_dev); return -1; }
+		if (!mcom_ragged_present(folder)) { fprintf(stderr, "minicom verify: %s has no len.bin: not an archive made with -V\n", folder); return -1; }
+		const std::string dir(folder), tmp_len = dir + "/verify_len.tmp";
+		struct Tmp { std::string p; ~Tmp() { remove(p.c_str()); } } tmp{tmp_len};
+		char err[320] = "";
+		uint64_t n_in = 0, n_odd_in = 0, ne_in = 0, ne_q = 0; int L_in = 0;
+		if (mcomh_fastq_lengths_file(fastq, device, 0, tmp_len.c_str(), &n_in, &L_in, &n_odd_in, err, sizeof err)) { fprintf(stderr, "minicom verify: cannot read %s: %s\n", fastq, err); return -1; }
+		std::vector<uint8_t> len_in, odd_seq_in, odd_qual_in;
+		if (!slurp(tmp_len, len_in)) return -1;
+		const bool has_qual = file_exists(dir + "/qual.mcq");
+		struct Dev { uint8_t *d = nullptr; ~Dev() { mcomh_device_free(d); } } in, qin;
+		if (mcom_ragged_split_to_device(fastq, device, 1, L_in, tmp_len.c_str(), &in.d, odd_seq_in, &ne_in, err, sizeof err) ||
+		    (has_qual && mcom_ragged_split_to_device(fastq, device, 3, L_in, tmp_len.c_str(), &qin.d, odd_qual_in, &ne_q, err, sizeof err))) {
+			fprintf(stderr, "minicom verify: cannot read %s: %s\n", fastq, err); return -1;
+		}
+		const double ingest = now_ms() - t_begin;
+		const int rr = run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			RaggedDev R;
+			load_ragged(A, folder, table, n_rows, L, has_qual, R);
+			bytes_report(len_in, R.P.len, &rep[0], nullptr, L_in); present[0] = 1;
+			bytes_report(odd_seq_in, R.P.odd_seq, &rep[3], &len_in, L_in); present[3] = 1;
+			if (has_qual) { bytes_report(odd_qual_in, R.P.odd_qual, &rep[4], &len_in, L_in); present[4] = 1; }
+			if (L_in != L) return 0;                                           // another modal length: len.bin differs, and rows of two widths are not compared
+			mcom_verify_table a, b;
+			mcom_verify_report r;
+			a.d_rows = in.d; a.pitch = (uint64_t)L; a.n = ne_in; a.d_mates = nullptr;
+			b.d_rows = table; b.pitch = (uint64_t)L + 1; b.n = n_rows; b.d_mates = nullptr;
+			ok(A.ctx, mcom_verify_ordered(A.ctx, &a, &b, L, &r));
+			rows_report(r, &rep[1]); present[1] = 1;
+			if (has_qual) {
+				a.d_rows = qin.d; a.n = ne_q;
+				b.d_rows = R.S.d_quals; b.pitch = (uint64_t)L;
+				ok(A.ctx, mcom_verify_ordered(A.ctx, &a, &b, L, &r));
+				rows_report(r, &rep[2]); present[2] = 1;
+			}
+			return 0;
+		});
+		if (rr) return -1;
+		rep[0].times_ms[0] = ingest; rep[0].times_ms[4] = now_ms() - t_begin;
+		return 0;
+	} catch (...) { return -1; }
+}
+
 extern "C" int mcomh_test_decoder_piece_bytes(size_t bytes)
 {
 	if (bytes && bytes < 4096) return -1;

@@ -157,6 +157,12 @@ def load_host_library():
     L.mcomh_verify_quality_member_gpu.restype = i32; L.mcomh_verify_quality_member_gpu.argtypes = [cp, cp, cp, i32, C.POINTER(VerifyReport)]
     L.mcomh_verify_names_member_gpu.restype = i32; L.mcomh_verify_names_member_gpu.argtypes = [cp, cp, cp, cp, i32, C.POINTER(VerifyReport)]
     L.mcomh_fastq_name_member_mate.restype = i32; L.mcomh_fastq_name_member_mate.argtypes = [cp, cp, i32, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_fastq_lengths_file.restype = i32; L.mcomh_fastq_lengths_file.argtypes = [cp, i32, sz, cp, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_fastq_ragged_files.restype = i32; L.mcomh_fastq_ragged_files.argtypes = [cp, i32, i32, i32, cp, sz, cp, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_fastq_to_device_ragged.restype = i32; L.mcomh_fastq_to_device_ragged.argtypes = [cp, i32, i32, cp, sz, C.POINTER(vp), C.POINTER(sz), cp, C.c_char_p, sz]
+    L.mcomh_fastq_quality_member_ragged.restype = i32; L.mcomh_fastq_quality_member_ragged.argtypes = [cp, i32, i32, cp, cp, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_fastq_emit_ragged.restype = i32; L.mcomh_fastq_emit_ragged.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64)]
+    L.mcomh_verify_ragged_gpu.restype = i32; L.mcomh_verify_ragged_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport), C.POINTER(i32)]
     _lib = L
     return L
 
@@ -199,6 +205,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_bgzf_bound", "mcomh_bgzf_encode", "mcomh_bgzf_file",
                     # BGZF input inflated on the GPU (host/mcom_gzip_gpu.cpp)
                     "mcomh_gzip_inflate_members", "mcomh_gzip_inflate", "mcomh_gunzip_file",
+                    # reads of differing lengths (`minicom -p -V`, host/mcom_ragged.cpp)
+                    "mcomh_fastq_lengths_file", "mcomh_fastq_ragged_files", "mcomh_fastq_to_device_ragged", "mcomh_fastq_quality_member_ragged",
+                    "mcomh_fastq_emit_ragged", "mcomh_verify_ragged_gpu",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -473,6 +482,70 @@ def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None =
     if load_host_library().mcomh_fastq_quality_member(os.fsencode(fastq), int(L), -1 if device is None else int(device), os.fsencode(out_path), C.byref(n), err, 320):
         raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
     return int(n.value)
+
+
+# ---- reads of differing lengths (`minicom -p -V`, host/mcom_ragged.cpp) ----
+def fastq_lengths(fastq: str, out_path: str, device: int | None = None, piece_bytes: int = 0):
+    """mcomh_fastq_lengths_file: one pass over a four-line FASTQ file (plain or .gz) whose reads may differ in length.  Every record is
+    checked, out_path gets len.bin (one byte, length - 1, per record).  Returns (n, L, n_odd): the records, the modal sequence length
+    (ties: the larger), the records of another length.  device=None: the host twin; an integer: on that GPU, the text going up in
+    pieces of piece_bytes (0: 32 MiB).  McomError names the first bad record."""
+    err = C.create_string_buffer(320)
+    n, L, n_odd = C.c_uint64(), C.c_int32(), C.c_uint64()
+    if load_host_library().mcomh_fastq_lengths_file(os.fsencode(fastq), -1 if device is None else int(device), int(piece_bytes), os.fsencode(out_path), C.byref(n), C.byref(L),
+                                                    C.byref(n_odd), err, 320):
+        raise McomError(f"{fastq}: {err.value.decode() or 'cannot take the lengths'}")
+    return int(n.value), int(L.value), int(n_odd.value)
+
+
+def fastq_ragged_files(fastq: str, which: int, L: int, len_path: str, out_rows: str, out_odd: str, device: int | None = None, piece_bytes: int = 0) -> int:
+    """mcomh_fastq_ragged_files: line `which` (1: sequence, 3: quality) of every record, split by the lengths in len_path: the lines of L
+    bytes as raw rows to out_rows, the others back to back to out_odd.  Returns n_even.  device as for fastq_lengths."""
+    err = C.create_string_buffer(320)
+    ne = C.c_uint64()
+    if load_host_library().mcomh_fastq_ragged_files(os.fsencode(fastq), int(which), int(L), -1 if device is None else int(device), os.fsencode(len_path), int(piece_bytes),
+                                                    os.fsencode(out_rows), os.fsencode(out_odd), C.byref(ne), err, 320):
+        raise McomError(f"{fastq}: {err.value.decode() or 'cannot split the file'}")
+    return int(ne.value)
+
+
+def fastq_quality_member_ragged(fastq: str, L: int, len_path: str, out_mcq: str, out_odd_qual: str, device: int | None = None) -> int:
+    """mcomh_fastq_quality_member_ragged: qual.mcq over the records of L bases and the quality lines of the others (odd.qual).  Returns the
+    rows of the member."""
+    err = C.create_string_buffer(320)
+    ne = C.c_uint64()
+    if load_host_library().mcomh_fastq_quality_member_ragged(os.fsencode(fastq), int(L), -1 if device is None else int(device), os.fsencode(len_path), os.fsencode(out_mcq),
+                                                             os.fsencode(out_odd_qual), C.byref(ne), err, 320):
+        raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
+    return int(ne.value)
+
+
+def ragged_index(len_bin: bytes, L: int):
+    """The slots of the records of a len.bin in plain Python (what mcom_ragged_index computes on the device): (slots, n_even, n_odd,
+    odd_bytes); a slot is the rank among the records of L bases, or bit 63 | the offset into the odd text."""
+    slots, n_even, odd_bytes = [], 0, 0
+    for b in len_bin:
+        if b + 1 == L:
+            slots.append(n_even); n_even += 1
+        else:
+            slots.append((1 << 63) | odd_bytes); odd_bytes += b + 1
+    return slots, n_even, len(len_bin) - n_even, odd_bytes
+
+
+def verify_ragged(folder: str, fastq: str, device: int = 0):
+    """mcomh_verify_ragged_gpu: an archive made with -V against its FASTQ file, part by part.  Returns a dict part -> report for the parts
+    that were compared: len, even_reads, even_quals, odd_seq, odd_qual."""
+    reps = (VerifyReport * 5)(); present = (C.c_int32 * 5)()
+    if load_host_library().mcomh_verify_ragged_gpu(os.fsencode(folder), os.fsencode(fastq), int(device), reps, present):
+        raise McomError(f"{folder} could not be verified against {fastq}")
+    out = {"identical": True}
+    for k, tag in enumerate(("len", "even_reads", "even_quals", "odd_seq", "odd_qual")):
+        if present[k]:
+            r = reps[k]
+            out[tag] = {"identical": bool(r.identical), "n_input": int(r.n_input), "n_archive": int(r.n_archive), "differing": int(r.differing),
+                        "first_diff": None if r.first_diff == 2 ** 64 - 1 else int(r.first_diff)}
+            out["identical"] = out["identical"] and out[tag]["identical"]
+    return out
 
 
 def decompress_fastq(folder: str, out_path: str, device: int | None = None) -> int:
@@ -1011,6 +1084,27 @@ class Pipeline:
         if L and L != self.L:
             self.close()
             raise McomError(f"{path}: reads of {self.L} bases, {L} expected")
+        return self
+
+    @classmethod
+    def from_fastq_ragged(cls, path: str, L: int, len_path: str, odd_seq_path: str, device: int = 0, piece_bytes: int = 0, **params):
+        """A FASTQ file whose reads differ in length -> pipeline over its reads of L bases: the text is parsed on
+        the card by the lengths in len_path (fastq_lengths wrote it and returned L), the reads of L bases go to HBM in input order
+        (mcomh_fastq_to_device_ragged), the bases of the others to odd_seq_path."""
+        lib = load_host_library()
+        err = C.create_string_buffer(320)
+        d, n = C.c_void_p(), C.c_size_t()
+        if lib.mcomh_fastq_to_device_ragged(os.fsencode(path), int(device), int(L), os.fsencode(len_path), int(piece_bytes), C.byref(d), C.byref(n), os.fsencode(odd_seq_path), err, 320):
+            raise McomError(f"{path}: {err.value.decode() or 'cannot read the file'}")
+        self = cls.__new__(cls)
+        self.lib = lib
+        p = Params(**{k: int(v) for k, v in params.items()})
+        h = C.c_void_p()
+        if lib.mcomh_create(C.byref(h), device, C.c_void_p(0), None, d, int(L), n.value, int(L), C.byref(p)):
+            lib.mcomh_device_free(d)
+            raise McomError("mcomh_create failed: no usable GPU or bad arguments; there is no CPU fallback")
+        self._h, self._dev_reads, self._keep = h, d, None
+        self.n, self.L = int(n.value), int(L)
         return self
 
     def _check(self, rc):
