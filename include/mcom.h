@@ -702,6 +702,31 @@ typedef struct {
 int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
                       uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag);
 
+/* ---- consensus agreement (`minicom -a Q[:C]`; csrc/decode.hip, csrc/qual_agree.hip; definitions: DESIGN.md section 3.17) ----
+ * mcom_agree_coverage: d_cov[b] (ref_bases bytes) = number of the n_members member reads of ONE stream set whose window
+ * [d_coff[d_cid[q]] + d_pos[q], + L) holds contig base b, exact up to 254 and 255 for anything above.  The tables are those of
+ * mcom_decode_member_table, ref_bases its *h_ref_bases.  A member whose contig or window leaves the tables raises MCOM_DECODE_F_BOUNDS
+ * and is not counted.  Takes 8 (ref_bases + 1) bytes of HBM while it runs: MCOM_E_OVERFLOW when the card has not got them.  Synchronous. */
+int mcom_agree_coverage(mcom_ctx *ctx, const uint32_t *d_cid, const uint32_t *d_pos, const uint64_t *d_coff, uint64_t n_contigs, uint64_t n_members,
+                         int L, uint64_t ref_bases, uint8_t *d_cov, uint32_t *d_flag);
+/* The sibling of mcom_decode_reads: for read m of the same source, mask row d_dest[m] (NULL: dest0 + m) of d_mask -- n_rows rows of
+ * (L + 7) / 8 bytes, mask_pitch >= that apart, column i of the decoded row in bit i & 7 of byte i >> 3, the unused high bits zero.  A bit is
+ * set when the read is a contig member (src->d_cid given), its decoded base at that column equals the contig's base at the place it is
+ * aligned to, and d_cov (cov_bases entries, mcom_agree_coverage) is >= min_cov (1 .. 255) there; a source without d_cid gets zero rows.
+ * Nothing but the (L + 7) / 8 bytes of a row is written.  The flags are mcom_decode_reads' (no d_seen: the rows' decoder has looked for
+ * rows named twice).  Asynchronous.                                                                                                */
+int mcom_agree_mask(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0, uint64_t n_rows,
+                      const uint8_t *d_cov, uint64_t cov_bases, uint32_t min_cov, uint8_t *d_mask, uint64_t mask_pitch, uint32_t *d_flag);
+/* The transform: byte i of quality row r (n_rows rows of L bytes in HBM, `pitch` >= L apart, any address, in place) becomes 33 + Q where
+ * bit i of mask row first_mask_row + r is set, and stays as it is elsewhere; the bytes between two rows are never written.  *h_report
+ * (may be NULL): mcom_qual_lossy_report's four counters and the number of mask bits set in the rows' columns.  MCOM_E_ARG, with nothing
+ * touched, for Q > 93, L outside 1 .. 256, pitch < L, mask_pitch < (L + 7) / 8.  Synchronous.  Bytes and report equal mcomh_qual_agree's. */
+typedef struct {
+	uint64_t changed, sum_abs, sum_sq, max_abs, mask_bits;
+} mcom_qual_agree_report;
+int mcom_qual_agree(mcom_ctx *ctx, uint8_t *d_rows, uint64_t n_rows, uint32_t L, uint64_t pitch, const uint8_t *d_mask, uint64_t mask_pitch,
+                    uint64_t first_mask_row, uint32_t Q, mcom_qual_agree_report *h_report);
+
 /* ---- verification: are two tables of reads in HBM the same reads?  (csrc/verify.hip) ----------
  * A table: n rows (below 2^32) of L characters (1 .. 256), `pitch` >= L bytes apart, at ANY address -- the ingested reads have
  * pitch L, the decoder's file image pitch L + 1.  A record is row i, or, when d_mates is given (on both sides), row i followed by

@@ -386,6 +386,42 @@ int mcomh_fastq_quality_member_lossy(const char *fastq, int L, int device, const
                                      uint64_t *n, mcomh_qual_lossy_report *report, char *err, size_t err_cap);
 int mcomh_qual_lossy_marker(const char *folder, mcomh_qual_lossy_spec *spec, char *text, size_t cap);
 
+/* ---- `minicom -a Q[:C]`: consensus-guided lossy quality values (host/mcom_agree.cpp) ----
+ * Every quality value of a base that agrees with its contig's consensus at a place at least C member reads cover becomes Phred Q; every
+ * other value stays.  The mask is a function of the archive's own core members, so a verifier rebuilds it from the archive.  The `.mcq`
+ * format and the decoders do not change; the archive says so in the plain file qual_agree.txt (`Q C` and a newline).
+ *   mcomh_agree_mask       the mask of the stream files in FOLDER, written to out_path: n rows of (L + 7) / 8 bytes, row j beside row j of
+ *                          the decoder's image, column i in bit i & 7 of byte i >> 3.  A folder with ids.bin.* is decoded as a -p archive,
+ *                          otherwise as a default one; a paired-end default archive (file.bin.*) and a ragged one (len.bin) are refused
+ *                          with a message.  What the matching decoder refuses is refused and leaves no file.  device = -1: the host
+ *                          decoders' member loops; otherwise mcom_agree_coverage and mcom_agree_mask on that GPU -- the same bytes.
+ *                          *bits_set = the mask bits set.  C is 1 .. 255.
+ *   mcomh_qual_agree       the host twin of mcom_qual_agree (include/mcom.h): the same arguments over host memory, the same bytes, the
+ *                          same report, the same arguments refused (-1, nothing touched)
+ *   mcomh_fastq_quality_member_agree   mcomh_fastq_quality_member_lossy (order_path NULL: input order; spec NULL: no -b transform) with the
+ *                          agreement transform behind the gather and in front of the -b transform: quality row r of the member belongs
+ *                          to row first_mask_row + r of the mask file, which must hold at least that many rows of (L + 7) / 8 bytes.
+ *                          On GPU `device` mcom_qual_agree, device = -1 its twin.  A call that fails writes no member.
+ *   mcomh_qual_agree_marker  FOLDER/qual_agree.txt: 0 = none, 1 = read (*Q, *C), -1 = there but not `Q C` and a newline with canonical
+ *                          decimal numbers in range -- the verifiers refuse such an archive
+ * mcomh_verify_quality_gpu and the quality parts of mcomh_verify_order_pe_parts_gpu send the file's rows through the rebuilt mask (as far as it
+ * has rows: a file of more records comes out different, not refused).  mcomh_verify_records_gpu (a `-q` archive of one file made with -a):
+ * "identical" means that the file's records can be assigned one-to-one to the archive's rows so that every record has its row's read and,
+ * sent through its row's mask (then through qual_lossy.txt's transform), its row's quality values; rows, quality rows and mask are made on
+ * the device, the matching -- both sides sorted by read, groups of equal reads settled by augmenting paths -- is host code.  A paired-end
+ * folder of the default mode that carries the marker is refused.                                                                           */
+typedef struct {
+	uint64_t changed, sum_abs, sum_sq, max_abs; /* as mcomh_qual_lossy_report                                                       */
+	uint64_t mask_bits;                         /* mask bits set in the rows' columns                                               */
+} mcomh_qual_agree_report;
+int mcomh_agree_mask(const char *folder, int C, const char *out_path, int device, uint64_t *n_rows, int *L, uint64_t *bits_set);
+int mcomh_qual_agree(uint8_t *rows, uint64_t n_rows, uint32_t L, uint64_t pitch, const uint8_t *mask, uint64_t mask_pitch, uint64_t first_mask_row, uint32_t Q,
+                     mcomh_qual_agree_report *report);
+int mcomh_fastq_quality_member_agree(const char *fastq, int L, int device, const char *order_path, const char *mask_path, uint64_t first_mask_row, uint32_t Q,
+                                     const mcomh_qual_lossy_spec *spec, const char *out_path, uint64_t *n, mcomh_qual_agree_report *agree_report,
+                                     mcomh_qual_lossy_report *report, char *err, size_t err_cap);
+int mcomh_qual_agree_marker(const char *folder, uint32_t *Q, uint32_t *C);
+
 /* ---- BGZF output (host/mcom_bgzf.cpp) ----
  * The host twin of mcom_bgzf_encode (include/mcom.h): a plain loop over csrc/deflate_model.hpp, the same bytes as the device call.
  * Any gzip reader takes the result; the member-parallel ingest (host/mcom_fastq_gz.cpp) finds the members by their BC field.

@@ -47,6 +47,7 @@ PAIR_ORDER = "pe_order.txt"       # marks a pair kept in input order (DESIGN.md 
 PAIR_MEMBERS = ("qual_1.mcq", "qual_2.mcq", "name_1.mcn", "name_2.mcn")     # its quality values and names, file by file; name_2 is coded against name_1
 LOSSY_MARKER = "qual_lossy.txt"   # marks quality values stored with bounded loss: the canonical spec and a newline; stored as it is
 RAGGED_MEMBERS = ("len.bin", "odd.seq", "odd.qual")   # reads of differing lengths: through the codec like the singles; len.bin marks the archive
+AGREE_MARKER = "qual_agree.txt"   # marks quality values of agreeing bases stored as one Phred value: `Q C` and a newline; stored as it is
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -159,7 +160,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
     if os.path.isfile(os.path.join(folder, NAME_MEMBER)):        # likewise (section 3.10)
         with open(os.path.join(folder, NAME_MEMBER), "rb") as f:
             packed.append((NAME_MEMBER, f.read()))
-    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS + (LOSSY_MARKER,):   # likewise (sections 3.11, 3.12 and 3.13)
+    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS + (LOSSY_MARKER, AGREE_MARKER):   # likewise (sections 3.11, 3.12, 3.13 and 3.17)
         if os.path.isfile(os.path.join(folder, m)):
             with open(os.path.join(folder, m), "rb") as f:
                 packed.append((m, f.read()))
@@ -184,7 +185,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
     "quality" / "names" speak of qual_1.mcq + qual_2.mcq / name_1.mcn + name_2.mcn), "ragged": True for an archive of reads of differing
     lengths (len.bin), "quality_lossy": the text of qual_lossy.txt for
     an archive whose quality values went through a lossy transform (the file is left in the folder, where the
-    verifiers look for it).
+    verifiers look for it), "quality_agree": the text of qual_agree.txt (`Q C`) for an archive made with quality_agree (section 3.17).
     device: where `.rans` and `.bwt` members are decoded -- None = the host twin, an integer = that GPU."""
     os.makedirs(folder, exist_ok=True)
     with tarfile.open(path, mode="r") as t:
@@ -193,7 +194,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS or name == LOSSY_MARKER:
+        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS or name == LOSSY_MARKER or name == AGREE_MARKER:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -221,6 +222,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             kinds["ragged"] = True
         if name == LOSSY_MARKER:
             kinds["quality_lossy"] = data.decode("latin-1").rstrip("\n")      # (as stored: the verifiers judge whether it is a spec)
+        if name == AGREE_MARKER:
+            kinds["quality_agree"] = data.decode("latin-1").rstrip("\n")     # (as stored, `Q C`: the verifiers judge whether it parses)
         if name in PAIR_MEMBERS:
             kinds["quality" if name.endswith(".mcq") else "names"] = True
         if name.startswith("idsbin.tar"):
@@ -243,7 +246,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, quality_reordered: bool = False,
-                   quality_lossy=None, ragged: bool = False, **params) -> dict:
+                   quality_lossy=None, ragged: bool = False, quality_agree=None, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
@@ -256,6 +259,9 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     quality_lossy (`minicom -b SPEC`; needs quality or quality_reordered): a lossy spec (`ill8`, `thr:T:LO:HI`,
     `pblock:P`); the quality rows go through mcom_qual_transform on `device` in front of the coder, and the archive says so in
     qual_lossy.txt.
+    quality_agree (`minicom -a Q[:C]`, DESIGN.md section 3.17; needs order=True and quality=True, or quality_reordered=True without path2; not with ragged): (Q, C) or Q alone (C = 3);
+    the quality value of every base that agrees with its contig's consensus at a place at least C member reads cover is stored as Phred Q.
+    The mask is made on `device` from the stream files just dumped; the archive says so in qual_agree.txt.  With quality_lossy: agreement first.
     ragged=True (`minicom -p -V`; needs order=True; not with path2, quality_reordered or quality_lossy): the
     reads may differ in length.  Those of the modal length are the archive's reads, the others travel in len.bin, odd.seq and odd.qual;
     a file of one length gives the archive made without it.  Returns pack()'s member sizes plus the read count (with ragged: "n_reads"
@@ -264,6 +270,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     from .hip import McomError
     from .pipeline import Pipeline
     lossy = _lossy_spec(quality_lossy, quality or quality_reordered)
+    agree = _agree_spec(quality_agree, ((quality and order) or (quality_reordered and path2 is None)) and not ragged)
     if order and path2 is not None:
         raise ValueError("-p is a single-end option (reference minicom:439-476)")
     if quality and (not order or path2 is not None):
@@ -289,17 +296,28 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
             if quality_reordered:
                 from .pipeline import fastq_quality_member
                 order_path = os.path.join(td, READ_ORDER)
+                mask_path = os.path.join(td, "agree.mask")              # a temporary like the order: never a member
+                if agree is not None:
+                    from .pipeline import agree_mask, fastq_quality_member_agree
+                    agree_mask(td, agree[1], device=device, out_path=mask_path)
                 for fq, member in ((path, "rqual.mcq"),) if path2 is None else ((path, "rqual_1.mcq"), (path2, "rqual_2.mcq")):
-                    fastq_quality_member(fq, p.L, os.path.join(td, member), device=device, order_path=order_path, lossy=lossy)
+                    if agree is not None:
+                        fastq_quality_member_agree(fq, p.L, os.path.join(td, member), mask_path, agree[0], device=device, order_path=order_path, lossy=lossy)
+                    else:
+                        fastq_quality_member(fq, p.L, os.path.join(td, member), device=device, order_path=order_path, lossy=lossy)
                 os.remove(order_path)
+                if agree is not None:
+                    os.remove(mask_path)
+            mask = _agree_mask(td, agree, device) if quality else None
             if quality:
-                _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER), lossy)
+                _quality_member(path, p.n, p.L, device, os.path.join(td, QUALITY_MEMBER), lossy, agree, mask, 0)
             if names:
                 from .pipeline import fastq_name_member
                 n_names = fastq_name_member(path, os.path.join(td, NAME_MEMBER), device=device)
                 if n_names != p.n:
                     raise McomError("%s: %d names for %d reads" % (path, n_names, p.n))
             _mark_lossy(td, lossy)
+            _mark_agree(td, agree)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         return sizes
@@ -337,11 +355,12 @@ def _compress_ragged(path, out_path, td, codec, device, threads, quality, names,
 
 
 def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = False, names: bool = False, codec: str = "xz", device: int = 0,
-                        threads: int = 8, quality_lossy=None, **params) -> dict:
+                        threads: int = 8, quality_lossy=None, quality_agree=None, **params) -> dict:
     """Two FASTQ files of a pair -> a `.minicom` archive that keeps both in input order (`minicom -1 A_1.fastq -2 A_2.fastq -p [-Q [-N]]`,
     DESIGN.md section 3.12): the order-preserving members of the second file's reads behind the first's, and pe_order.txt.  quality=True:
     qual_1.mcq and qual_2.mcq; names=True (needs quality=True): name_1.mcn and name_2.mcn, the second coded against the first file's names
-    -- decompress_file then gives both input files back byte for byte.  quality_lossy (needs quality=True): as for compress_fastq.
+    -- decompress_file then gives both input files back byte for byte.  quality_lossy, quality_agree (need quality=True): as for
+    compress_fastq; rows [0, n) of the agreement mask belong to the first file and rows [n, 2 n) to the second.
     Returns pack()'s member sizes plus the number of pairs."""
     import tempfile
     from .hip import McomError
@@ -349,20 +368,23 @@ def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = F
     if names and not quality:
         raise ValueError("names are kept beside the quality values only (quality=True)")
     lossy = _lossy_spec(quality_lossy, quality)
+    agree = _agree_spec(quality_agree, quality)
     p = Pipeline.from_fastq(path1, device=device, path2=path2, host_threads=threads, **params)
     try:
         p.pre_process()
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
             p.cluster_dump_order_pe(td)
             half = p.n // 2
+            mask = _agree_mask(td, agree, device)
             for k, fq in ((1, path1), (2, path2)):
                 if quality:
-                    _quality_member(fq, half, p.L, device, os.path.join(td, "qual_%d.mcq" % k), lossy)
+                    _quality_member(fq, half, p.L, device, os.path.join(td, "qual_%d.mcq" % k), lossy, agree, mask, (k - 1) * half)
                 if names:
                     n_names = fastq_name_member(fq, os.path.join(td, "name_%d.mcn" % k), device=device, mate_path=path1 if k == 2 else None)
                     if n_names != half:
                         raise McomError("%s: %d names for %d reads" % (fq, n_names, half))
             _mark_lossy(td, lossy)
+            _mark_agree(td, agree)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_pairs"] = half
         return sizes
@@ -384,20 +406,50 @@ def _lossy_spec(quality_lossy, keeps_quality: bool):
         raise ValueError(str(e)) from None
 
 
+def _agree_spec(quality_agree, allowed: bool):
+    """(Q, C) of compress_fastq's quality_agree (None: none); ValueError where there are no quality values in input order or for numbers out of range"""
+    if quality_agree is None:
+        return None
+    if not allowed:
+        raise ValueError("quality_agree changes the quality values of an order-preserving archive (order=True or a pair, quality=True) or of one file kept with quality_reordered; not with ragged or a paired-end archive of the default mode")
+    q, c = (quality_agree, 3) if isinstance(quality_agree, int) else tuple(quality_agree)
+    if not (isinstance(q, int) and isinstance(c, int) and 0 <= q <= 93 and 1 <= c <= 255):
+        raise ValueError("quality_agree is (Q, C) with Q 0 .. 93 and C 1 .. 255")
+    return q, c
+
+
+def _agree_mask(folder: str, agree, device: int):
+    """the agreement mask of the stream files in `folder` as a uint8 device matrix (None without agree)"""
+    if agree is None:
+        return None
+    import torch
+    from .pipeline import agree_mask
+    mask, _, _ = agree_mask(folder, agree[1], device=device)
+    return torch.from_numpy(mask).to(f"cuda:{int(device)}")
+
+
+def _mark_agree(folder: str, agree) -> None:
+    if agree is not None:
+        with open(os.path.join(folder, AGREE_MARKER), "wb") as f:
+            f.write(b"%d %d\n" % agree)
+
+
 def _mark_lossy(folder: str, lossy) -> None:
     if lossy is not None:
         with open(os.path.join(folder, LOSSY_MARKER), "wb") as f:
             f.write(lossy.encode() + b"\n")
 
 
-def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str, lossy=None) -> None:
-    """the quality lines of `fastq` -> rows on the device [-> the lossy transform, in place] -> a `.mcq` member in out_path"""
+def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str, lossy=None, agree=None, mask=None, first_mask_row: int = 0) -> None:
+    """the quality lines of `fastq` -> rows on the device [-> the agreement transform] [-> the lossy transform, in place] -> a `.mcq` member in out_path"""
     from .hip import Context, McomError
     from .pipeline import fastq_qualities
     rows = fastq_qualities(fastq, L, device=device)
     if int(rows.shape[0]) != n:
         raise McomError("%s: %d quality lines for %d reads" % (fastq, int(rows.shape[0]), n))
     ctx = Context(device)
+    if agree is not None:
+        rows, _ = ctx.qual_agree(rows, mask, agree[0], first_mask_row=first_mask_row, in_place=True)
     if lossy is not None:
         rows, _ = ctx.qual_transform(rows, lossy, in_place=True)
     member = ctx.qual_encode(rows)
@@ -414,7 +466,8 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
     and `+` texts: the input file.  gzip=True: the output file(s) are BGZF (gzip members of 65280 bytes of text
     each) -- compressed on the GPU by the decoders' tails when `device` is given and the paths end in `.gz` (on that route the suffix
     alone decides, with or without the keyword), otherwise the plain file is written beside the archive's members first and
-    pipeline.bgzf_file turns it into the same bytes."""
+    pipeline.bgzf_file turns it into the same bytes.  An archive made with quality_agree (qual_agree.txt) is decoded as ever; that its
+    quality values are lossy is said in one line on stderr, as `minicom -d` says it."""
     import tempfile
     from .pipeline import decompress, decompress_fastq, decompress_pe
     outs = [o for o in (out_path, out_path2) if o is not None]
@@ -428,6 +481,9 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
         return n
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        if kinds.get("quality_agree") is not None:                   # as `minicom -d` says it; the decoders do not change
+            import sys
+            print("minicom: the quality values of this archive are lossy: agreeing bases stored as Phred %s (coverage >= %s)" % tuple((kinds["quality_agree"].split(" ") + ["?", "?"])[:2]), file=sys.stderr)
         if kinds.get("pair_order"):                                  # seen first: its other members are those of a -p archive
             from .pipeline import decompress_order_pe
             if out_path2 is None:
@@ -454,6 +510,8 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
     from the members, as in decompress_file: a paired-end archive needs `fastq2`, a -p archive is held line against line, any other
     one as a multiset of reads.  For an archive made with quality_lossy the FASTQ file's quality rows go through the transform that
     qual_lossy.txt names before they are compared (the report gets "quality_lossy": its spec; McomError when the file holds no spec).
+    For an archive made with quality_agree the agreement mask is rebuilt from the archive on `device` and the file's quality rows go through it
+    first (the report gets "quality_agree": (Q, C); McomError when qual_agree.txt does not parse).
     An archive with quality values is held against the quality lines as well: the report gets
     "quality" (pipeline.verify_quality's) and "identical" is true only when both checks say so; one with names likewise gets "names"
     (pipeline.verify_names's)."""
@@ -466,7 +524,9 @@ def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int =
         kinds = unpack(path, td, threads=threads, device=device)
         from .pipeline import qual_lossy_marker
         lossy = qual_lossy_marker(td)                                # (McomError for a marker that is no spec)
-        tag = lambda r: dict(r, quality_lossy=lossy) if lossy is not None else r
+        from .pipeline import qual_agree_marker
+        agree = qual_agree_marker(td)                                # (McomError for a marker that does not parse)
+        tag = lambda r: dict(r, **({"quality_lossy": lossy} if lossy is not None else {}), **({"quality_agree": agree} if agree is not None else {}))
         if kinds.get("pair_order"):
             from .pipeline import verify_order_pe
             if fastq2 is None:

@@ -210,24 +210,24 @@ struct DcReads {
 
 __device__ __forceinline__ uint8_t dc_comp(uint8_t c) { return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'N'; }
 
-__global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
+// Steps 1 to 3 of a read's decode, the body k_dc_reads and k_dc_agree share: the reference window into the LDS row, the literals of the
+// line laid over it, the destination row into s_dest[g] (~0: none).  Every thread of the workgroup calls it (two barriers).  WIN (the
+// agreement mask): only a contig member has a window, whose places must also lie inside the coverage array
+// (cov_bases); `win` says per column "still the window byte" -- a literal clears it unless it equals the window byte -- and every other
+// read gets a row of N that agrees with nothing; no duplicate check (the rows' decoder has made it).
+template <bool WIN>
+__device__ __forceinline__ void dc_row_steps(const DcReads &a, uint64_t m, bool live, int g, int lane, uint8_t *row, uint8_t *win, uint64_t cov_bases, uint64_t *s_dest,
+                                             bool &have, uint64_t &off)
 {
-	__shared__ __align__(16) uint8_t s_row[DC_RPB][DC_PITCH];
-	__shared__ uint64_t s_dest[DC_RPB];
-	const int g = threadIdx.x / DC_G, lane = threadIdx.x % DC_G;
-	const uint64_t m = (uint64_t)blockIdx.x * DC_RPB + g;
-	const bool live = m < a.n;
 	const int L = a.L;
-	uint8_t *row = s_row[g];
+	have = false; off = 0;
 	// 1. the reference window
 	if (live) {
-		bool have = false;
-		uint64_t off = 0;
-		if (a.ref) {
+		if (a.ref && (!WIN || a.cid)) {
 			have = true;
 			if (a.cid) { const uint64_t c = a.cid[m]; if (c < a.n_contigs) off = a.coff[c] + a.pos[m]; else have = false; }
 			else off = m * (uint64_t)L;
-			if (have && off + (uint64_t)L > 4 * a.ref_bytes) have = false;
+			if (have && (off + (uint64_t)L > 4 * a.ref_bytes || (WIN && off + (uint64_t)L > cov_bases))) have = false;
 			if (!have && lane == 0) atomicOr(a.flag, MCOM_DECODE_F_BOUNDS);
 		}
 		if (have) {
@@ -240,15 +240,16 @@ __global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
 #pragma unroll
 				for (int j = 0; j < 4; ++j) w |= (uint32_t)(uint8_t)"ACGT"[(v >> (2 * j)) & 3u] << (8 * j);
 				*(uint32_t*)(row + p) = w;
+				if (WIN) *(uint32_t*)(win + p) = 0x01010101u;
 			}
 		} else {
-			const uint32_t ch = a.ref ? (uint32_t)'A' : (uint32_t)(uint8_t)a.ref_const;
-			for (int p = lane * 4; p < L; p += DC_G * 4) *(uint32_t*)(row + p) = ch * 0x01010101u;
+			const uint32_t ch = WIN ? (uint32_t)'N' : a.ref ? (uint32_t)'A' : (uint32_t)(uint8_t)a.ref_const;
+			for (int p = lane * 4; p < L; p += DC_G * 4) { *(uint32_t*)(row + p) = ch * 0x01010101u; if (WIN) *(uint32_t*)(win + p) = 0u; }
 		}
 	}
 	__syncthreads();
 	// 2. the line: its literals over the window (one lane: a line is a few bytes), or the line itself
-	if (live && a.text) {
+	if (live && a.text && (!WIN || (have && !a.verbatim))) {
 		const uint64_t s = a.line_start[m], e1 = a.line_start[m + 1];
 		if (e1 <= s || e1 > a.text_bytes) { if (lane == 0) atomicOr(a.flag, MCOM_DECODE_F_BOUNDS); }
 		else if (a.verbatim) {
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
 			bool ok = true;
 			for (uint64_t i = s; i + 1 < e1 && ok; ++i) {
 				const uint8_t ch = a.text[i];
-				if (ch >= 'A' && ch <= 'Z') { if (at + eq + 1 > (long)L) ok = false; else { at += eq; eq = 0; row[at++] = ch; } }
+				if (ch >= 'A' && ch <= 'Z') { if (at + eq + 1 > (long)L) ok = false; else { at += eq; eq = 0; if (WIN && row[at] != ch) win[at] = 0; row[at++] = ch; } }
 				else if (ch >= '0' && ch <= '9') { eq = eq * 10 + (ch - '0'); if (eq > (long)L) ok = false; }
 				else ok = false;
 			}
@@ -270,13 +271,26 @@ __global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
 	if (live && lane == 0) {
 		uint64_t d = a.dest ? a.dest[m] : a.dest0 + m;
 		if (d >= a.n_rows) { atomicOr(a.flag, MCOM_DECODE_F_DEST); d = ~0ull; }
-		else if (a.seen) {
+		else if (!WIN && a.seen) {
 			const uint32_t bit = 1u << (d & 31);
 			if (atomicOr(a.seen + (d >> 5), bit) & bit) { atomicOr(a.flag, MCOM_DECODE_F_DUP); d = ~0ull; }
 		}
 		s_dest[g] = d;
 	}
 	__syncthreads();
+}
+
+__global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
+{
+	__shared__ __align__(16) uint8_t s_row[DC_RPB][DC_PITCH];
+	__shared__ uint64_t s_dest[DC_RPB];
+	const int g = threadIdx.x / DC_G, lane = threadIdx.x % DC_G;
+	const uint64_t m = (uint64_t)blockIdx.x * DC_RPB + g;
+	const bool live = m < a.n;
+	const int L = a.L;
+	uint8_t *row = s_row[g];
+	bool have; uint64_t off;
+	dc_row_steps<false>(a, m, live, g, lane, row, nullptr, 0, s_dest, have, off);
 	if (!live) return;
 	const uint64_t d = s_dest[g];
 	if (d == ~0ull) return;
@@ -461,6 +475,127 @@ extern "C" int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint
 	a.dir = src->d_dir; a.dir_bytes = src->dir_bytes;
 	a.dest = d_dest; a.dest0 = dest0; a.n = n; a.L = L; a.out = d_out; a.n_rows = n_rows; a.seen = d_seen; a.flag = d_flag;
 	MCOM_LAUNCH(k_dc_reads, dim3((unsigned)((n + DC_RPB - 1) / DC_RPB)), dim3(DC_THREADS), 0, ctx->stream, a);
+	MCOM_LAUNCH_CHECK(ctx);
+	return MCOM_OK;
+}
+
+// ---- consensus agreement (`minicom -a Q[:C]`) ---------------------------------------------------------
+// coverage   cov[b] = member reads of the stream set whose window [coff[cid] + pos, + L) holds contig base b.  +1 at the window's first
+//            base and -1 behind its last into a cleared array of 64-bit words (wrapping), one exclusive scan (scan.hip) over bases + 1
+//            words -- cov[b] is entry b + 1 -- and a pass that narrows to bytes, saturating at 255          (k_dc_cov_mark, k_dc_cov_narrow)
+// mask       k_dc_reads' window and line walk with a second LDS row that says "still the window byte": a literal clears it unless it
+//            equals the window byte.  Then the flag meets the coverage of its place, and the row leaves as bits, reversed when the
+//            direction bit is set: column i in bit i & 7 of byte i >> 3 of mask row dest                                  (k_dc_agree)
+__global__ __launch_bounds__(DC_THREADS) void k_dc_cov_mark(const uint32_t *__restrict__ cid, const uint32_t *__restrict__ pos, const uint64_t *__restrict__ coff,
+                                                            uint64_t n_contigs, uint64_t n_members, int L, uint64_t bases, unsigned long long *__restrict__ diff,
+                                                            uint32_t *__restrict__ flag)
+{
+	const uint64_t q = (uint64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+	if (q >= n_members) return;
+	const uint64_t c = cid[q];
+	if (c >= n_contigs) { atomicOr(flag, MCOM_DECODE_F_BOUNDS); return; }
+	const uint64_t off = coff[c] + pos[q];
+	if (off > bases || (uint64_t)L > bases - off) { atomicOr(flag, MCOM_DECODE_F_BOUNDS); return; }
+	atomicAdd(diff + off, 1ull);
+	atomicAdd(diff + off + (uint64_t)L, ~0ull);                             // diff has bases + 1 words
+}
+
+__global__ __launch_bounds__(DC_THREADS) void k_dc_cov_narrow(const uint64_t *__restrict__ e, uint64_t bases, uint8_t *__restrict__ cov)
+{
+	const uint64_t b = (uint64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+	if (b >= bases) return;
+	const uint64_t v = e[b + 1];
+	cov[b] = v > 255 ? (uint8_t)255 : (uint8_t)v;
+}
+
+struct DcAgree {
+	DcReads r;                                                              // r.out and r.seen are not used
+	const uint8_t *cov; uint64_t cov_bases; uint32_t min_cov;
+	uint8_t *mask; uint64_t mask_pitch;
+};
+
+__global__ __launch_bounds__(DC_THREADS) void k_dc_agree(const DcAgree b)
+{
+	__shared__ __align__(16) uint8_t s_row[DC_RPB][DC_PITCH];
+	__shared__ __align__(16) uint8_t s_win[DC_RPB][DC_PITCH];               // 1: column p of the window still holds the window's byte
+	__shared__ uint64_t s_dest[DC_RPB];
+	const DcReads &a = b.r;
+	const int g = threadIdx.x / DC_G, lane = threadIdx.x % DC_G;
+	const uint64_t m = (uint64_t)blockIdx.x * DC_RPB + g;
+	const bool live = m < a.n;
+	const int L = a.L;
+	uint8_t *win = s_win[g];
+	bool have; uint64_t off;
+	dc_row_steps<true>(a, m, live, g, lane, s_row[g], win, b.cov_bases, s_dest, have, off);
+	const uint64_t d = live ? s_dest[g] : ~0ull;
+	// 4. the coverage of every agreeing column's place (off + p < cov_bases: checked in 1)
+	if (have && d != ~0ull) for (int p = lane; p < L; p += DC_G) if (win[p] && (uint32_t)b.cov[off + p] < b.min_cov) win[p] = 0;
+	__syncthreads();
+	if (d == ~0ull) return;
+	bool rev = false;
+	if (a.dir && (m >> 3) < a.dir_bytes) rev = (a.dir[m >> 3] >> (m & 7)) & 1u;
+	// 5. the mask row: a lane assembles whole bytes, (L + 7) / 8 of them, none behind the row
+	uint8_t *dst = b.mask + d * b.mask_pitch;
+	const int n_bytes = (L + 7) >> 3;
+	for (int k = lane; k < n_bytes; k += DC_G) {
+		uint32_t x = 0;
+#pragma unroll
+		for (int j = 0; j < 8; ++j) { const int i = 8 * k + j; if (i < L && win[rev ? L - 1 - i : i]) x |= 1u << j; }
+		dst[k] = (uint8_t)x;
+	}
+}
+
+extern "C" int mcom_agree_coverage(mcom_ctx *ctx, const uint32_t *d_cid, const uint32_t *d_pos, const uint64_t *d_coff, uint64_t n_contigs, uint64_t n_members,
+                                    int L, uint64_t ref_bases, uint8_t *d_cov, uint32_t *d_flag)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (!d_flag || L < 1 || L > 256 || (ref_bases && !d_cov)) return mcom_fail(ctx, MCOM_E_ARG, "agree_coverage: bad argument");
+	if (n_members && (!d_cid || !d_pos || !d_coff || n_contigs == 0)) return mcom_fail(ctx, MCOM_E_ARG, "agree_coverage: null pointer");
+	if (n_members >= DC_MAX_ITEMS || ref_bases >= DC_MAX_ITEMS) return mcom_fail(ctx, MCOM_E_ARG, "agree_coverage: too many members or bases");
+	if (ref_bases == 0 && n_members == 0) return MCOM_OK;
+	const uint64_t work = (ref_bases + 1) * 8;
+	{
+		size_t fr = 0, tot = 0;
+		MCOM_HIP(ctx, hipMemGetInfo(&fr, &tot));
+		if (work + ((uint64_t)64 << 20) > fr)
+			return mcom_fail(ctx, MCOM_E_OVERFLOW, "agree_coverage: %llu bytes of counters for %llu contig bases do not fit the card (%zu bytes free)", (unsigned long long)work, (unsigned long long)ref_bases, fr);
+	}
+	uint64_t *e = nullptr;
+	MCOM_HIP(ctx, mcom_dmalloc(&e, work));
+	mcom_dfree_later(ctx, e);
+	MCOM_HIP(ctx, hipMemsetAsync(e, 0, work, ctx->stream));
+	if (n_members) {
+		MCOM_LAUNCH(k_dc_cov_mark, dim3(dc_blocks(n_members)), dim3(DC_THREADS), 0, ctx->stream, d_cid, d_pos, d_coff, n_contigs, n_members, L, ref_bases, (unsigned long long*)e, d_flag);
+		MCOM_LAUNCH_CHECK(ctx);
+	}
+	int rc = mcom_scan64(ctx, e, e, ref_bases + 1, nullptr);
+	if (rc) return rc;
+	if (ref_bases) {
+		MCOM_LAUNCH(k_dc_cov_narrow, dim3(dc_blocks(ref_bases)), dim3(DC_THREADS), 0, ctx->stream, (const uint64_t*)e, ref_bases, d_cov);
+		MCOM_LAUNCH_CHECK(ctx);
+	}
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	return MCOM_OK;
+}
+
+extern "C" int mcom_agree_mask(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0, uint64_t n_rows,
+                                 const uint8_t *d_cov, uint64_t cov_bases, uint32_t min_cov, uint8_t *d_mask, uint64_t mask_pitch, uint32_t *d_flag)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (n == 0) return MCOM_OK;
+	if (!src || !d_mask || !d_flag || L < 1 || L > 256 || n >= (1ull << 34)) return mcom_fail(ctx, MCOM_E_ARG, "agree_mask: bad argument");
+	if (min_cov < 1 || min_cov > 255 || mask_pitch < (uint64_t)((L + 7) / 8)) return mcom_fail(ctx, MCOM_E_ARG, "agree_mask: coverage %u (1 .. 255), mask pitch %llu for %d columns", min_cov, (unsigned long long)mask_pitch, L);
+	if (src->d_text && !src->d_line_start) return mcom_fail(ctx, MCOM_E_ARG, "agree_mask: a text without its line index");
+	if (src->d_cid && (!src->d_ref || !src->d_pos || !src->d_coff || !d_cov)) return mcom_fail(ctx, MCOM_E_ARG, "agree_mask: a member table without its reference or its coverage");
+	DcAgree b;
+	DcReads &a = b.r;
+	a.text = src->d_text; a.text_bytes = src->text_bytes; a.line_start = src->d_line_start; a.verbatim = src->verbatim;
+	a.ref = src->d_ref; a.ref_bytes = src->ref_bytes; a.ref_const = src->ref_const;
+	a.cid = src->d_cid; a.pos = src->d_pos; a.coff = src->d_coff; a.n_contigs = src->n_contigs;
+	a.dir = src->d_dir; a.dir_bytes = src->dir_bytes;
+	a.dest = d_dest; a.dest0 = dest0; a.n = n; a.L = L; a.out = nullptr; a.n_rows = n_rows; a.seen = nullptr; a.flag = d_flag;
+	b.cov = d_cov; b.cov_bases = cov_bases; b.min_cov = min_cov; b.mask = d_mask; b.mask_pitch = mask_pitch;
+	MCOM_LAUNCH(k_dc_agree, dim3((unsigned)((n + DC_RPB - 1) / DC_RPB)), dim3(DC_THREADS), 0, ctx->stream, b);
 	MCOM_LAUNCH_CHECK(ctx);
 	return MCOM_OK;
 }

@@ -65,6 +65,14 @@ class QualLossyReport(C.Structure):
         return {"changed": int(self.changed), "sum_abs": int(self.sum_abs), "sum_sq": int(self.sum_sq), "max_abs": int(self.max_abs)}
 
 
+class QualAgreeReport(C.Structure):
+    """mcom_qual_agree_report of include/mcom.h = mcomh_qual_agree_report of include/mcom_host.h"""
+    _fields_ = [("changed", C.c_uint64), ("sum_abs", C.c_uint64), ("sum_sq", C.c_uint64), ("max_abs", C.c_uint64), ("mask_bits", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"changed": int(self.changed), "sum_abs": int(self.sum_abs), "sum_sq": int(self.sum_sq), "max_abs": int(self.max_abs), "mask_bits": int(self.mask_bits)}
+
+
 class RaggedSrc(C.Structure):
     """mcom_ragged_src of include/mcom.h"""
     _fields_ = [("d_reads", C.c_void_p), ("read_pitch", C.c_uint64), ("d_quals", C.c_void_p), ("qual_pitch", C.c_uint64), ("n_even", C.c_uint64),
@@ -219,6 +227,9 @@ def load_library():
     L.mcom_qual_gather_rows.restype = i32; L.mcom_qual_gather_rows.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, vp, u64, vp]
     L.mcom_dump_read_order.restype = i32; L.mcom_dump_read_order.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
     L.mcom_verify_multiset_parts.restype = i32; L.mcom_verify_multiset_parts.argtypes = [vp, C.POINTER(VerifyParts), C.POINTER(VerifyParts), i32, C.POINTER(VerifyReport)]
+    L.mcom_agree_coverage.restype = i32; L.mcom_agree_coverage.argtypes = [vp, vp, vp, vp, u64, u64, i32, u64, vp, vp]
+    L.mcom_agree_mask.restype = i32; L.mcom_agree_mask.argtypes = [vp, C.POINTER(DecodeSrc), u64, i32, vp, u64, u64, vp, u64, C.c_uint32, vp, u64, vp]
+    L.mcom_qual_agree.restype = i32; L.mcom_qual_agree.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, u64, u64, C.c_uint32, C.POINTER(QualAgreeReport)]
     L.mcom_qual_transform.restype = i32; L.mcom_qual_transform.argtypes = [vp, vp, u64, C.c_uint32, u64, C.POINTER(QualLossySpec), C.POINTER(QualLossyReport)]
     L.mcom_bgzf_bound.restype = u64; L.mcom_bgzf_bound.argtypes = [u64]
     L.mcom_bgzf_encode.restype = i32; L.mcom_bgzf_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
@@ -980,6 +991,70 @@ class Context:
         self._check(self.lib.mcom_decode_reads(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, self._p(out), n_rows, self._p(seen) if seen is not None else None, self._p(flag)))
         self.sync()
         return out, int(flag.item())
+
+    # ---- consensus agreement (`minicom -a Q[:C]`) ----
+    def decode_coverage(self, cid, pos, coff, L: int, ref_bases: int, out=None):
+        """mcom_agree_coverage over the member table of ONE stream set (decode_member_table).  Returns (cov uint8 [ref_bases], flag);
+        out: a uint8 device tensor of at least ref_bases entries to write into instead of a fresh one."""
+        torch = _torch()
+        nm = int(cid.shape[0])
+        cov = out if out is not None else torch.zeros(max(ref_bases, 1), dtype=torch.uint8, device=self.device)
+        assert cov.is_cuda and cov.dtype == torch.uint8 and cov.is_contiguous() and cov.numel() >= ref_bases
+        flag = self._dflag()
+        self._check(self.lib.mcom_agree_coverage(self._h, self._p(cid.contiguous(), torch.int32) if nm else None, self._p(pos.contiguous(), torch.int32) if nm else None,
+                                                  self._p(coff, torch.int64), int(coff.shape[0]) - 1, nm, L, int(ref_bases), self._p(cov), self._p(flag)))
+        return (cov if out is not None else cov[:ref_bases]), int(flag.item())
+
+    def decode_agree(self, n: int, L: int, n_rows: int, cov=None, min_cov: int = 3, text=None, line_start=None, verbatim=False, ref=None, ref_const="A", cid=None, pos=None, coff=None,
+                     dirbits=None, dest=None, dest0: int = 0, mask=None, mask_pitch: int | None = None):
+        """mcom_agree_mask: the sibling of decode_reads over the same source.  mask: uint8 [n_rows * mask_pitch] (made, zeroed, when None;
+        mask_pitch defaults to ceil(L / 8)).  Returns (mask, flag)."""
+        torch = _torch()
+        mb = (L + 7) // 8
+        if mask_pitch is None:
+            mask_pitch = mb
+        if mask is None:
+            mask = torch.zeros(n_rows * mask_pitch, dtype=torch.uint8, device=self.device)
+        flag = self._dflag()
+        src = DecodeSrc()
+        keep = []
+        def ptr(t, dt):
+            if t is None or t.numel() == 0:
+                return None
+            t = t.contiguous(); keep.append(t)
+            assert t.is_cuda and t.dtype == dt, (t.dtype, dt)
+            return t.data_ptr()
+        src.d_text = ptr(text, torch.uint8) if text is not None and line_start is not None else None
+        if text is not None and line_start is not None and src.d_text is None and n:
+            text = torch.zeros(1, dtype=torch.uint8, device=self.device); keep.append(text); src.d_text = text.data_ptr(); src.text_bytes = 0
+        else:
+            src.text_bytes = int(text.shape[0]) if text is not None else 0
+        src.d_line_start = ptr(line_start, torch.int64); src.verbatim = int(verbatim)
+        src.d_ref = ptr(ref, torch.uint8); src.ref_bytes = int(ref.shape[0]) if ref is not None else 0; src.ref_const = ord(ref_const)
+        src.d_cid = ptr(cid, torch.int32); src.d_pos = ptr(pos, torch.int32); src.d_coff = ptr(coff, torch.int64); src.n_contigs = (int(coff.shape[0]) - 1) if coff is not None else 0
+        src.d_dir = ptr(dirbits, torch.uint8); src.dir_bytes = int(dirbits.shape[0]) if dirbits is not None else 0
+        self._check(self.lib.mcom_agree_mask(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, n_rows, ptr(cov, torch.uint8), int(cov.shape[0]) if cov is not None else 0,
+                                               int(min_cov), self._p(mask), int(mask_pitch), self._p(flag)))
+        self.sync()
+        return mask, int(flag.item())
+
+    def qual_agree(self, rows, mask, Q: int, first_mask_row: int = 0, in_place: bool = False):
+        """mcom_qual_agree.  rows: uint8 device matrix [n, L] with contiguous rows (any row stride >= L, any address); mask: uint8 device
+        matrix [m, >= ceil(L / 8)] with contiguous rows, m >= first_mask_row + n.  Returns (the transformed matrix, the report as a dict of
+        exact integers: changed, sum_abs, sum_sq, max_abs, mask_bits).  The matrix is a copy unless in_place."""
+        torch = _torch()
+        if rows.dim() != 2 or rows.dtype != torch.uint8 or (rows.shape[0] and rows.stride(1) != 1) or mask.dim() != 2 or mask.dtype != torch.uint8 or (mask.shape[0] and mask.stride(1) != 1):
+            raise McomError("qual_agree: uint8 matrices with contiguous rows")
+        n, L = int(rows.shape[0]), int(rows.shape[1])
+        if first_mask_row < 0 or first_mask_row + n > int(mask.shape[0]):
+            raise McomError("qual_agree: the mask has no row for every quality row")
+        if not in_place:
+            rows = rows.contiguous().clone()
+        pitch = int(rows.stride(0)) if n > 1 else L
+        mask_pitch = int(mask.stride(0)) if mask.shape[0] > 1 else int(mask.shape[1])
+        rep = QualAgreeReport()
+        self._check(self.lib.mcom_qual_agree(self._h, rows.data_ptr() if n else None, n, L, pitch, mask.data_ptr() if mask.numel() else None, mask_pitch, int(first_mask_row), int(Q), C.byref(rep)))
+        return rows, rep.as_dict()
 
     # ---- the built-in entropy stage (csrc/entropy.hip) ----
     def rans_encode(self, raw, model=None, stride=1, out=None):

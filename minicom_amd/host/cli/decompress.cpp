@@ -22,6 +22,8 @@
 // decompress --verify-ragged DIR IN.fastq: an archive made with -V (DIR holds len.bin): the file is split again on
 // GPU 0 and its lengths, its reads of the modal length, their quality lines and the two texts of the other reads are set against the
 // archive's, part by part; exit status as --verify.  The plain decoder and --fastq pick DIR/len.bin up by themselves.
+// decompress --agree-mask [--gpu] DIR C OUT: the agreement mask of `minicom -a Q[:C]` of the stream files in DIR -- a
+// default-mode or a -p archive -- written to OUT; prints `n L bits_set`.  The quality verifiers pick DIR/qual_agree.txt up by themselves.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
@@ -35,13 +37,40 @@ static void examples(const char *what, const uint64_t *ex, uint32_t n)
 }
 
 // " under SPEC" for an archive made with `minicom -b SPEC` (qual_lossy.txt; the verifier has read it already, so it parses), "" otherwise
+// An archive made with `minicom -a Q[:C]` (qual_agree.txt) says " under agree Q:C" in front of it.
 static const char *under(const char *folder)
 {
-	static char text[48];
+	static char text[96];
 	mcomh_qual_lossy_spec sp; char spec[40];
+	uint32_t Q = 0, C = 0;
 	text[0] = 0;
-	if (mcomh_qual_lossy_marker(folder, &sp, spec, sizeof spec) == 1) snprintf(text, sizeof text, " under %s", spec);
+	const bool agree = mcomh_qual_agree_marker(folder, &Q, &C) == 1;
+	if (agree) snprintf(text, sizeof text, " under agree %u:%u", Q, C);
+	if (mcomh_qual_lossy_marker(folder, &sp, spec, sizeof spec) == 1) snprintf(text + strlen(text), sizeof text - strlen(text), "%s under %s", agree ? " and" : "", spec);
 	return text;
+}
+
+// decompress --agree-mask [--gpu] DIR C OUT: the agreement mask of the stream files in DIR as a file of n rows of
+// (L + 7) / 8 bytes; prints `n L bits_set`
+static int agree_mask(int argc, char **argv)
+{
+	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+	if (gpu) { --argc; ++argv; }
+	if (argc < 4) { fprintf(stderr, "usage: decompress --agree-mask [--gpu] DIR C OUT\n"); return 1; }
+	int C = 0;
+	{
+		const char *p = argv[2];
+		if (!*p || strlen(p) > 3 || (p[0] == '0')) C = -1;
+		for (; C >= 0 && *p; ++p) { if (*p < '0' || *p > '9') C = -1; else C = C * 10 + (*p - '0'); }
+	}
+	if (C < 1 || C > 255) { fprintf(stderr, "decompress: the coverage `%s` is not a decimal number 1 .. 255\n", argv[2]); return 1; }
+	uint64_t n = 0, bits = 0; int L = 0;
+	if (mcomh_agree_mask(argv[1], C, argv[3], gpu ? 0 : -1, &n, &L, &bits)) {
+		fprintf(stderr, "decompress: no agreement mask for %s: not a complete, consistent default-mode or -p archive%s\n", argv[1], gpu ? ", or the GPU route is not available" : "");
+		return 1;
+	}
+	fprintf(stdout, "%llu %d %llu\n", (unsigned long long)n, L, (unsigned long long)bits);
+	return 0;
 }
 
 static int verify(int argc, char **argv)
@@ -190,6 +219,7 @@ static int verify_ragged(int argc, char **argv)
 int main(int argc, char **argv)
 {
 	if (argc > 1 && !strcmp(argv[1], "--verify-ragged")) return verify_ragged(argc - 1, argv + 1);
+	if (argc > 1 && !strcmp(argv[1], "--agree-mask")) return agree_mask(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--order-pe")) return order_pe(argc - 1, argv + 1, false);
 	if (argc > 1 && !strcmp(argv[1], "--fastq-order-pe")) return order_pe(argc - 1, argv + 1, true);
 	if (argc > 1 && !strcmp(argv[1], "--verify-order-pe")) return verify_order_pe(argc - 1, argv + 1);

@@ -15,6 +15,10 @@
 // thr:T:LO:HI or pblock:P in their canonical form) in front of the coder -- mcom_qual_transform with --gpu, its host
 // twin without, the same member either way.  The report goes to stderr in one line, `lossy SPEC: changed C sum_abs A sum_sq S max_abs M`;
 // a spec the parser refuses is exit status 1 and no member.  pblock is not idempotent: coding a decoded matrix again changes it again.
+// mcomz e --fastq-qual L [--order FILE] --agree Q MASKFILE [--mask-first ROW] [--lossy SPEC]: the rows go through the agreement transform of
+// `minicom -a` behind the gather and in front of SPEC: the value of every column whose bit of MASKFILE
+// (`decompress --agree-mask`) is set becomes Phred Q; row r of the member belongs to mask row ROW + r (ROW 0 without --mask-first).  The
+// report goes to stderr in one line, `agree Q: mask_bits B changed C sum_abs A sum_sq S max_abs M`, in front of the lossy one.
 // mcomz --lossy-spec SPEC: prints the canonical text of SPEC; exit status 1 when the parser refuses it (what `minicom -b` asks first).
 // mcomz e --names [--gpu] IN OUT: IN is a name text (per record its name and the text of its third line, a line each; DESIGN.md section
 // 3.10), OUT a `.mcn` member; a line above 255 bytes is refused and its record named.  d knows such a member by its magic.
@@ -97,13 +101,29 @@ int main(int argc, char **argv)
 	}
 	bool gpu = false, bwt = false, names = false, fastq_names = false;
 	int at = 2, qual_L = 0, fastq_L = 0;
-	const char *order_path = nullptr, *mate_path = nullptr, *lossy_text = nullptr;
+	const char *order_path = nullptr, *mate_path = nullptr, *lossy_text = nullptr, *agree_mask = nullptr;
+	long agree_Q = -1; long long mask_first = -1;
+	// a canonical decimal number of at most `digits` digits, or -1
+	auto number = [](const char *t, int digits) -> long long {
+		if (!*t || (int)strlen(t) > digits || (t[0] == '0' && t[1])) return -1;
+		long long v = 0;
+		for (; *t; ++t) { if (*t < '0' || *t > '9') return -1; v = v * 10 + (*t - '0'); }
+		return v;
+	};
 	for (; at < argc; ++at) {
 		if (!strcmp(argv[at], "--gpu") && !gpu) gpu = true;
 		else if (!strcmp(argv[at], "--qual") && !qual_L && at + 1 < argc) { qual_L = atoi(argv[++at]); if (qual_L < 1 || qual_L > 256) { fprintf(stderr, "mcomz: --qual takes the row length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--fastq-qual") && !fastq_L && at + 1 < argc) { fastq_L = atoi(argv[++at]); if (fastq_L < 1 || fastq_L > 256) { fprintf(stderr, "mcomz: --fastq-qual takes the read length, 1 .. 256\n"); return 1; } }
 		else if (!strcmp(argv[at], "--order") && !order_path && at + 1 < argc) order_path = argv[++at];
 		else if (!strcmp(argv[at], "--lossy") && !lossy_text && at + 1 < argc) lossy_text = argv[++at];
+		else if (!strcmp(argv[at], "--agree") && !agree_mask && at + 2 < argc) {
+			agree_Q = (long)number(argv[at + 1], 2); agree_mask = argv[at + 2]; at += 2;
+			if (agree_Q < 0 || agree_Q > 93) { fprintf(stderr, "mcomz: --agree takes a Phred value 0 .. 93 (a decimal number without leading zeros) and the mask file\n"); return 1; }
+		}
+		else if (!strcmp(argv[at], "--mask-first") && mask_first < 0 && at + 1 < argc) {
+			mask_first = number(argv[++at], 18);
+			if (mask_first < 0) { fprintf(stderr, "mcomz: --mask-first takes a row number\n"); return 1; }
+		}
 		else if (!strcmp(argv[at], "--mate") && !mate_path && at + 1 < argc) mate_path = argv[++at];
 		else if (!strcmp(argv[at], "--bwt") && !bwt) bwt = true;
 		else if (!strcmp(argv[at], "--names") && !names) names = true;
@@ -111,7 +131,7 @@ int main(int argc, char **argv)
 		else break;
 	}
 	const bool enc = argc > 1 && !strcmp(argv[1], "e"), dec = argc > 1 && !strcmp(argv[1], "d");
-	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (lossy_text && !fastq_L && !qual_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--lossy SPEC] [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--lossy SPEC] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n       mcomz z [--gpu] IN OUT.gz\n       mcomz u [--gpu] IN.gz OUT\n"); return 1; }
+	if ((!enc && !dec) || argc != at + 2 || (dec && (bwt || qual_L || fastq_L)) || (bwt && (qual_L || fastq_L)) || (qual_L && fastq_L) || (order_path && !fastq_L) || (agree_mask && !fastq_L) || (mask_first >= 0 && !agree_mask) || (lossy_text && !fastq_L && !qual_L) || (names && (dec || bwt || qual_L || fastq_L)) || (fastq_names && (dec || bwt || qual_L || fastq_L || names)) || (mate_path && enc && !names && !fastq_names)) { fprintf(stderr, "usage: mcomz e|d [--gpu] IN OUT\n       mcomz e --bwt [--gpu] IN OUT\n       mcomz e --qual L [--lossy SPEC] [--gpu] IN OUT\n       mcomz e --fastq-qual L [--order FILE] [--agree Q MASKFILE [--mask-first ROW]] [--lossy SPEC] [--gpu] IN.fastq OUT\n       mcomz e --names [--gpu] IN OUT\n       mcomz e --fastq-names [--gpu] IN.fastq OUT\n       mcomz e --names --mate TEXT1 [--gpu] IN OUT\n       mcomz e --fastq-names --mate FILE_1.fastq [--gpu] IN.fastq OUT\n       mcomz d --mate TEXT1 [--gpu] IN OUT\n       mcomz z [--gpu] IN OUT.gz\n       mcomz u [--gpu] IN.gz OUT\n"); return 1; }
 	const char *in = argv[at], *out = argv[at + 1];
 	const int device = gpu ? 0 : -1;
 	int rc = 0;
@@ -124,6 +144,17 @@ int main(int argc, char **argv)
 		fprintf(stderr, "lossy %s: changed %llu sum_abs %llu sum_sq %llu max_abs %llu\n", lossy_text, (unsigned long long)lossy_rep.changed, (unsigned long long)lossy_rep.sum_abs,
 		        (unsigned long long)lossy_rep.sum_sq, (unsigned long long)lossy_rep.max_abs);
 	};
+	if (fastq_L && agree_mask) {
+		char err[320] = ""; uint64_t n = 0;
+		mcomh_qual_agree_report ar;
+		if (mcomh_fastq_quality_member_agree(in, fastq_L, device, order_path, agree_mask, mask_first < 0 ? 0 : (uint64_t)mask_first, (uint32_t)agree_Q, lossy_text ? &lossy : nullptr, out, &n, &ar, &lossy_rep,
+		                                     err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }
+		fprintf(stderr, "agree %ld: mask_bits %llu changed %llu sum_abs %llu sum_sq %llu max_abs %llu\n", agree_Q, (unsigned long long)ar.mask_bits, (unsigned long long)ar.changed,
+		        (unsigned long long)ar.sum_abs, (unsigned long long)ar.sum_sq, (unsigned long long)ar.max_abs);
+		if (lossy_text) report();
+		printf("%llu\n", (unsigned long long)n);
+		return 0;
+	}
 	if (fastq_L && lossy_text) {
 		char err[320] = ""; uint64_t n = 0;
 		if (mcomh_fastq_quality_member_lossy(in, fastq_L, device, order_path, &lossy, out, &n, &lossy_rep, err, sizeof err)) { fprintf(stderr, "mcomz: %s: %s\n", in, err[0] ? err : "cannot code the qualities"); return 1; }

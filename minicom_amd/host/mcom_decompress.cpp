@@ -6,6 +6,7 @@
 // proven on a machine where the reference does not exist.  Plain host code, no GPU.
 #include "../../include/mcom_host.h"
 #include "mcom_ragged.hpp"
+#include "mcom_agree.hpp"
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -80,7 +81,7 @@ void revcomp(std::string &s)
 } // namespace
 
 // keep: the rows (L characters each, back to back) are handed out instead of being written (mcomh_decompress_fastq_reordered)
-static int decompress_impl(const char *folder, const char *out_path, uint64_t *n_reads, std::vector<char> *keep = nullptr, int *L_out = nullptr)
+static int decompress_impl(const char *folder, const char *out_path, uint64_t *n_reads, std::vector<char> *keep = nullptr, int *L_out = nullptr, McomAgreeSink *agree = nullptr)
 {
 	if (!folder || (!out_path && !keep)) return -1;
 	const std::string dir(folder);
@@ -132,6 +133,8 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 		DnaReader rr(bref); BitReader dr(bdir);
 		size_t pp = 0, dp = 0;
 		std::string ref;
+		uint64_t coff = 0;                                                  // bases of ref.bin before this contig (the agreement mask's places)
+		if (agree) agree->L = L;
 		while (pp + 4 <= bpos.size()) {
 			uint32_t num; memcpy(&num, bpos.data() + pp, 4); pp += 4;
 			ref.clear();
@@ -145,10 +148,13 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 				size_t e = dp; while (e < bdif.size() && bdif[e] != '\n') ++e;
 				if (e >= bdif.size() || !decode_line((const char*)bdif.data() + dp, e - dp, ref.c_str() + pos, L, seq)) { shut(out); return -1; }
 				dp = e + 1;
+				if (agree) agree->member(total, coff + (uint64_t)pos, rev, seq.data(), ref.c_str() + pos);
 				if (rev) revcomp(seq);
 				line(seq);
 			}
+			coff += ref.size();
 		}
+		if (agree) agree->end_set();
 	}
 	shut(out);
 	if (keep && keep->size() != (size_t)total * (size_t)L) return -1;
@@ -163,7 +169,7 @@ static int decompress_impl(const char *folder, const char *out_path, uint64_t *n
 // are uint32, delta coded inside a list (lists are sorted by id); in ids.bin.T a member carries its id when it is the
 // first of its contig or starts at a new position, else the difference to the previous member's id (:164-167).
 // keep: the table of n_seq x L characters is handed out instead of being written (mcomh_decompress_fastq)
-static int decompress_order_impl(const char *folder, const char *out_path, uint64_t *n_reads, std::vector<char> *keep = nullptr, int *L_out = nullptr)
+static int decompress_order_impl(const char *folder, const char *out_path, uint64_t *n_reads, std::vector<char> *keep = nullptr, int *L_out = nullptr, McomAgreeSink *agree = nullptr)
 {
 	if (!folder || (!out_path && !keep)) return -1;
 	const std::string dir(folder);
@@ -244,6 +250,8 @@ static int decompress_order_impl(const char *folder, const char *out_path, uint6
 		DnaReader rr(bref); BitReader dr(bdir);
 		size_t pp = 0, dp = 0, ip = 0;
 		std::string ref;
+		uint64_t coff = 0;                                                  // bases of ref.bin before this contig (the agreement mask's places)
+		if (agree) agree->L = L;
 		while (pp + 4 <= bpos.size()) {
 			uint32_t num; memcpy(&num, bpos.data() + pp, 4); pp += 4;
 			ref.clear();
@@ -261,10 +269,13 @@ static int decompress_order_impl(const char *folder, const char *out_path, uint6
 				size_t e = dp; while (e < bdif.size() && bdif[e] != '\n') ++e;
 				if (e >= bdif.size() || !decode_line((const char*)bdif.data() + dp, e - dp, ref.c_str() + pos, L, seq)) return -1;
 				dp = e + 1;
+				if (agree) agree->member(id & 0xFFFFFFFFull, coff + (uint64_t)pos, rev, seq.data(), ref.c_str() + pos);
 				if (rev) revcomp(seq);
 				put(id & 0xFFFFFFFFull, seq);
 			}
+			coff += ref.size();
 		}
+		if (agree) agree->end_set();
 	}
 	if (bad) return -1;
 	for (uint8_t s : seen) if (!s) return -1;                              // every position filled exactly once
@@ -670,4 +681,22 @@ extern "C" int mcomh_decompress_order_pe(const char *folder, const char *out_pat
 extern "C" int mcomh_decompress_fastq_order_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
 {
 	try { return decompress_fastq_order_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
+}
+
+// ---- the agreement mask of a folder on the host (`minicom -a Q[:C]`): the default / -p decoder with its rows kept
+// in memory -- the same validations, the same refusals -- and the member loop's report to a McomAgreeSink.  The twin of mcom_agree_mask_gpu.
+int mcom_agree_mask_host(const char *folder, bool order, int C, std::vector<uint8_t> &mask, uint64_t *n_rows, int *L_out)
+{
+	if (!folder || C < 1 || C > 255) return -1;
+	try {
+		McomAgreeSink sink; sink.C = C;
+		std::vector<char> reads; int L = 0; uint64_t n = 0;
+		if (order ? decompress_order_impl(folder, nullptr, &n, &reads, &L, &sink) : decompress_impl(folder, nullptr, &n, &reads, &L, &sink)) return -1;
+		const size_t mb = (size_t)(L + 7) / 8;
+		mask.assign((size_t)n * mb, 0);
+		for (const McomAgreeSink::Row &r : sink.rows) { if (r.row >= n) return -1; memcpy(mask.data() + (size_t)r.row * mb, r.bits, mb); }
+		if (n_rows) *n_rows = n;
+		if (L_out) *L_out = L;
+		return 0;
+	} catch (...) { return -1; }
 }

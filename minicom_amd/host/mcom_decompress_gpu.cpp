@@ -15,7 +15,9 @@
 #include "../../include/mcom.h"
 #include "mcom_fastq.hpp"
 #include "mcom_ragged.hpp"
+#include "mcom_agree.hpp"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdint>
@@ -82,6 +84,7 @@ struct Seg {
 	mcom_decode_src src;
 	uint64_t n = 0;
 	const uint64_t *d_dest = nullptr; uint64_t dest0 = 0;
+	uint64_t ref_bases = 0;                                                 // a stream set: the bases of its contigs (mcom_decode_member_table)
 };
 
 // An output path that ends in `.gz` is written as BGZF: the pieces of text never leave the card, their members do.
@@ -150,8 +153,11 @@ uint32_t read_flag(Arena &A, const uint32_t *d_flag)
 
 // Phases A and B for the three decoders and for the verifier alike; `tail` gets the rows while they are still in HBM: 0 = done, else the call fails
 using Tail = std::function<int(Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L)>;
+// between B and C, for the callers that need what the rows were decoded from (the agreement mask): the segments of
+// an archive that has passed every check of A and B.  It throws Refuse like everything inside run().
+using Between = std::function<void(Arena &A, const std::vector<Seg> &segs, uint64_t n_rows, int L, uint32_t *d_flag)>;
 
-int run(Mode mode, const char *folder, int device, const Tail &tail)
+int run(Mode mode, const char *folder, int device, const Tail &tail, const Between *between = nullptr)
 {
 	const double t_begin = now_ms();
 	memset(g_times, 0, sizeof(g_times));
@@ -294,6 +300,7 @@ int run(Mode mode, const char *folder, int device, const Tail &tail)
 			uint64_t ref_bases = 0;
 			ok(A.ctx, mcom_decode_member_table(A.ctx, d_bpos, f.pos.size(), d_moff, nc, nm, L, cid, pos, coff, &ref_bases, d_flag));
 			if (ref_bases > 4 * (uint64_t)f.ref.size()) throw Refuse{"ref.bin is shorter than its contigs"};
+			s.ref_bases = ref_bases;
 			ok(A.ctx, mcom_decode_check_lines(A.ctx, t.d, t.bytes, t.start, nm, L, 0, d_flag));
 			s.src.d_text = t.d; s.src.text_bytes = t.bytes; s.src.d_line_start = t.start;
 			s.src.d_ref = A.upload(f.ref.data(), f.ref.size()); s.src.ref_bytes = f.ref.size();
@@ -367,6 +374,7 @@ int run(Mode mode, const char *folder, int device, const Tail &tail)
 		{ float ms = 0; if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_times[3] = ms; }
 		g_times[2] = now_ms() - t0;
 		if (fl) throw Refuse{"a read cannot be decoded or placed"};
+		if (between) (*between)(A, segs, n_rows, L, d_flag);
 
 		// ---- C. what becomes of the rows: the file(s), or the comparison of mcomh_verify_gpu
 		if (tail(A, table, n_rows, (uint64_t)half, L)) return -1;
@@ -376,6 +384,34 @@ int run(Mode mode, const char *folder, int device, const Tail &tail)
 	}
 	g_times[6] = now_ms() - t_begin;
 	return 0;
+}
+
+// ---- the agreement mask (`minicom -a Q[:C]`) of an archive run() has accepted: n_rows rows of (L + 7) / 8 bytes in
+// HBM.  Per stream set one mcom_agree_coverage (its array lives until the set's mask rows are written) and one mcom_agree_mask; the
+// lists' rows stay zero.  The array of the largest set and the mask must fit the card beside the rows.
+uint8_t *agree_mask(Arena &A, const std::vector<Seg> &segs, uint64_t n_rows, int L, uint32_t *d_flag, int C)
+{
+	const uint64_t mb = (uint64_t)(L + 7) / 8;
+	uint64_t most = 0;
+	for (const Seg &s : segs) if (s.src.d_cid && s.ref_bases > most) most = s.ref_bases;
+	{
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess || n_rows * mb + 9 * (most + 1) + ((size_t)64 << 20) > fr) {
+			fprintf(stderr, "minicom gpu decoder: the mask of %llu rows and the coverage of %llu contig bases do not fit the card (%zu bytes free)\n", (unsigned long long)n_rows, (unsigned long long)most, fr);
+			throw Refuse{"the agreement mask does not fit the card"};
+		}
+	}
+	uint8_t *mask = A.alloc<uint8_t>(n_rows * mb);
+	if (hipMemset(mask, 0, n_rows * mb + 16) != hipSuccess) throw Refuse{"memset failed"};
+	uint8_t *cov = A.alloc<uint8_t>(most);
+	for (const Seg &s : segs) {
+		if (!s.src.d_cid || !s.n) continue;
+		ok(A.ctx, mcom_agree_coverage(A.ctx, s.src.d_cid, s.src.d_pos, s.src.d_coff, s.src.n_contigs, s.n, L, s.ref_bases, cov, d_flag));
+		ok(A.ctx, mcom_agree_mask(A.ctx, &s.src, s.n, L, s.d_dest, s.dest0, n_rows, cov, s.ref_bases, (uint32_t)C, mask, mb, d_flag));
+		ok(A.ctx, mcom_sync(A.ctx));                                        // (the next set writes the same coverage array)
+	}
+	if (read_flag(A, d_flag)) throw Refuse{"a member's place leaves its contig"};
+	return mask;
 }
 
 // the file(s): copy of piece i + 1 under the write of piece i
@@ -705,6 +741,69 @@ int verify(const char *folder, int mode, const char *fastq1, const char *fastq2,
 	return 0;
 }
 
+// ---- `minicom -q -a`: the records of a default-mode archive against those of the file UNDER THE MASK.  The archive
+// does not say which record of the file a row was, and the mask row belongs to the archive's row, so "identical" means: there is a
+// one-to-one assignment of the file's records to the archive's rows such that every record has its row's read and, sent through its row's
+// mask (then through qual_lossy.txt's transform), its row's quality values.  Rows and records are grouped by read (a sort of either side);
+// a group of one is compared directly, a larger group is a bipartite matching (augmenting paths: exact, and a group is a handful of
+// records unless the file repeats a read thousands of times).  The rows, the mask and the quality rows are made on the device as ever;
+// the matching itself is host code over their downloaded bytes.
+struct AgreeRecords {
+	int L = 0; uint32_t Q = 0; bool lossy = false; mcomh_qual_lossy_spec spec;
+	std::vector<uint8_t> a_reads, a_quals, mask, f_reads, f_quals;          // archive: pitch L + 1, L, (L + 7) / 8; file: pitch L
+	uint64_t na = 0, nf = 0;
+	const uint8_t *aread(uint64_t j) const { return a_reads.data() + j * ((size_t)L + 1); }
+	const uint8_t *fread_(uint64_t k) const { return f_reads.data() + k * (size_t)L; }
+	// does record k of the file, sent through row j's mask, give row j's quality values?
+	bool fits(uint64_t k, uint64_t j) const
+	{
+		uint8_t tmp[256];
+		memcpy(tmp, f_quals.data() + k * (size_t)L, (size_t)L);
+		const uint8_t *m = mask.data() + j * (size_t)((L + 7) / 8);
+		for (int i = 0; i < L; ++i) if ((m[i >> 3] >> (i & 7)) & 1u) tmp[i] = (uint8_t)(33 + Q);
+		if (lossy && mcomh_qual_transform(tmp, 1, (uint32_t)L, (uint64_t)L, &spec, nullptr)) return false;
+		return !memcmp(tmp, a_quals.data() + j * (size_t)L, (size_t)L);
+	}
+	void compare(mcomh_verify_report *rep) const
+	{
+		std::vector<uint64_t> ia(na), jf(nf);
+		for (uint64_t i = 0; i < na; ++i) ia[i] = i;
+		for (uint64_t i = 0; i < nf; ++i) jf[i] = i;
+		std::sort(ia.begin(), ia.end(), [&](uint64_t x, uint64_t y) { const int c = memcmp(aread(x), aread(y), (size_t)L); return c < 0 || (c == 0 && x < y); });
+		std::sort(jf.begin(), jf.end(), [&](uint64_t x, uint64_t y) { const int c = memcmp(fread_(x), fread_(y), (size_t)L); return c < 0 || (c == 0 && x < y); });
+		uint64_t missing = 0, extra = 0, runs = 0;
+		auto miss = [&](uint64_t k) { if (rep->n_missing_ex < 8) rep->missing_ex[rep->n_missing_ex++] = k; ++missing; };
+		auto over = [&](uint64_t j) { if (rep->n_extra_ex < 8) rep->extra_ex[rep->n_extra_ex++] = j; ++extra; };
+		uint64_t a = 0, f = 0;
+		while (a < na || f < nf) {
+			const int c = a >= na ? 1 : f >= nf ? -1 : memcmp(aread(ia[a]), fread_(jf[f]), (size_t)L);
+			if (c < 0) { over(ia[a++]); continue; }
+			if (c > 0) { miss(jf[f++]); continue; }
+			uint64_t a1 = a + 1, f1 = f + 1;
+			while (a1 < na && !memcmp(aread(ia[a1]), aread(ia[a]), (size_t)L)) ++a1;
+			while (f1 < nf && !memcmp(fread_(jf[f1]), fread_(jf[f]), (size_t)L)) ++f1;
+			const size_t ga = (size_t)(a1 - a), gf = (size_t)(f1 - f);
+			if (ga > 1 || gf > 1) ++runs;
+			// row_of[x]: the file record (index into the group) matched to archive row x of the group, or -1
+			std::vector<long> row_of(ga, -1);
+			std::vector<char> seen;
+			std::function<bool(size_t)> place = [&](size_t y) {                   // an augmenting path from file record y
+				for (size_t x = 0; x < ga; ++x) {
+					if (seen[x] || !fits(jf[f + y], ia[a + x])) continue;
+					seen[x] = 1;
+					if (row_of[x] < 0 || place((size_t)row_of[x])) { row_of[x] = (long)y; return true; }
+				}
+				return false;
+			};
+			for (size_t y = 0; y < gf; ++y) { seen.assign(ga, 0); if (!place(y)) miss(jf[f + y]); }
+			for (size_t x = 0; x < ga; ++x) if (row_of[x] < 0) over(ia[a + x]);
+			a = a1; f = f1;
+		}
+		rep->n_input = nf; rep->n_archive = na; rep->missing = missing; rep->extra = extra; rep->exact_runs = runs;
+		rep->identical = missing == 0 && extra == 0 && na == nf;
+	}
+};
+
 // records with their quality lines (`minicom -q`): side a = the reads and quality rows of the FASTQ file(s) at pitch L, side b = the decoder's
 // image and the rows of rqual*.mcq decoded beside it at pitch L + 1; 2 parts in the default mode, 4 in the paired-end mode
 int verify_records(const char *folder, int mode, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
@@ -722,6 +821,11 @@ int verify_records(const char *folder, int mode, const char *fastq1, const char 
 		if (f) fclose(f);
 		if ((f != nullptr) != (mode == PE)) { fprintf(stderr, "minicom verify: %s is %sa paired-end archive\n", folder, f ? "" : "not "); return -1; }
 	}
+	// an archive made with -a (qual_agree.txt, section 3.17): the single-file archive is compared under its mask; a paired one has none
+	uint32_t agree_Q = 0, agree_C = 0;
+	const int have_agree = mcomh_qual_agree_marker(folder, &agree_Q, &agree_C);
+	if (have_agree < 0) { fprintf(stderr, "minicom verify: %s/qual_agree.txt does not hold `Q C` (0 .. 93, 1 .. 255) and a newline\n", folder); return -1; }
+	if (have_agree && mode == PE) { fprintf(stderr, "minicom verify: %s carries qual_agree.txt, and a paired-end archive of the default mode has no agreement mask\n", folder); return -1; }
 	struct Dev { uint8_t *d = nullptr; ~Dev() { mcomh_device_free(d); } } in, qin[2];
 	size_t n_in = 0, nq[2] = {0, 0}; int L_in = 0;
 	char err[320] = "";
@@ -735,12 +839,35 @@ int verify_records(const char *folder, int mode, const char *fastq1, const char 
 		if (L_in < 1 || mcomh_fastq_qualities_to_device(fq[k], device, L_in, 0, &qin[k].d, &nq[k], err, sizeof(err)) || nq[k] != n_rec) {
 			fprintf(stderr, "minicom verify: cannot read the qualities of %s: %s\n", fq[k], err[0] ? err : "another number of records than reads"); return -1;
 		}
-		if (mcom_qual_lossy_apply_marker(folder, device, qin[k].d, nq[k], L_in)) return -1;   // an archive made with -b holds T(file): row-local, so it commutes with the order
+		// an archive made with -b holds T(file): row-local, so it commutes with the order (under -a it follows the mask, row by row: AgreeRecords)
+		if (!have_agree && mcom_qual_lossy_apply_marker(folder, device, qin[k].d, nq[k], L_in)) return -1;
 	}
 	const double ingest = now_ms() - t_begin;
+	const uint8_t *d_mask = nullptr;
+	const Between between = [&](Arena &A, const std::vector<Seg> &segs, uint64_t n_rows, int L, uint32_t *d_flag) { d_mask = agree_mask(A, segs, n_rows, L, d_flag, (int)agree_C); };
 	const int rr = run((Mode)mode, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t half, int L) {
 		if (n_in && L_in != L) { fprintf(stderr, "minicom verify: the reads of the FASTQ are %d long, those of the archive %d\n", L_in, L); return -1; }
 		const uint64_t row = (uint64_t)L + 1, nb = mode == PE ? half : n_rows;
+		if (have_agree) {
+			AgreeRecords R;
+			R.L = L; R.Q = agree_Q; R.na = n_rows; R.nf = n_rec;
+			const int lm = mcomh_qual_lossy_marker(folder, &R.spec, nullptr, 0);
+			if (lm < 0) { fprintf(stderr, "minicom verify: %s/qual_lossy.txt does not hold a lossy spec (ill8, thr:T:LO:HI, pblock:P) and a newline\n", folder); return -1; }
+			R.lossy = lm == 1;
+			const uint8_t *d_q = load_quals(A, folder, "rqual.mcq", "-q", n_rows, L, (uint64_t)L);
+			const size_t mb = (size_t)(L + 7) / 8;
+			R.a_reads.resize((size_t)n_rows * row + 1); R.a_quals.resize((size_t)n_rows * L + 1); R.mask.resize((size_t)n_rows * mb + 1);
+			R.f_reads.resize(n_rec * (size_t)L + 1); R.f_quals.resize(n_rec * (size_t)L + 1);
+			if ((n_rows && (hipMemcpy(R.a_reads.data(), table, (size_t)n_rows * row, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(R.a_quals.data(), d_q, (size_t)n_rows * L, hipMemcpyDeviceToHost) != hipSuccess ||
+			                hipMemcpy(R.mask.data(), d_mask, (size_t)n_rows * mb, hipMemcpyDeviceToHost) != hipSuccess)) ||
+			    (n_rec && (hipMemcpy(R.f_reads.data(), in.d, n_rec * (size_t)L, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(R.f_quals.data(), qin[0].d, n_rec * (size_t)L, hipMemcpyDeviceToHost) != hipSuccess))) {
+				fprintf(stderr, "minicom verify: download failed\n"); return -1;
+			}
+			const double t0 = now_ms();
+			R.compare(rep);
+			rep->times_ms[3] = now_ms() - t0;
+			return 0;
+		}
 		mcom_verify_parts a, b;
 		memset(&a, 0, sizeof a); memset(&b, 0, sizeof b);
 		a.pitch = (uint64_t)L; a.n = n_rec; b.pitch = row; b.n = nb;
@@ -766,7 +893,7 @@ int verify_records(const char *folder, int mode, const char *fastq1, const char 
 		rep->n_missing_ex = r.n_missing_ex; rep->n_extra_ex = r.n_extra_ex;
 		memcpy(rep->missing_ex, r.missing_ex, sizeof(r.missing_ex)); memcpy(rep->extra_ex, r.extra_ex, sizeof(r.extra_ex));
 		return 0;
-	});
+	}, have_agree ? &between : nullptr);
 	if (rr) return -1;
 	rep->mode = mode;
 	rep->times_ms[0] = ingest; rep->times_ms[1] = g_times[1]; rep->times_ms[2] = g_times[2]; rep->times_ms[5] = g_times[0]; rep->times_ms[7] = g_times[3];
@@ -1004,6 +1131,25 @@ extern "C" int mcomh_verify_ragged_gpu(const char *folder, const char *fastq, in
 		rep[0].times_ms[0] = ingest; rep[0].times_ms[4] = now_ms() - t_begin;
 		return 0;
 	} catch (...) { return -1; }
+}
+
+// ---- the agreement mask of a folder (`minicom -a Q[:C]`; mcomh_agree_mask of mcom_agree.cpp): phases A and B as
+// ever -- an archive the decoder refuses has no mask -- then agree_mask() between B and C, and the mask comes back to the host as the tail.
+int mcom_agree_mask_gpu(const char *folder, bool order, int C, int device, std::vector<uint8_t> &mask, uint64_t *n_rows_out, int *L_out)
+{
+	if (!folder || C < 1 || C > 255) return -1;
+	try {
+		const uint8_t *d_mask = nullptr;
+		const Between between = [&](Arena &A, const std::vector<Seg> &segs, uint64_t n_rows, int L, uint32_t *d_flag) { d_mask = agree_mask(A, segs, n_rows, L, d_flag, C); };
+		return run(order ? ORDER : DEFAULT, folder, device, [&](Arena &, const uint8_t *, uint64_t n_rows, uint64_t, int L) {
+			const size_t bytes = (size_t)n_rows * (size_t)((L + 7) / 8);
+			mask.resize(bytes);
+			if (bytes && hipMemcpy(mask.data(), d_mask, bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+			if (n_rows_out) *n_rows_out = n_rows;
+			if (L_out) *L_out = L;
+			return 0;
+		}, &between);
+	} catch (...) { return -1; }   // no C++ exception crosses the C boundary
 }
 
 extern "C" int mcomh_test_decoder_piece_bytes(size_t bytes)

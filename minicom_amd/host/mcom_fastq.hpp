@@ -19,3 +19,6 @@ void mcom_fastq_stream_free(McomFastqStream *st);
 // mcom_qual_transform -- what a verifier does to the FASTQ file's rows before it compares.  0 = no marker, or applied; -1 = a marker that
 // is not a spec, or a device error (the message is printed)
 int mcom_qual_lossy_apply_marker(const char *folder, int device, uint8_t *d_rows, size_t n, int L);
+// the same for FOLDER/qual_agree.txt (`minicom -a`): the agreement mask rebuilt from the folder's stream files on the
+// device, its rows [first_mask_row, first_mask_row + n) laid over the rows by mcom_qual_agree.  Before the call above: agreement first.
+int mcom_qual_agree_apply_marker(const char *folder, int device, uint8_t *d_rows, size_t n, int L, uint64_t first_mask_row);

@@ -15,6 +15,7 @@
 #include "../../include/mcom.h"
 #include "mcom_fastq.hpp"
 #include "mcom_gzip_gpu.hpp"
+#include "mcom_agree.hpp"
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 #include <chrono>
@@ -200,6 +201,8 @@ int verify_quality(const char *folder, const char *member_name, const char *fast
 	size_t n_in = 0;
 	char err[320] = "";
 	if (qualities(fastq, device, (int)qL, 0, &in.d, &n_in, err, sizeof err)) { fprintf(stderr, "minicom verify: cannot read the qualities of %s: %s\n", fastq, err); return -1; }
+	// an archive made with -a holds the file's rows under its own agreement mask (section 3.17): rows [n, 2 n) of it for the second file of a pair
+	if (mcom_qual_agree_apply_marker(folder, device, in.d, n_in, (int)qL, strcmp(member_name, "qual_2.mcq") ? 0 : qn)) return -1;
 	if (mcom_qual_lossy_apply_marker(folder, device, in.d, n_in, (int)qL)) return -1;   // an archive made with -b holds T(file): section 3.13
 	const double ingest = now_ms() - t_begin;
 	struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d_member = nullptr, *d_rows = nullptr; ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d_member) (void)hipFree(d_member); if (d_rows) (void)hipFree(d_rows); if (ctx) mcom_destroy(ctx); } } D;
@@ -329,9 +332,41 @@ int qual_file(const char *in_path, const char *out_path, int L, int device, bool
 	return write_file(out_path, out.data(), n * qL) ? 0 : -1;
 }
 
+// `minicom -a Q[:C]`: the agreement transform between the gather of the rows and the -b transform.  The mask file
+// (mcomh_agree_mask) must hold rows first_row .. first_row + n - 1 of (L + 7) / 8 bytes each.
+struct AgreeArgs { const char *mask_path; uint64_t first_row; uint32_t Q; mcomh_qual_agree_report *rep; };
+int load_mask(const AgreeArgs &ag, size_t n, int L, std::vector<uint8_t> &mask, char *err, size_t err_cap)
+{
+	if (!ag.mask_path || ag.Q > 93) return fail(err, err_cap, "agree: a mask file and a Phred value 0 .. 93");
+	if (!slurp_file(ag.mask_path, mask)) return fail(err, err_cap, "cannot read the mask file");
+	const size_t mb = (size_t)(L + 7) / 8;
+	if (mask.size() % mb || mask.size() / mb < ag.first_row || mask.size() / mb - ag.first_row < n)
+		return fail(err, err_cap, "the mask file holds %llu bytes: not the rows [first, first + %llu) of this read length", (unsigned long long)mask.size(), (unsigned long long)n);
+	return 0;
+}
+int agree_host(const AgreeArgs &ag, uint8_t *rows, size_t n, int L, char *err, size_t err_cap)
+{
+	std::vector<uint8_t> mask;
+	if (load_mask(ag, n, L, mask, err, err_cap)) return -1;
+	if (mcomh_qual_agree(rows, n, (uint32_t)L, (uint64_t)L, mask.data(), (uint64_t)((L + 7) / 8), ag.first_row, ag.Q, ag.rep)) return fail(err, err_cap, "the agreement transform failed");
+	return 0;
+}
+int agree_device(const AgreeArgs &ag, mcom_ctx *ctx, uint8_t *d_rows, size_t n, int L, char *err, size_t err_cap)
+{
+	std::vector<uint8_t> mask;
+	if (load_mask(ag, n, L, mask, err, err_cap)) return -1;
+	const size_t mb = (size_t)(L + 7) / 8;
+	struct Dev { uint8_t *d = nullptr; ~Dev() { if (d) (void)hipFree(d); } } M;
+	if (hipMalloc((void**)&M.d, n * mb + 16) != hipSuccess) return fail(err, err_cap, "no room on the card for the mask");
+	if (n && hipMemcpy(M.d, mask.data() + (size_t)ag.first_row * mb, n * mb, hipMemcpyHostToDevice) != hipSuccess) return fail(err, err_cap, "upload failed");
+	if (mcom_qual_agree(ctx, d_rows, n, (uint32_t)L, (uint64_t)L, M.d, mb, 0, ag.Q, (mcom_qual_agree_report*)ag.rep)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(ctx)); return -1; }
+	return 0;
+}
+
 // FASTQ file -> `.mcq` member file (bin/mcomz e --fastq-qual L): on GPU `device` the quality lines are gathered by
 // mcomh_fastq_qualities_to_device and coded by mcom_qual_encode; device -1 is the host twin of both.  The same bytes either way.
-int fastq_member(const char *fastq, int L, int device, const char *out_path, uint64_t *n_out, char *err, size_t err_cap, const mcomh_qual_lossy_spec *spec = nullptr, mcomh_qual_lossy_report *rep = nullptr)
+int fastq_member(const char *fastq, int L, int device, const char *out_path, uint64_t *n_out, char *err, size_t err_cap, const mcomh_qual_lossy_spec *spec = nullptr, mcomh_qual_lossy_report *rep = nullptr,
+                 const AgreeArgs *agree = nullptr)
 {
 	if (!fastq || !out_path) return fail(err, err_cap, "null pointer");
 	if (spec && !spec_ok(spec)) return fail(err, err_cap, "not a lossy spec the transform takes");
@@ -340,6 +375,7 @@ int fastq_member(const char *fastq, int L, int device, const char *out_path, uin
 	if (device < 0) {
 		std::vector<uint8_t> rows;
 		if (host_qualities(fastq, L, rows, n, err, err_cap)) return -1;
+		if (agree && agree_host(*agree, rows.data(), n, L, err, err_cap)) return -1;
 		if (spec && mcomh_qual_transform(rows.data(), n, (uint32_t)L, (uint64_t)L, spec, rep)) return fail(err, err_cap, "the lossy transform failed");
 		out.resize(mcomh_qual_bound(n, (uint32_t)L));
 		if (mcomh_qual_encode(rows.data(), n, (uint32_t)L, (uint64_t)L, out.data(), out.size(), &len, 0)) return fail(err, err_cap, "the quality coder failed");
@@ -350,6 +386,7 @@ int fastq_member(const char *fastq, int L, int device, const char *out_path, uin
 		struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d_out = nullptr; ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d_out) (void)hipFree(d_out); if (ctx) mcom_destroy(ctx); } } D;
 		if (mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
 		if (hipMalloc((void**)&D.d_out, cap + 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
+		if (agree && agree_device(*agree, D.ctx, in.d, n, L, err, err_cap)) return -1;
 		if (spec && mcom_qual_transform(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)spec, (mcom_qual_lossy_report*)rep)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		if (mcom_qual_encode(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, D.d_out, cap, &len, 0)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		out.resize(len);
@@ -366,7 +403,7 @@ int fastq_member(const char *fastq, int L, int device, const char *out_path, uin
 // order is a permutation of the records; then the coder.  No member is written when the order's size is no multiple of 4, its entry
 // count differs from the record count, or a flag is raised.  On the GPU the matrix is held twice: refused when the card has no room.
 int fastq_member_ordered(const char *fastq, int L, int device, const char *order_path, const char *out_path, uint64_t *n_out, char *err, size_t err_cap, const mcomh_qual_lossy_spec *spec = nullptr,
-                         mcomh_qual_lossy_report *rep = nullptr)
+                         mcomh_qual_lossy_report *rep = nullptr, const AgreeArgs *agree = nullptr)
 {
 	if (!fastq || !out_path || !order_path) return fail(err, err_cap, "null pointer");
 	if (spec && !spec_ok(spec)) return fail(err, err_cap, "not a lossy spec the transform takes");
@@ -391,6 +428,7 @@ int fastq_member_ordered(const char *fastq, int L, int device, const char *order
 		std::vector<uint8_t> sorted(rows.size() + 1);
 		if (mcomh_qual_gather_rows(rows.data(), n, (uint32_t)L, (uint64_t)L, order.data(), n, sorted.data(), (uint64_t)L, &flag)) return fail(err, err_cap, "the row gather failed");
 		if (flag) return flagged();
+		if (agree && agree_host(*agree, sorted.data(), n, L, err, err_cap)) return -1;
 		if (spec && mcomh_qual_transform(sorted.data(), n, (uint32_t)L, (uint64_t)L, spec, rep)) return fail(err, err_cap, "the lossy transform failed");
 		out.resize(mcomh_qual_bound(n, (uint32_t)L));
 		if (mcomh_qual_encode(sorted.data(), n, (uint32_t)L, (uint64_t)L, out.data(), out.size(), &len, 0)) return fail(err, err_cap, "the quality coder failed");
@@ -415,6 +453,7 @@ int fastq_member_ordered(const char *fastq, int L, int device, const char *order
 		if (mcom_qual_gather_rows(D.ctx, in.d, n, (uint32_t)L, (uint64_t)L, D.d_order, n, D.d_sorted, (uint64_t)L, d_flag)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(err, err_cap, "cannot read the flag word");
 		if (flag) return flagged();
+		if (agree && agree_device(*agree, D.ctx, D.d_sorted, n, L, err, err_cap)) return -1;
 		if (spec && mcom_qual_transform(D.ctx, D.d_sorted, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)spec, (mcom_qual_lossy_report*)rep)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		if (mcom_qual_encode(D.ctx, D.d_sorted, n, (uint32_t)L, (uint64_t)L, D.d_out, cap, &len, 0)) { if (err && err_cap) snprintf(err, err_cap, "%s", mcom_last_error(D.ctx)); return -1; }
 		out.resize(len);
@@ -446,6 +485,18 @@ extern "C" int mcomh_fastq_quality_member_lossy(const char *fastq, int L, int de
 		return order_path ? fastq_member_ordered(fastq, L, device, order_path, out_path, n, err, err_cap, spec, report) : fastq_member(fastq, L, device, out_path, n, err, err_cap, spec, report);
 	} catch (...) { return -1; }
 }
+extern "C" int mcomh_fastq_quality_member_agree(const char *fastq, int L, int device, const char *order_path, const char *mask_path, uint64_t first_mask_row, uint32_t Q,
+                                                const mcomh_qual_lossy_spec *spec, const char *out_path, uint64_t *n, mcomh_qual_agree_report *agree_report,
+                                                mcomh_qual_lossy_report *report, char *err, size_t err_cap)
+{
+	if (err && err_cap) err[0] = 0;
+	if (agree_report) memset(agree_report, 0, sizeof *agree_report);
+	try {
+		const AgreeArgs ag = {mask_path, first_mask_row, Q, agree_report};
+		if (!mask_path || Q > 93) return fail(err, err_cap, "agree: a mask file and a Phred value 0 .. 93");
+		return order_path ? fastq_member_ordered(fastq, L, device, order_path, out_path, n, err, err_cap, spec, report, &ag) : fastq_member(fastq, L, device, out_path, n, err, err_cap, spec, report, &ag);
+	} catch (...) { return -1; }
+}
 extern "C" int mcomh_qual_pack_file_lossy(const char *in_path, const char *out_path, int L, int device, const mcomh_qual_lossy_spec *spec, mcomh_qual_lossy_report *report)
 {
 	try { return qual_file(in_path, out_path, L, device, true, spec, report); } catch (...) { return -1; }
@@ -460,6 +511,29 @@ int mcom_qual_lossy_apply_marker(const char *folder, int device, uint8_t *d_rows
 	struct Ctx { mcom_ctx *ctx = nullptr; ~Ctx() { if (ctx) { (void)mcom_sync(ctx); mcom_destroy(ctx); } } } C;
 	if (hipSetDevice(device) != hipSuccess || mcom_create(&C.ctx, device, nullptr) != MCOM_OK) { C.ctx = nullptr; fprintf(stderr, "minicom verify: cannot create a context on the GPU\n"); return -1; }
 	if (mcom_qual_transform(C.ctx, d_rows, n, (uint32_t)L, (uint64_t)L, (const mcom_qual_lossy_spec*)&spec, nullptr)) { fprintf(stderr, "minicom verify: %s\n", mcom_last_error(C.ctx)); return -1; }
+	return 0;
+}
+// FOLDER/qual_agree.txt, when there: the mask rebuilt from the folder on the device, its rows [first_mask_row, + n) applied to the rows at d_rows (mcom_fastq.hpp)
+int mcom_qual_agree_apply_marker(const char *folder, int device, uint8_t *d_rows, size_t n, int L, uint64_t first_mask_row)
+{
+	uint32_t Q = 0, C = 0;
+	const int have = mcomh_qual_agree_marker(folder, &Q, &C);
+	if (have < 0) { fprintf(stderr, "minicom verify: %s/qual_agree.txt does not hold `Q C` (0 .. 93, 1 .. 255) and a newline\n", folder); return -1; }
+	if (!have) return 0;
+	std::vector<uint8_t> mask;
+	uint64_t m_rows = 0; int m_L = 0;
+	FILE *f = fopen((std::string(folder) + "/ids.bin.0").c_str(), "rb");
+	if (f) fclose(f);
+	if (mcom_agree_mask_gpu(folder, f != nullptr, (int)C, device, mask, &m_rows, &m_L)) { fprintf(stderr, "minicom verify: the agreement mask of %s cannot be rebuilt\n", folder); return -1; }
+	if (m_L != L) { fprintf(stderr, "minicom verify: the agreement mask of %s has rows of %d columns, the quality rows %d\n", folder, m_L, L); return -1; }
+	// a file of more records than the mask has rows is not refused: the rows the mask knows go through it, and the comparison reports the other count
+	if (first_mask_row > m_rows) first_mask_row = m_rows;
+	if (n > m_rows - first_mask_row) n = (size_t)(m_rows - first_mask_row);
+	const size_t mb = (size_t)(L + 7) / 8;
+	struct Dev { mcom_ctx *ctx = nullptr; uint8_t *d = nullptr; ~Dev() { if (ctx) (void)mcom_sync(ctx); if (d) (void)hipFree(d); if (ctx) mcom_destroy(ctx); } } D;
+	if (hipSetDevice(device) != hipSuccess || mcom_create(&D.ctx, device, nullptr) != MCOM_OK) { D.ctx = nullptr; fprintf(stderr, "minicom verify: cannot create a context on the GPU\n"); return -1; }
+	if (hipMalloc((void**)&D.d, n * mb + 16) != hipSuccess || (n && hipMemcpy(D.d, mask.data() + (size_t)first_mask_row * mb, n * mb, hipMemcpyHostToDevice) != hipSuccess)) { fprintf(stderr, "minicom verify: the card has no room for the agreement mask\n"); return -1; }
+	if (mcom_qual_agree(D.ctx, d_rows, n, (uint32_t)L, (uint64_t)L, D.d, mb, 0, Q, nullptr)) { fprintf(stderr, "minicom verify: %s\n", mcom_last_error(D.ctx)); return -1; }
 	return 0;
 }
 extern "C" int mcomh_device_copy(void *d_dst, const void *d_src, size_t bytes)

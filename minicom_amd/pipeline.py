@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from .hip import McomError, QualLossyReport, QualLossySpec, load_library
+from .hip import McomError, QualAgreeReport, QualLossyReport, QualLossySpec, load_library
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -128,6 +128,11 @@ def load_host_library():
     L.mcomh_fastq_quality_member_lossy.restype = i32
     L.mcomh_fastq_quality_member_lossy.argtypes = [cp, i32, i32, cp, C.POINTER(QualLossySpec), cp, C.POINTER(u64), C.POINTER(QualLossyReport), C.c_char_p, sz]
     L.mcomh_qual_lossy_marker.restype = i32; L.mcomh_qual_lossy_marker.argtypes = [cp, C.POINTER(QualLossySpec), C.c_char_p, sz]
+    L.mcomh_agree_mask.restype = i32; L.mcomh_agree_mask.argtypes = [cp, i32, cp, i32, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)]
+    L.mcomh_qual_agree.restype = i32; L.mcomh_qual_agree.argtypes = [vp, u64, u32, u64, vp, u64, u64, u32, C.POINTER(QualAgreeReport)]
+    L.mcomh_fastq_quality_member_agree.restype = i32
+    L.mcomh_fastq_quality_member_agree.argtypes = [cp, i32, i32, cp, cp, u64, u32, C.POINTER(QualLossySpec), cp, C.POINTER(u64), C.POINTER(QualAgreeReport), C.POINTER(QualLossyReport), C.c_char_p, sz]
+    L.mcomh_qual_agree_marker.restype = i32; L.mcomh_qual_agree_marker.argtypes = [cp, C.POINTER(u32), C.POINTER(u32)]
     L.mcomh_decompress_fastq_reordered.restype = i32; L.mcomh_decompress_fastq_reordered.argtypes = [cp, cp, C.POINTER(u64)]
     L.mcomh_decompress_fastq_reordered_gpu.restype = i32; L.mcomh_decompress_fastq_reordered_gpu.argtypes = [cp, cp, C.POINTER(u64), i32]
     L.mcomh_decompress_fastq_pe.restype = i32; L.mcomh_decompress_fastq_pe.argtypes = [cp, cp, cp, C.POINTER(u64)]
@@ -201,6 +206,8 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     # lossy quality values (`minicom -b`, host/mcom_qual_lossy.cpp)
                     "mcomh_qual_lossy_parse", "mcomh_qual_lossy_print", "mcomh_qual_transform", "mcomh_qual_pack_file_lossy", "mcomh_fastq_quality_member_lossy",
                     "mcomh_qual_lossy_marker",
+                    # consensus-guided lossy quality values (`minicom -a`, host/mcom_agree.cpp)
+                    "mcomh_agree_mask", "mcomh_qual_agree", "mcomh_fastq_quality_member_agree", "mcomh_qual_agree_marker",
                     # BGZF output (`minicom -d -z`, host/mcom_bgzf.cpp)
                     "mcomh_bgzf_bound", "mcomh_bgzf_encode", "mcomh_bgzf_file",
                     # BGZF input inflated on the GPU (host/mcom_gzip_gpu.cpp)
@@ -457,6 +464,72 @@ def qual_lossy_marker(folder: str):
     if rc < 0:
         raise McomError(f"{folder}/qual_lossy.txt does not hold a lossy spec and a newline")
     return out.value.decode() if rc else None
+
+
+# ---- consensus-guided lossy quality values (`minicom -a Q[:C]`, host/mcom_agree.cpp) ----
+def agree_mask(folder: str, C_min: int = 3, device: int | None = None, out_path: str | None = None):
+    """mcomh_agree_mask: the agreement mask of the stream files in `folder` (a default-mode or a -p archive): a uint8 matrix [n, ceil(L / 8)],
+    row j beside row j of the decoder's image, column i in bit i & 7 of byte i >> 3.  Returns (mask, L, bits_set).  device=None: the host
+    decoders' member loops; an integer: mcom_agree_coverage and mcom_agree_mask on that GPU -- the same bytes.  out_path: where the
+    mask file is left (otherwise a temporary file that is removed).  McomError for a folder the matching decoder refuses, a paired-end
+    default-mode archive, a ragged one, or C_min outside 1 .. 255; no file is left then."""
+    import tempfile
+    own = out_path is None
+    if own:
+        fd, out_path = tempfile.mkstemp(suffix=".mask"); os.close(fd); os.remove(out_path)
+    n, L, bits = C.c_uint64(), C.c_int32(), C.c_uint64()
+    try:
+        if load_host_library().mcomh_agree_mask(os.fsencode(folder), int(C_min), os.fsencode(out_path), -1 if device is None else int(device), C.byref(n), C.byref(L), C.byref(bits)):
+            raise McomError(f"{folder}: no agreement mask (not a complete, consistent default-mode or -p archive, or a coverage outside 1 .. 255)")
+        mb = (int(L.value) + 7) // 8
+        mask = np.fromfile(out_path, dtype=np.uint8).reshape(int(n.value), mb)
+    finally:
+        if own and os.path.exists(out_path):
+            os.remove(out_path)
+    return mask, int(L.value), int(bits.value)
+
+
+def qual_agree(rows, mask, Q: int, first_mask_row: int = 0, device: int | None = None):
+    """The agreement transform: rows uint8 [n, L] is left alone; returns (the matrix with 33 + Q wherever bit i of
+    mask row first_mask_row + r is set, the report {"changed", "sum_abs", "sum_sq", "max_abs", "mask_bits"}).  mask: uint8 [m, >= ceil(L / 8)].
+    device=None: mcomh_qual_agree, the host twin; an integer: mcom_qual_agree on that GPU -- the same bytes and the same report."""
+    rows = np.asarray(rows); mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    if rows.ndim != 2 or rows.dtype != np.uint8 or mask.ndim != 2 or first_mask_row < 0 or first_mask_row + rows.shape[0] > mask.shape[0]:
+        raise McomError("qual_agree: a uint8 matrix of rows and a mask with a row for each of them")
+    n, L = rows.shape
+    if device is not None:
+        import torch
+        from .hip import Context
+        dev = f"cuda:{int(device)}"
+        out, rep = Context(int(device)).qual_agree(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(mask).to(dev), int(Q), first_mask_row=int(first_mask_row))
+        return out.cpu().numpy(), rep
+    out = np.array(rows, dtype=np.uint8, order="C")
+    r = QualAgreeReport()
+    if load_host_library().mcomh_qual_agree(out.ctypes.data if n else None, n, L, L, mask.ctypes.data if mask.size else None, mask.shape[1], int(first_mask_row), int(Q), C.byref(r)):
+        raise McomError("qual_agree: Q 0 .. 93, rows of 1 .. 256 bytes and mask rows of at least ceil(L / 8) bytes")
+    return out, r.as_dict()
+
+
+def qual_agree_marker(folder: str):
+    """mcomh_qual_agree_marker: (Q, C) of FOLDER/qual_agree.txt, None without the file; McomError when it holds anything but `Q C` and a newline."""
+    q, c = C.c_uint32(), C.c_uint32()
+    rc = load_host_library().mcomh_qual_agree_marker(os.fsencode(folder), C.byref(q), C.byref(c))
+    if rc < 0:
+        raise McomError(f"{folder}/qual_agree.txt does not hold `Q C` (0 .. 93, 1 .. 255) and a newline")
+    return (int(q.value), int(c.value)) if rc else None
+
+
+def fastq_quality_member_agree(fastq: str, L: int, out_path: str, mask_path: str, Q: int, first_mask_row: int = 0, device: int | None = None, order_path: str | None = None, lossy=None):
+    """mcomh_fastq_quality_member_agree: fastq_quality_member with the agreement transform behind the gather and in front of the lossy
+    transform (when one is given).  Returns (records, agreement report, lossy report or None)."""
+    err = C.create_string_buffer(320)
+    n = C.c_uint64(); ar = QualAgreeReport(); lr = QualLossyReport()
+    s = qual_lossy_spec(lossy) if lossy is not None else None
+    if load_host_library().mcomh_fastq_quality_member_agree(os.fsencode(fastq), int(L), -1 if device is None else int(device), None if order_path is None else os.fsencode(order_path),
+                                                            os.fsencode(mask_path), int(first_mask_row), int(Q), C.byref(s) if s is not None else None, os.fsencode(out_path), C.byref(n),
+                                                            C.byref(ar), C.byref(lr), err, 320):
+        raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
+    return int(n.value), ar.as_dict(), (lr.as_dict() if s is not None else None)
 
 
 def fastq_quality_member(fastq: str, L: int, out_path: str, device: int | None = None, order_path: str | None = None, lossy=None):

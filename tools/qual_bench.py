@@ -17,7 +17,16 @@ measures the lossy transform instead (`minicom -b`), per
 (wall clock around the synchronous call -- its fill, its launch, the 32 bytes of the report coming back and the wait -- against the byte
 model of 2 n L bytes moved), the report, and the member step `mcomz e --fastq-qual L --gpu` over a FASTQ file of the same qualities with
 and without `--lossy SPEC` (wall clock around the child process, sizes of the members, whether the host twin writes the same member
-where --host-check is given).  Median and spread (max - min) of --repeats runs after one warm-up."""
+where --host-check is given).  Median and spread (max - min) of --repeats runs after one warm-up.
+
+  python tools/qual_bench.py --rows 2000000 --len 150 --agree 40:3 40:2 [--lossy ill8] [--repeats 3] [--dir DIR] [--out FILE] [--sizes FILE]
+
+measures the consensus-guided transform (`minicom -a Q[:C]`) on a -p archive of synthetic reads (coverage 30,
+substitution rate 0.5 %) with the synthetic qualities: per Q:C the share of mask bits set, the time of the mask step (`decompress
+--agree-mask --gpu`) against the plain stream-files -> rows decode of the same folder (`decompress --gpu`), the time of the quality-member
+step with and without `--agree`, and the size of `qual.mcq` against the member made without it; with --lossy also Q:C of the first --agree
+argument followed by SPEC.  Wall clock around the child processes.  The generator's qualities are independent of its base errors: the
+sizes say nothing about real instrument data.  --sizes: the sizes alone as JSON."""
 import argparse
 import bz2
 import filecmp
@@ -125,6 +134,57 @@ def lossy_main(a):
         shutil.rmtree(work, ignore_errors=True)
 
 
+def agree_main(a):
+    from minicom_amd import synth
+    from minicom_amd.pipeline import Pipeline
+    DECOMPRESS = os.path.join(ROOT, "bin", "decompress")
+    work = tempfile.mkdtemp(prefix="qual_bench_", dir=a.dir)
+    try:
+        L, rows = a.L, a.rows
+        reads = synth.synth_reads(1002, rows, L)
+        q = synth_quals(5, rows, L, a.binned)
+        fq = os.path.join(work, "q.fastq")
+        fastq_file(fq, q)                                                  # (the member step reads the quality lines only)
+        folder = os.path.join(work, "streams")
+        os.mkdir(folder)
+        p = Pipeline(reads, host_threads=16); p.pre_process()
+        try:
+            p.cluster_dump(folder, order=True, paired=False)
+        finally:
+            p.close()
+
+        def runs(cmd):
+            timed(cmd, stdout=subprocess.DEVNULL)                          # warm-up
+            t = [timed(cmd, stdout=subprocess.DEVNULL) for _ in range(a.repeats)]
+            return {"ms": round(statistics.median(t), 1), "spread_ms": round(max(t) - min(t), 1)}
+        res = {"rows": rows, "L": L, "repeats": a.repeats, "what": "synthetic reads (coverage 30, 0.5 % substitutions) and synthetic qualities, independent of each other", "agree": {}}
+        res["decode_rows"] = runs([DECOMPRESS, "--gpu", folder, os.path.join(work, "reads.out"), "false", "true", "1"])
+        plain = os.path.join(work, "plain.mcq")
+        res["member_plain"] = dict(runs([MCOMZ, "e", "--fastq-qual", str(L), "--gpu", fq, plain]), bytes=os.path.getsize(plain))
+        sizes = {"rows": rows, "L": L, "qual.mcq": os.path.getsize(plain)}
+        legs = [(s, None) for s in a.agree] + ([(a.agree[0], spec) for spec in a.lossy] if a.lossy else [])
+        for spec, lossy in legs:
+            Q, C = (spec.split(":") + ["3"])[:2]
+            mask, out = os.path.join(work, "m.mask"), os.path.join(work, "agree.mcq")
+            r = {"mask_step": runs([DECOMPRESS, "--agree-mask", "--gpu", folder, C, mask])}
+            n_rows, _, bits = subprocess.run([DECOMPRESS, "--agree-mask", "--gpu", folder, C, mask], check=True, capture_output=True, text=True).stdout.split()
+            r["mask_bits_share"] = round(int(bits) / (int(n_rows) * L), 4)
+            r["member"] = dict(runs([MCOMZ, "e", "--fastq-qual", str(L), "--agree", Q, mask] + (["--lossy", lossy] if lossy else []) + ["--gpu", fq, out]), bytes=os.path.getsize(out))
+            name = "-a %s:%s" % (Q, C) + (" -b %s" % lossy if lossy else "")
+            res["agree"][name] = r
+            sizes[name] = {"qual.mcq": r["member"]["bytes"], "mask_bits_share": r["mask_bits_share"]}
+        res["ok"] = True
+        line = json.dumps(res)
+        print(line)
+        for path, text in ((a.out, line), (a.sizes, json.dumps(sizes))):
+            if path:
+                with open(path, "w") as f:
+                    f.write(text + "\n")
+        return 0
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -136,7 +196,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--lossy", nargs="+", default=None, metavar="SPEC")
     ap.add_argument("--host-check", action="store_true")
+    ap.add_argument("--agree", nargs="+", default=None, metavar="Q[:C]")
+    ap.add_argument("--sizes", default=None)
     a = ap.parse_args()
+    if a.agree:
+        return agree_main(a)
     if a.lossy:
         return lossy_main(a)
     from minicom_amd import pipeline
