@@ -44,6 +44,12 @@ int mcom_screen_fallbacks(const mcom_ctx *ctx);
  * workgroup lists the (singleton, pair) tasks whose keys this share owns on a stack in LDS and a thread takes one task (k_realign_owned);
  * 1 = the kernel of the whole index with several pairs per lane, a lane dropping the pairs it does not own.  Same claims either way.  */
 int mcom_set_lookup_route(mcom_ctx *ctx, int route);
+/* mcom_find_next_candidates / _new / _ord test their (query, hit) pairs and list the passing ones in one of two ways.  route 0 = the
+ * default: the evaluation kernel itself leaves the passing candidates in pair order (a run per workgroup, gathered behind a scan of the
+ * workgroups' counts), one lane per pair; 1 = a flag per pair, a scan over the flags and a second kernel that looks the passing pairs up
+ * again; 4, 8, 16 = route 0 with a group of that many lanes per pair, a lane comparing every G-th word of the overlap (measured: slower
+ * than one lane at every G, csrc/contigs.hip).  Same candidates in the same order, same counts every way.                              */
+int mcom_set_eval_route(mcom_ctx *ctx, int route);
 /* The entropy stage (csrc/entropy.hip) has two kernels whose output never leaves the library: the histograms are only seen through the
  * 12-bit tables of the chosen model, the per-segment CRCs only after the host has joined them.  These run the very launches of
  * mcom_rans_encode / mcom_rans_decode (same grid, same aligned / byte-wise choice from the pointer, same cleared table) and hand the

@@ -380,6 +380,12 @@ extern "C" int mcom_set_lookup_route(mcom_ctx *ctx, int route)
 	ctx->lookup_route = route;
 	return MCOM_OK;
 }
+extern "C" int mcom_set_eval_route(mcom_ctx *ctx, int route)
+{
+	if (!ctx || (route != 0 && route != 1 && route != 4 && route != 8 && route != 16)) return MCOM_E_ARG;
+	ctx->eval_route = route;
+	return MCOM_OK;
+}
 extern "C" int mcom_set_index_capacity(mcom_ctx *ctx, int entries)
 {
 	if (!ctx) return MCOM_E_ARG;

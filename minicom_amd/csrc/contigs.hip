@@ -1038,6 +1038,104 @@ __global__ void k_fn_emit(const uint32_t *__restrict__ first, const mcom_mm128 *
 	mcom_mm128 v; v.x = qy ? qy[i] : q[i].y; v.y = irec[first[i] + (p - pair_off[i])].y;   // x = query y (contig i, pos_ori, dir), y = hit y
 	out[here] = v;
 }
+// Round 19: the evaluation leaves the passing candidates itself.  k_fn_eval wrote a flag per pair, a scan ran over all the flags and
+// k_fn_emit started a thread per pair again to look the passing ones up a second time (pass_pre twice, pair_q, pair_off, first, qy, irec).
+// Here the lane that tested a pair has {query y, hit y} in registers: a workgroup ballots its passing pairs and writes them, in pair order,
+// at its own base in `stage` (the index of its first pair; written only where a pair passes) and its count to wg_cnt; a scan over the
+// counts (256 / G times fewer than pairs) and k_fn_gather put the runs into the output.  Scan + emit 2.45 -> 0.42 ms per step.
+// G lanes per pair: sub-lane s of a group takes the words s, s + G, ... of the overlap.  One side of the comparison is always
+// word-aligned (lo = max(d, 0) is zero on A's side or makes p - d zero on B's), so a lane loads one word of each side and gets the shifted
+// side's following word from sub-lane s + 1; only the lane with the group's or the overlap's last word loads that one itself (the same
+// words match_pro_packed reads: nothing behind a contig's padding word, and a sub-lane without a word in range loads nothing).  The group
+// sums its popcounts after every G words and stops above cbthr -- what counts is mis <= cbthr, as there.  G = 1 is match_pro_packed's own
+// walk and the DEFAULT: the groups were built to cut the lines a wave's load touches and they LOSE at every G, in every round (first
+// round, 119 M pairs: 2.96 ms with G = 1, 5.50 / 8.22 / 15.10 with 4 / 8 / 16; profiles/r19_find_next.txt) -- the time follows the number
+// of lanes, so what a pair costs is not the words of its overlap but the chain of look-ups in front of them (pair_q -> first, qy -> irec
+// -> coff, clen -> words), which every lane of a group walks again.  4, 8 and 16 stay behind mcom_set_eval_route (tests).
+static const int FN_EVAL_G = 1;
+template <int G>
+__global__ __launch_bounds__(256) void k_fn_eval_grp(const uint32_t *__restrict__ first, const mcom_mm128 *__restrict__ irec,
+                          const mcom_mm128 *__restrict__ q, const uint64_t *__restrict__ qy, const uint32_t *__restrict__ pair_off, const uint32_t *__restrict__ pair_q, uint32_t n_pairs,
+                          const uint64_t *__restrict__ cbits, const uint64_t *__restrict__ coff, const uint32_t *__restrict__ clen,
+                          int cbthr, uint32_t new_lo, uint32_t new_span, mcom_mm128 *__restrict__ stage, uint32_t *__restrict__ wg_cnt)
+{
+	constexpr uint32_t PPW = 256 / G;                                              // pairs per workgroup
+	__shared__ uint32_t wave_cnt[4];
+	const uint32_t sub = threadIdx.x & (G - 1);
+	const size_t p = (size_t)blockIdx.x * PPW + threadIdx.x / G;
+	uint64_t my = 0, y = 0;
+	bool ok = false;
+	if (p < n_pairs) {
+		const uint32_t i = pair_q[p];
+		const uint32_t u = (uint32_t)p - pair_off[i], s = first[i];
+		my = qy ? qy[i] : q[i].y; y = irec[s + u].y;
+		const uint32_t ci = (uint32_t)(my >> 32), pos_ori = (uint32_t)my >> 1;
+		const uint32_t cj = (uint32_t)(y >> 32), pos = (uint32_t)y >> 1;
+		if (cj != ci && ((my ^ y) & 1) == 0 && (new_span == 0 || fn_is_new(ci, new_lo, new_span) || fn_is_new(cj, new_lo, new_span))) {
+			const uint64_t *A = cbits + coff[ci], *B = cbits + coff[cj];
+			const long lenA = (long)clen[ci], lenB = (long)clen[cj];
+			const long d = (long)(int)pos_ori - (long)(int)pos;                      // A[p] is compared with B[p - d], p in [lo, hi)
+			const long lo = d > 0 ? d : 0;
+			long hi = lenB + d; if (hi > lenA) hi = lenA;
+			const long nb_all = hi - lo;
+			const uint32_t nw = nb_all > 0 ? (uint32_t)((nb_all + 31) >> 5) : 0u;    // words of the overlap
+			const long ahead = d > 0 ? d : -d;                                       // the shifted side starts this many bases in, the other at 0
+			const uint64_t *S = (d > 0 ? A : B) + (ahead >> 5), *T = d > 0 ? B : A;
+			const int sh = (int)((2 * ahead) & 63);
+			const uint32_t thr = (uint32_t)cbthr;
+			uint32_t mis = 0;
+			for (uint32_t k0 = 0; k0 < nw; k0 += G) {                                // (everything that steers the loop is the same in all lanes of a group)
+				const uint32_t k = k0 + sub;
+				const bool have = k < nw;
+				uint64_t ws = 0, wt = 0;
+				if (have) { ws = S[k]; wt = T[k]; }
+				uint64_t x = ws;
+				if (sh) {
+					uint64_t nx = 0;
+					if (G > 1) nx = __shfl_down((unsigned long long)ws, 1, G);
+					if (have && (sub == G - 1 || k + 1 == nw)) nx = S[k + 1];
+					x = (ws >> sh) | (nx << (64 - sh));
+				}
+				x ^= wt;
+				x = (x | (x >> 1)) & 0x5555555555555555ull;
+				if (k + 1 == nw) { const long nb = nb_all - 32 * (long)k; if (nb < 32) x &= (1ull << (2 * nb)) - 1; }
+				uint32_t c = have ? (uint32_t)__popcll(x) : 0u;
+#pragma unroll
+				for (int o = G / 2; o; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, G);
+				mis += c;
+				if (mis > thr) break;
+			}
+			ok = mis <= thr;
+		}
+	}
+	const bool lead = ok && sub == 0;
+	const unsigned long long bal = __ballot(lead);
+	const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	if (lane == 0) wave_cnt[wv] = (uint32_t)__popcll(bal);
+	__syncthreads();
+	uint32_t before = 0, tot = 0;
+#pragma unroll
+	for (uint32_t w = 0; w < 4; ++w) { const uint32_t c = wave_cnt[w]; if (w < wv) before += c; tot += c; }
+	if (lead) {
+		mcom_mm128 v; v.x = my; v.y = y;                                            // x = query y (contig i, pos_ori, dir), y = hit y
+		stage[(size_t)blockIdx.x * PPW + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1))] = v;
+	}
+	if (threadIdx.x == 0) {
+		wg_cnt[blockIdx.x] = tot;
+		if (blockIdx.x == 0) wg_cnt[gridDim.x] = 0;                                 // the scan over the counts and this word leaves the number of passing pairs here
+	}
+}
+// eight lanes (32 where a run has up to 256 records) copy the run of one evaluation workgroup to its place in the output (wg_off: the
+// scanned counts)
+template <int G>
+__global__ void k_fn_gather(const mcom_mm128 *__restrict__ stage, const uint32_t *__restrict__ wg_off, uint32_t n_wg, size_t cap, mcom_mm128 *__restrict__ out)
+{
+	constexpr uint32_t PPW = 256 / G, LPR = G == 1 ? 32 : 8;
+	const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, w = t / LPR;
+	if (w >= n_wg) return;
+	const uint32_t o0 = wg_off[w], n = wg_off[w + 1] - o0;
+	for (uint32_t r = (uint32_t)(t % LPR); r < n; r += LPR) { const size_t o = (size_t)o0 + r; if (o < cap) out[o] = stage[w * PPW + r]; }
+}
 
 extern "C" int mcom_find_next_candidates(mcom_ctx *ctx, const mcom_idx *mi, const mcom_mm128 *d_query, size_t n_query,
                                          const uint64_t *d_cbits, const uint64_t *d_coff, const uint32_t *d_clen, int cbthr,
@@ -1116,30 +1214,45 @@ static int find_next_impl(mcom_ctx *ctx, const mcom_idx *mi, const mcom_mm128 *d
 	if (h_counts) h_counts[0] = n_pairs;
 	if (n_pairs == 0) return MCOM_OK;
 	// pass 2: evaluate pairs
+	// route 1 (mcom_set_eval_route): a flag per pair, a scan over the flags, k_fn_emit (G = 0 below); otherwise G lanes per pair, the candidates
+	// staged by the evaluation itself (16 bytes per pair, written where a pair passes) and a count per workgroup of 256 / G pairs to scan
+	const int G = ctx->eval_route == 1 ? 0 : ctx->eval_route ? ctx->eval_route : FN_EVAL_G;
+	const size_t n_cnt = G ? ((size_t)n_pairs + 256 / G - 1) / (256 / G) : (size_t)n_pairs;   // what the scan runs over (+ 1 for the total)
 	uint32_t *pass = nullptr, *pair_q = nullptr;
-	const size_t scr2_b = (mcom_scan_scratch_elems(n_pairs) * 4 + 1024 + 255) & ~(size_t)255;
-	hipError_t e = mcom_dmalloc(&pass, ((size_t)n_pairs + 1) * 4);
+	mcom_mm128 *stage = nullptr;
+	const size_t scr2_b = (mcom_scan_scratch_elems(n_cnt) * 4 + 1024 + 255) & ~(size_t)255;
+	hipError_t e = mcom_dmalloc(&pass, (n_cnt + 1) * 4);
 	if (e == hipSuccess) e = mcom_dmalloc(&pair_q, (size_t)n_pairs * 4);
-	auto cleanup = [&]() { mcom_dfree_later(ctx, pass); mcom_dfree_later(ctx, pair_q); };
+	if (e == hipSuccess && G) e = mcom_dmalloc(&stage, (size_t)n_pairs * sizeof(mcom_mm128));
+	auto cleanup = [&]() { mcom_dfree_later(ctx, pass); mcom_dfree_later(ctx, pair_q); mcom_dfree_later(ctx, stage); };
 	if (e != hipSuccess) { cleanup(); return mcom_fail(ctx, MCOM_E_NOMEM, "candidate buffers: %s", hipGetErrorString(e)); }
 	hipError_t e1 = hipSuccess;
 	rc = mcom_ws_reserve(ctx, scr2_b);
 	if (rc) { cleanup(); return rc; }
-	const unsigned pb = (unsigned)(((size_t)n_pairs + 255) / 256);
+	const unsigned pb = (unsigned)(G ? n_cnt : ((size_t)n_pairs + 255) / 256);
+#define FN_EVAL_GRP(GG) MCOM_LAUNCH((k_fn_eval_grp<GG>), dim3(pb), dim3(256), 0, ctx->stream, first, mi->rec, d_query, (const uint64_t*)qy, pair_off, pair_q, n_pairs, \
+	                                d_cbits, d_coff, d_clen, cbthr, new_lo, new_span, stage, pass)
 	{ McomProfScope ps_(ctx, PROF_FIND_NEXT);
 	MCOM_LAUNCH(k_fn_expand, dim3(qb), dim3(256), 0, ctx->stream, pair_off, n_query, pair_q);
-	MCOM_LAUNCH(k_fn_eval, dim3(pb), dim3(256), 0, ctx->stream, first, mi->rec, d_query, (const uint64_t*)qy, pair_off, pair_q, n_pairs, d_cbits, d_coff, d_clen, cbthr, new_lo, new_span, pass); }
+	if (G == 1) FN_EVAL_GRP(1); else if (G == 4) FN_EVAL_GRP(4); else if (G == 8) FN_EVAL_GRP(8); else if (G == 16) FN_EVAL_GRP(16);
+	else MCOM_LAUNCH(k_fn_eval, dim3(pb), dim3(256), 0, ctx->stream, first, mi->rec, d_query, (const uint64_t*)qy, pair_off, pair_q, n_pairs, d_cbits, d_coff, d_clen, cbthr, new_lo, new_span, pass); }
+#undef FN_EVAL_GRP
 	uint32_t n_pass = 0;
-	rc = mcom_scan_u32(ctx, pass, pass, (size_t)n_pairs + 1, (uint32_t*)ctx->ws);
+	rc = mcom_scan_u32(ctx, pass, pass, n_cnt + 1, (uint32_t*)ctx->ws);
 	if (rc) { cleanup(); return rc; }
-	hipError_t e1b = mcom_d2h_async(ctx, &n_pass, pass + n_pairs, 4);               // (the scan's own total: no copy, scan.hip)
+	hipError_t e1b = mcom_d2h_async(ctx, &n_pass, pass + n_cnt, 4);                 // (the scan's own total: no copy, scan.hip)
 	if (e1b == hipSuccess) e1b = mcom_stream_sync(ctx);
 	if (e1b != hipSuccess) { cleanup(); return mcom_fail(ctx, MCOM_E_HIP, "candidate scan: %s", hipGetErrorString(e1b)); }
 	if (h_counts) h_counts[1] = n_pass;
 	if (n_pass > cap) { cleanup(); return mcom_fail(ctx, MCOM_E_OVERFLOW, "%u passing candidates but room for %zu", n_pass, cap); }
 	if (n_pass) {
 		if (!d_out) { cleanup(); return mcom_fail(ctx, MCOM_E_ARG, "null output pointer"); }
-		MCOM_LAUNCH(k_fn_emit, dim3(pb), dim3(256), 0, ctx->stream, first, mi->rec, d_query, (const uint64_t*)qy, pair_off, pair_q, pass, n_pairs, d_out);
+		const unsigned gb = (unsigned)((n_cnt * (G == 1 ? 32 : 8) + 255) / 256);      // (k_fn_gather's lanes per run)
+		if (G == 1) MCOM_LAUNCH((k_fn_gather<1>), dim3(gb), dim3(256), 0, ctx->stream, stage, pass, (uint32_t)n_cnt, cap, d_out);
+		else if (G == 4) MCOM_LAUNCH((k_fn_gather<4>), dim3(gb), dim3(256), 0, ctx->stream, stage, pass, (uint32_t)n_cnt, cap, d_out);
+		else if (G == 8) MCOM_LAUNCH((k_fn_gather<8>), dim3(gb), dim3(256), 0, ctx->stream, stage, pass, (uint32_t)n_cnt, cap, d_out);
+		else if (G == 16) MCOM_LAUNCH((k_fn_gather<16>), dim3(gb), dim3(256), 0, ctx->stream, stage, pass, (uint32_t)n_cnt, cap, d_out);
+		else MCOM_LAUNCH(k_fn_emit, dim3(pb), dim3(256), 0, ctx->stream, first, mi->rec, d_query, (const uint64_t*)qy, pair_off, pair_q, pass, n_pairs, d_out);
 		e1 = hipGetLastError();                                                     // (d_out is complete when the stream gets there: no wait here)
 		if (e1 != hipSuccess) { cleanup(); return mcom_fail(ctx, MCOM_E_HIP, "candidate emit: %s", hipGetErrorString(e1)); }
 	}

@@ -424,6 +424,12 @@ class Context:
         self.lib.mcom_set_claim_route.restype = C.c_int; self.lib.mcom_set_claim_route.argtypes = [C.c_void_p, C.c_int]
         self._check(self.lib.mcom_set_claim_route(self._h, route))
 
+    def set_eval_route(self, route: int):
+        """Test hook of mcom_find_next_candidates*: 0 = default (one lane per pair, candidates staged by the evaluation kernel), 1 = a flag
+        per pair, a scan over the flags and k_fn_emit, 4 / 8 / 16 = the default with a group of that many lanes per pair."""
+        self.lib.mcom_set_eval_route.restype = C.c_int; self.lib.mcom_set_eval_route.argtypes = [C.c_void_p, C.c_int]
+        self._check(self.lib.mcom_set_eval_route(self._h, route))
+
     def claim_fallbacks(self) -> int:
         self.lib.mcom_claim_fallbacks.restype = C.c_int; self.lib.mcom_claim_fallbacks.argtypes = [C.c_void_p]
         return int(self.lib.mcom_claim_fallbacks(self._h))
