@@ -1008,6 +1008,27 @@ int mcom_fastq_ragged_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_byte
 int mcom_fastq_emit_ragged(mcom_ctx *ctx, const mcom_ragged_src *src, uint64_t first, uint64_t count, uint8_t *d_out, uint64_t cap,
                            uint64_t *bytes);
 
+/* ---- the digest of a FASTQ file (`minicom -K`; csrc/digest.hip, csrc/digest_model.hpp) ----
+ * A line is the bytes of a FASTQ line without its newline and without the leading '@' / '+' of lines 1 and 3.  Every hash is a pair of
+ * 64-bit words, one per seed; the definition is digest_model.hpp's and DESIGN.md's.
+ *   mcom_fastq_record_hashes  record r of this call is lines 4r .. 4r + 3 (lines_per_record 4) or line r (lines_per_record 1: a file of
+ *                             one read per line) of a line index made by mcom_decode_line_index over d_text.  d_hS, d_hQ, d_hN: arrays of
+ *                             2 * n_total words that cover ALL records of the file; the two words of record first_record + r are written:
+ *                             hS = H(sequence), hQ = H(qualities), hN = C(H(name), H(plus text)).  d_hQ and d_hN may be NULL and are not
+ *                             touched with lines_per_record 1.  Checked: '@', '+', sequence and quality lines of one length 1 .. 256, at
+ *                             most 255 bytes behind the '@' and the '+' (MCOM_FASTQ_F_NAME, _PLUS, _LENGTH, _LONG); with lines_per_record 1
+ *                             only the length.  A record that fails is flagged in the two words of d_flag as mcom_fastq_quality_rows
+ *                             does and gets no hash; nothing is read outside d_text[0 .. n_bytes).  Synchronous; below 2^32 records.
+ *   mcom_digest_reduce        the sixteen sums of n records: word 2 * key + seed, keys in the order seq.ordered.1, qual.ordered.1,
+ *                             name.ordered.1, seq.ordered.2, qual.ordered.2, name.ordered.2, seq.multiset, rec.multiset.  d_hS2 NULL: one
+ *                             file; otherwise the arrays of the second file of a pair, the same ones as of the first.  The sums of arrays
+ *                             not given are 0.  sums: HOST memory.  Synchronous.                                                        */
+int mcom_fastq_record_hashes(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_line_start, uint64_t first_record,
+                             uint64_t n_records, int lines_per_record, uint64_t n_total, uint64_t *d_hS, uint64_t *d_hQ, uint64_t *d_hN,
+                             uint32_t *d_flag);
+int mcom_digest_reduce(mcom_ctx *ctx, const uint64_t *d_hS1, const uint64_t *d_hQ1, const uint64_t *d_hN1, const uint64_t *d_hS2,
+                       const uint64_t *d_hQ2, const uint64_t *d_hN2, uint64_t n, uint64_t sums[16]);
+
 /* ---- synthetic input (bench / tests): same generator as minicom_amd/synth.py ------------------ */
 int mcom_synth_reads(mcom_ctx *ctx, uint64_t seed, uint64_t n_reads, int L, int coverage, double sub_rate,
                      uint64_t first, uint64_t count, uint8_t *d_ascii, size_t pitch);

@@ -586,6 +586,54 @@ int mcomh_fastq_quality_member_ragged(const char *fastq, int L, int device, cons
 int mcomh_fastq_emit_ragged(const mcomh_ragged_src *src, uint64_t first, uint64_t count, uint8_t *out, uint64_t cap, uint64_t *bytes);
 int mcomh_verify_ragged_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report rep[5], int present[5]);
 
+/* ---- self-checking archives: `minicom -K` stores a digest of the input, `minicom -d` checks it (host/mcom_digest.cpp, DESIGN.md
+ * section 3.18) ----
+ * digest.txt is plain text, a member stored as it is: `minicom-digest 1`, `files <1|2>`, `n <records per file>`, then one line per key,
+ * `<key> <16 hex digits> <16 hex digits>` (one word per seed), in the order seq.ordered.1, qual.ordered.1, name.ordered.1, the same three
+ * with .2 for a pair, seq.multiset, rec.multiset.  The quality keys (qual.ordered.*, rec.multiset) are left out together when the quality
+ * lines were not digested, the name keys for a file of one read per line.  The same input gives the same bytes on every route.
+ *   mcomh_fastq_record_hashes  the twin of mcom_fastq_record_hashes (include/mcom.h) over host memory: the same checks, flags and words
+ *   mcomh_digest_reduce        the twin of mcom_digest_reduce
+ *   mcomh_fastq_digest_files   the digest of one file, or of a pair (fastq2 not NULL), as digest.txt to out_path; *n = records per file.
+ *                              lines_per_record 4: four-line FASTQ records; 1: one read per line (sequence keys only).  with_qual 0: the
+ *                              quality keys are left out.  device >= 0: on that GPU through the piece loop of the quality, name and length
+ *                              passes (plain, .gz; a BGZF file is inflated on the card; pieces of piece_bytes, 0: 32 MiB); -1: the twins.
+ *                              -1 with a message in err -- the first record that is no record, by its number from 1; two files of
+ *                              different record counts; an empty file -- and no output file.
+ *   mcomh_digest_print         the text of a digest: *len bytes into out (NULL: only the length; -2: cap too small)
+ *   mcomh_digest_parse         the inverse; -1 with the reason in why for anything the printer does not write: an unknown key, a key
+ *                              given twice or out of order, a wrong digit count, upper-case digits, a number with leading zeros, a missing
+ *                              last newline, keys that are not those of a digest of that many files
+ *   mcomh_digest_check         digests the decoder's output files (out2 NULL: one file; .gz included; one read per line when the
+ *                              archive holds neither quality values nor names, as the decoders write it) exactly as the input was, and compares n and the keys that the archive in
+ *                              `folder` can answer: with a list of ids (idsbin.tar.*, ids.bin.*, *.ids.bin: the order-preserving modes)
+ *                              seq.ordered.f, qual.ordered.f when the output is FASTQ and the key is stored, name.ordered.f when there is a
+ *                              name member; otherwise rec.multiset when the archive holds rqual*.mcq and the key is stored, else
+ *                              seq.multiset.  0: rep says what was compared and what differed; -1: refused (no digest.txt, one that
+ *                              does not parse, another number of files, an output file that is not records), the reason in rep->message. */
+typedef struct {
+	uint32_t files;                             /* 1 or 2                                                                          */
+	uint32_t present;                           /* bit k: key k is stated (the order above, from 0)                                 */
+	uint64_t n;                                 /* records per file                                                                */
+	uint64_t sums[16];                          /* word 2 * key + seed                                                             */
+} mcomh_digest;
+typedef struct {
+	int32_t identical;                          /* n and every compared key agree                                                  */
+	int32_t first_diff;                         /* -1: none; -2: n; else the first key that differs                                */
+	uint32_t compared, differing;               /* bit k: key k was compared / differs                                             */
+	uint32_t files, reserved;
+	uint64_t n_stored, n_output;
+	char message[256];                          /* why the check was refused                                                       */
+} mcomh_digest_report;
+int mcomh_fastq_record_hashes(const uint8_t *text, uint64_t n_bytes, const uint64_t *line_start, uint64_t first_record, uint64_t n_records, int lines_per_record, uint64_t n_total,
+                              uint64_t *hS, uint64_t *hQ, uint64_t *hN, uint32_t *flag);
+int mcomh_digest_reduce(const uint64_t *hS1, const uint64_t *hQ1, const uint64_t *hN1, const uint64_t *hS2, const uint64_t *hQ2, const uint64_t *hN2, uint64_t n, uint64_t sums[16]);
+int mcomh_fastq_digest_files(const char *fastq1, const char *fastq2, int lines_per_record, int with_qual, int device, size_t piece_bytes, const char *out_path, uint64_t *n, char *err,
+                             size_t err_cap);
+int mcomh_digest_print(const mcomh_digest *d, char *out, size_t cap, size_t *len);
+int mcomh_digest_parse(const char *text, size_t bytes, mcomh_digest *out, char *why, size_t why_cap);
+int mcomh_digest_check(const char *folder, const char *out1, const char *out2, int device, mcomh_digest_report *rep);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

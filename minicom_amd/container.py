@@ -48,6 +48,7 @@ PAIR_MEMBERS = ("qual_1.mcq", "qual_2.mcq", "name_1.mcn", "name_2.mcn")     # it
 LOSSY_MARKER = "qual_lossy.txt"   # marks quality values stored with bounded loss: the canonical spec and a newline; stored as it is
 RAGGED_MEMBERS = ("len.bin", "odd.seq", "odd.qual")   # reads of differing lengths: through the codec like the singles; len.bin marks the archive
 AGREE_MARKER = "qual_agree.txt"   # marks quality values of agreeing bases stored as one Phred value: `Q C` and a newline; stored as it is
+DIGEST_MEMBER = "digest.txt"      # the digest of the input of an archive made with digest=True (`minicom -K`): plain text, stored as it is
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
 CODECS = ("xz", "bz2", "gz", "raw", "bsc", "rans", "bwt")
 
@@ -160,7 +161,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
     if os.path.isfile(os.path.join(folder, NAME_MEMBER)):        # likewise (section 3.10)
         with open(os.path.join(folder, NAME_MEMBER), "rb") as f:
             packed.append((NAME_MEMBER, f.read()))
-    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS + (LOSSY_MARKER, AGREE_MARKER):   # likewise (sections 3.11, 3.12, 3.13 and 3.17)
+    for m in REORDERED_MEMBERS + (PAIR_ORDER,) + PAIR_MEMBERS + (LOSSY_MARKER, AGREE_MARKER, DIGEST_MEMBER):   # likewise (sections 3.11, 3.12, 3.13, 3.17 and 3.18)
         if os.path.isfile(os.path.join(folder, m)):
             with open(os.path.join(folder, m), "rb") as f:
                 packed.append((m, f.read()))
@@ -194,7 +195,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 
     def dec(item):
         name, data = item
-        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS or name == LOSSY_MARKER or name == AGREE_MARKER:
+        if name == "info.txt" or name == QUALITY_MEMBER or name == NAME_MEMBER or name in REORDERED_MEMBERS or name == PAIR_ORDER or name in PAIR_MEMBERS or name == LOSSY_MARKER or name == AGREE_MARKER or name == DIGEST_MEMBER:
             return name, data
         base, ext = name.rsplit(".", 1)
         if ext == "bsc":
@@ -224,6 +225,8 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
             kinds["quality_lossy"] = data.decode("latin-1").rstrip("\n")      # (as stored: the verifiers judge whether it is a spec)
         if name == AGREE_MARKER:
             kinds["quality_agree"] = data.decode("latin-1").rstrip("\n")     # (as stored, `Q C`: the verifiers judge whether it parses)
+        if name == DIGEST_MEMBER:
+            kinds["digest"] = True
         if name in PAIR_MEMBERS:
             kinds["quality" if name.endswith(".mcq") else "names"] = True
         if name.startswith("idsbin.tar"):
@@ -246,7 +249,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, quality_reordered: bool = False,
-                   quality_lossy=None, ragged: bool = False, quality_agree=None, **params) -> dict:
+                   quality_lossy=None, ragged: bool = False, quality_agree=None, digest: bool = False, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
@@ -264,7 +267,10 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     The mask is made on `device` from the stream files just dumped; the archive says so in qual_agree.txt.  With quality_lossy: agreement first.
     ragged=True (`minicom -p -V`; needs order=True; not with path2, quality_reordered or quality_lossy): the
     reads may differ in length.  Those of the modal length are the archive's reads, the others travel in len.bin, odd.seq and odd.qual;
-    a file of one length gives the archive made without it.  Returns pack()'s member sizes plus the read count (with ragged: "n_reads"
+    a file of one length gives the archive made without it.
+    digest=True (`minicom -K`; every mode): one more pass over the input on `device` stores its digest as
+    digest.txt (without the quality keys beside quality_lossy or quality_agree); decompress_file then checks what it wrote against it, and
+    test_file tests the archive.  Without it the archive does not change.  Returns pack()'s member sizes plus the read count (with ragged: "n_reads"
     counts the reads of the modal length, "n_records" all)."""
     import tempfile
     from .hip import McomError
@@ -283,7 +289,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         raise ValueError("ragged keeps reads of differing lengths of one file in its input order: order=True, no path2, no quality_reordered, no quality_lossy")
     if ragged:
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
-            sizes = _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params)
+            sizes = _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params, digest)
         if sizes is not None:
             return sizes                                             # (None: one length after all -- on as without ragged)
     p = Pipeline.from_fastq(path, device=device, path2=path2, host_threads=threads, **params)
@@ -318,6 +324,8 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
                     raise McomError("%s: %d names for %d reads" % (path, n_names, p.n))
             _mark_lossy(td, lossy)
             _mark_agree(td, agree)
+            if digest:
+                _digest_member(td, path, path2, lossy is None and agree is None, device, p.n if path2 is None else p.n // 2)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         return sizes
@@ -325,7 +333,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.close()
 
 
-def _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params):
+def _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params, digest=False):
     """compress_fastq(ragged=True) in the order of `minicom -p -V`: lengths, the core over the reads of the modal length, the quality
     values, the names, the container.  None when every read has one length."""
     from .hip import McomError
@@ -346,6 +354,8 @@ def _compress_ragged(path, out_path, td, codec, device, threads, quality, names,
             n_names = fastq_name_member(path, os.path.join(td, NAME_MEMBER), device=device)
             if n_names != n:
                 raise McomError("%s: %d names for %d records" % (path, n_names, n))
+        if digest:
+            _digest_member(td, path, None, True, device, n)
         sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_reads"] = p.n
         sizes["n_records"] = n
@@ -355,12 +365,12 @@ def _compress_ragged(path, out_path, td, codec, device, threads, quality, names,
 
 
 def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = False, names: bool = False, codec: str = "xz", device: int = 0,
-                        threads: int = 8, quality_lossy=None, quality_agree=None, **params) -> dict:
+                        threads: int = 8, quality_lossy=None, quality_agree=None, digest: bool = False, **params) -> dict:
     """Two FASTQ files of a pair -> a `.minicom` archive that keeps both in input order (`minicom -1 A_1.fastq -2 A_2.fastq -p [-Q [-N]]`,
     DESIGN.md section 3.12): the order-preserving members of the second file's reads behind the first's, and pe_order.txt.  quality=True:
     qual_1.mcq and qual_2.mcq; names=True (needs quality=True): name_1.mcn and name_2.mcn, the second coded against the first file's names
     -- decompress_file then gives both input files back byte for byte.  quality_lossy, quality_agree (need quality=True): as for
-    compress_fastq; rows [0, n) of the agreement mask belong to the first file and rows [n, 2 n) to the second.
+    compress_fastq; rows [0, n) of the agreement mask belong to the first file and rows [n, 2 n) to the second.  digest=True: as for compress_fastq, the digest of the pair.
     Returns pack()'s member sizes plus the number of pairs."""
     import tempfile
     from .hip import McomError
@@ -385,11 +395,24 @@ def compress_fastq_pair(path1: str, path2: str, out_path: str, quality: bool = F
                         raise McomError("%s: %d names for %d reads" % (fq, n_names, half))
             _mark_lossy(td, lossy)
             _mark_agree(td, agree)
+            if digest:
+                _digest_member(td, path1, path2, lossy is None and agree is None, device, half)
             sizes = pack(td, out_path, codec=codec, threads=threads, device=device if codec in ("rans", "bwt") else None)
         sizes["n_pairs"] = half
         return sizes
     finally:
         p.close()
+
+
+def _digest_member(folder: str, path: str, path2, with_qual: bool, device: int, n_archive: int) -> None:
+    """digest.txt of the input into the folder; the run fails when it counts other records than the archive does"""
+    from .hip import McomError
+    from .pipeline import digest_parse, fastq_digest
+    out = os.path.join(folder, DIGEST_MEMBER)
+    n = digest_parse(fastq_digest(path, path2, with_qual=with_qual, device=device, out_path=out))["n"]
+    if n != n_archive:
+        os.remove(out)
+        raise McomError("%s: the digest counts %d records, the archive %d" % (path, n, n_archive))
 
 
 def _lossy_spec(quality_lossy, keeps_quality: bool):
@@ -467,9 +490,10 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
     each) -- compressed on the GPU by the decoders' tails when `device` is given and the paths end in `.gz` (on that route the suffix
     alone decides, with or without the keyword), otherwise the plain file is written beside the archive's members first and
     pipeline.bgzf_file turns it into the same bytes.  An archive made with quality_agree (qual_agree.txt) is decoded as ever; that its
-    quality values are lossy is said in one line on stderr, as `minicom -d` says it."""
+    quality values are lossy is said in one line on stderr, as `minicom -d` says it.  An archive made with digest=True (digest.txt) is
+    checked: the files just written are digested as the input was (pipeline.digest_check, on `device` when given) and McomError says which
+    part differs; the files are kept."""
     import tempfile
-    from .pipeline import decompress, decompress_fastq, decompress_pe
     outs = [o for o in (out_path, out_path2) if o is not None]
     if gzip and not (device is not None and all(o.endswith(".gz") for o in outs)):
         from .pipeline import bgzf_file
@@ -481,28 +505,63 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
         return n
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
-        if kinds.get("quality_agree") is not None:                   # as `minicom -d` says it; the decoders do not change
-            import sys
-            print("minicom: the quality values of this archive are lossy: agreeing bases stored as Phred %s (coverage >= %s)" % tuple((kinds["quality_agree"].split(" ") + ["?", "?"])[:2]), file=sys.stderr)
-        if kinds.get("pair_order"):                                  # seen first: its other members are those of a -p archive
-            from .pipeline import decompress_order_pe
-            if out_path2 is None:
-                raise ValueError("an archive of a pair decodes into two files")
-            return decompress_order_pe(td, out_path, out_path2, device=device, fastq=bool(kinds.get("quality") or kinds.get("names")))
-        if kinds.get("quality_reordered"):
-            from .pipeline import decompress_fastq_reordered, decompress_fastq_pe
-            if kinds["paired"]:
-                if out_path2 is None:
-                    raise ValueError("a paired-end archive decodes into two files")
-                return decompress_fastq_pe(td, out_path, out_path2, device=device)
-            return decompress_fastq_reordered(td, out_path, device=device)
-        if kinds.get("quality"):
-            return decompress_fastq(td, out_path, device=device)
+        n = _decode_folder(td, kinds, out_path, out_path2, device)
+        if kinds.get("digest"):
+            from .hip import McomError
+            from .pipeline import digest_check
+            rep = digest_check(td, out_path, out_path2, device=device)
+            if not rep["identical"]:
+                raise McomError("%s: the decompressed files are not the compressed input (%s differs); they were kept" % (path, rep["first_diff"]))
+        return n
+
+
+def _decode_folder(td: str, kinds: dict, out_path: str, out_path2, device) -> int:
+    """the stream files of an unpacked archive -> its output file(s), by what unpack says about it"""
+    from .pipeline import decompress, decompress_fastq, decompress_pe
+    if kinds.get("quality_agree") is not None:                   # as `minicom -d` says it (DESIGN.md section 3.17); the decoders do not change
+        import sys
+        print("minicom: the quality values of this archive are lossy: agreeing bases stored as Phred %s (coverage >= %s)" % tuple((kinds["quality_agree"].split(" ") + ["?", "?"])[:2]), file=sys.stderr)
+    if kinds.get("pair_order"):                                  # seen first: its other members are those of a -p archive
+        from .pipeline import decompress_order_pe
+        if out_path2 is None:
+            raise ValueError("an archive of a pair decodes into two files")
+        return decompress_order_pe(td, out_path, out_path2, device=device, fastq=bool(kinds.get("quality") or kinds.get("names")))
+    if kinds.get("quality_reordered"):
+        from .pipeline import decompress_fastq_reordered, decompress_fastq_pe
         if kinds["paired"]:
             if out_path2 is None:
                 raise ValueError("a paired-end archive decodes into two files")
-            return decompress_pe(td, out_path, out_path2, device=device)
-        return decompress(td, out_path, order=kinds["order"], device=device)
+            return decompress_fastq_pe(td, out_path, out_path2, device=device)
+        return decompress_fastq_reordered(td, out_path, device=device)
+    if kinds.get("quality"):
+        return decompress_fastq(td, out_path, device=device)
+    if kinds["paired"]:
+        if out_path2 is None:
+            raise ValueError("a paired-end archive decodes into two files")
+        return decompress_pe(td, out_path, out_path2, device=device)
+    return decompress(td, out_path, order=kinds["order"], device=device)
+
+
+def test_file(path: str, threads: int = 8, device: int | None = None) -> dict:
+    """`minicom -d X.minicom -T`: an archive made with digest=True is decoded into a temporary folder beside it and the result checked
+    against the stored digest; nothing is kept.  Returns pipeline.digest_check's report ("identical", "compared", "differing", ...);
+    McomError for an archive without digest.txt."""
+    import tempfile
+    from .hip import McomError
+    from .pipeline import digest_check
+    with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(path)) or ".") as td:
+        folder = os.path.join(td, "members")
+        kinds = unpack(path, folder, threads=threads, device=device)
+        if not kinds.get("digest"):
+            raise McomError("%s holds no digest.txt: it was made without digest=True (`minicom -K`)" % path)
+        two = bool(kinds["paired"] or kinds.get("pair_order"))
+        fastq = bool(kinds.get("quality") or kinds.get("names") or kinds.get("quality_reordered"))
+        outs = [os.path.join(td, "out_%d.%s" % (k + 1, "fastq" if fastq else "reads")) for k in range(2 if two else 1)]
+        _decode_folder(folder, kinds, outs[0], outs[1] if two else None, device)
+        return digest_check(folder, outs[0], outs[1] if two else None, device=device)
+
+
+test_file.__test__ = False        # (not a test: pytest collects by name)
 
 
 def verify_file(path: str, fastq: str, fastq2: str | None = None, threads: int = 8, device: int = 0) -> dict:

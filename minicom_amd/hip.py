@@ -249,6 +249,8 @@ def load_library():
     L.mcom_name_compare.restype = i32; L.mcom_name_compare.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_fastq_name_text.restype = i32; L.mcom_fastq_name_text.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp]
     L.mcom_fastq_emit_named.restype = i32; L.mcom_fastq_emit_named.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.c_uint32, vp, C.POINTER(u64)]
+    L.mcom_fastq_record_hashes.restype = i32; L.mcom_fastq_record_hashes.argtypes = [vp, vp, u64, vp, u64, u64, i32, u64, vp, vp, vp, vp]
+    L.mcom_digest_reduce.restype = i32; L.mcom_digest_reduce.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.mcom_fastq_lengths.restype = i32; L.mcom_fastq_lengths.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, vp]
     L.mcom_ragged_index.restype = i32; L.mcom_ragged_index.argtypes = [vp, vp, u64, C.c_uint32, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mcom_fastq_ragged_rows.restype = i32; L.mcom_fastq_ragged_rows.argtypes = [vp, vp, u64, vp, u64, u64, i32, C.c_uint32, vp, vp, u64, vp, u64, u64, vp, u64, vp]
@@ -1400,6 +1402,48 @@ class Context:
         self._check(self.lib.mcom_fastq_emit_named(self._h, reads.data_ptr() if count else None, rp, quals.data_ptr() if count else None, qp, self._p(names, torch.uint8),
                                                    int(names.shape[0]), self._p(off), count, L, self._p(out), C.byref(nb)))
         return out[:nb.value]
+
+    # ---- the digest of a FASTQ file (csrc/digest.hip) ----
+    def fastq_record_hashes(self, text, lines_per_record: int = 4, first_record: int = 0, hS=None, hQ=None, hN=None, with_qual: bool = True, with_names: bool = True):
+        """mcom_decode_line_index + mcom_fastq_record_hashes.  text: uint8 device tensor holding whole records of lines_per_record (4 or 1)
+        lines.  hS, hQ, hN: int64 device tensors [n_total, 2] that cover all records of the file and are written at first_record .. (fresh
+        ones of first_record + n_records rows otherwise; hQ / hN are left out with with_qual / with_names False and with lines_per_record
+        1).  Returns (hS, hQ, hN, flag bits of MCOM_FASTQ_F_*, the first flagged record or None); a flagged record's rows are not written."""
+        torch = _torch()
+        start, _ = self.decode_line_index(text)
+        n_rec = (int(start.shape[0]) - 1) // int(lines_per_record)
+        four = int(lines_per_record) == 4
+        fresh = lambda: torch.zeros((max(first_record + n_rec, 1), 2), dtype=torch.int64, device=self.device)  # noqa: E731
+        if hS is None:
+            hS = fresh()
+        if hQ is None and four and with_qual:
+            hQ = fresh()
+        if hN is None and four and with_names:
+            hN = fresh()
+        n_total = int(hS.shape[0])
+        for t in (hS, hQ, hN):
+            if t is not None and (t.dtype != torch.int64 or t.dim() != 2 or int(t.shape[1]) != 2 or int(t.shape[0]) != n_total or not t.is_contiguous()):
+                raise McomError("fastq_record_hashes: the hash arrays are contiguous int64 [n_total, 2] of one length")
+        if first_record + n_rec > n_total:
+            raise McomError("fastq_record_hashes: %d records from %d do not fit %d rows" % (n_rec, first_record, n_total))
+        flag = torch.tensor([0, -1], dtype=torch.int32, device=self.device)
+        self._check(self.lib.mcom_fastq_record_hashes(self._h, self._p(text, torch.uint8) if n_rec else None, int(text.shape[0]), self._p(start), int(first_record), n_rec,
+                                                      int(lines_per_record), n_total, self._p(hS), self._p(hQ), self._p(hN), self._p(flag)))
+        f = flag.cpu().numpy().view(np.uint32)
+        return hS, hQ, hN, int(f[0]), (None if f[1] == 0xFFFFFFFF else int(f[1]))
+
+    def digest_reduce(self, hS1, hQ1=None, hN1=None, hS2=None, hQ2=None, hN2=None, n=None):
+        """mcom_digest_reduce over int64 device tensors [>= n, 2] (n: all rows of hS1 by default).  Returns the sixteen sums as Python
+        integers: word 2 * key + seed, keys in the order seq.ordered.1, qual.ordered.1, name.ordered.1, the three of file 2, seq.multiset,
+        rec.multiset; the sums of arrays not given are 0."""
+        torch = _torch()
+        n = int(hS1.shape[0]) if n is None else int(n)
+        for t in (hS1, hQ1, hN1, hS2, hQ2, hN2):
+            if t is not None and (t.dtype != torch.int64 or t.dim() != 2 or int(t.shape[1]) != 2 or int(t.shape[0]) < n or not t.is_contiguous()):
+                raise McomError("digest_reduce: the hash arrays are contiguous int64 [>= n, 2]")
+        sums = (C.c_uint64 * 16)()
+        self._check(self.lib.mcom_digest_reduce(self._h, self._p(hS1) if n else None, self._p(hQ1), self._p(hN1), self._p(hS2), self._p(hQ2), self._p(hN2), n, sums))
+        return [int(v) for v in sums]
 
     # ---- reads of differing lengths (csrc/ragged.hip; DESIGN.md section 3.16) ----
     def fastq_lengths(self, text, first_record: int = 0, lens=None, hist=None):

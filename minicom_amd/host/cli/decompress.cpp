@@ -24,6 +24,9 @@
 // archive's, part by part; exit status as --verify.  The plain decoder and --fastq pick DIR/len.bin up by themselves.
 // decompress --agree-mask [--gpu] DIR C OUT: the agreement mask of `minicom -a Q[:C]` of the stream files in DIR -- a
 // default-mode or a -p archive -- written to OUT; prints `n L bits_set`.  The quality verifiers pick DIR/qual_agree.txt up by themselves.
+// decompress --check-digest [--gpu] DIR OUT1 [OUT2]: an archive made with -K (DIR holds digest.txt): the output
+// files are digested as the input was (on GPU 0 with --gpu, by the host twin without) and set against it, every key that the archive's
+// kind can answer; one line says what was compared.  Exit status as --verify: 0 identical, 2 different, 1 refused or error.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
@@ -71,6 +74,31 @@ static int agree_mask(int argc, char **argv)
 	}
 	fprintf(stdout, "%llu %d %llu\n", (unsigned long long)n, L, (unsigned long long)bits);
 	return 0;
+}
+
+static int check_digest(int argc, char **argv)
+{
+	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+	if (gpu) { --argc; ++argv; }
+	if (argc != 3 && argc != 4) { fprintf(stderr, "usage: decompress --check-digest [--gpu] DIR OUT1 [OUT2]\n"); return 1; }
+	mcomh_digest_report r;
+	if (mcomh_digest_check(argv[1], argv[2], argc == 4 ? argv[3] : nullptr, gpu ? 0 : -1, &r)) { fprintf(stderr, "decompress: the digest of %s was not checked: %s\n", argv[1], r.message[0] ? r.message : "error"); return 1; }
+	// keys: seq.ordered.1 qual.ordered.1 name.ordered.1 seq.ordered.2 qual.ordered.2 name.ordered.2 seq.multiset rec.multiset
+	static const char *part[8] = {"reads", "quality lines", "names", "reads of file 2", "quality lines of file 2", "names of file 2", "reads (in any order)", "reads with their quality lines (in any order)"};
+	if (r.identical) {
+		const bool multi = (r.compared & 0xC0u) != 0, qual = (r.compared & 0x12u) != 0, names = (r.compared & 0x24u) != 0;
+		printf("verified: %s identical to the compressed input of %llu %s\n", multi ? (r.compared & 0x80u ? "reads with their quality lines, in any order," : "reads, in any order,")
+		       : qual && names ? "reads, quality lines and names" : qual ? "reads and quality lines" : names ? "reads and names" : "reads", (unsigned long long)r.n_stored, r.files == 2 ? "pairs" : "records");
+		return 0;
+	}
+	if (r.first_diff == -2) printf("DIFFERENT: the compressed input held %llu %s, the decompressed output holds %llu\n", (unsigned long long)r.n_stored, r.files == 2 ? "pairs" : "records", (unsigned long long)r.n_output);
+	else {
+		printf("DIFFERENT: the decompressed output is not the compressed input: the");
+		bool first = true;
+		for (int k = 0; k < 8; ++k) if (r.differing >> k & 1) { printf("%s %s%s", first ? "" : ",", part[k], k < 3 && r.files == 2 ? " of file 1" : ""); first = false; }
+		printf(" differ (first: %s)\n", part[r.first_diff]);
+	}
+	return 2;
 }
 
 static int verify(int argc, char **argv)
@@ -218,6 +246,7 @@ static int verify_ragged(int argc, char **argv)
 
 int main(int argc, char **argv)
 {
+	if (argc > 1 && !strcmp(argv[1], "--check-digest")) return check_digest(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify-ragged")) return verify_ragged(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--agree-mask")) return agree_mask(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--order-pe")) return order_pe(argc - 1, argv + 1, false);

@@ -36,6 +36,9 @@
 // (length - 1) per record; prints `n L n_odd` -- the records, the modal length, the records of another length.
 // mcomz e --fastq-qual L --ragged LENFILE [--gpu] IN.fastq OUT.mcq OUT.oddqual: the `.mcq` member over the records of L bases and the
 // quality lines of the others back to back; prints the number of rows of the member.
+// mcomz e --fastq-digest [--gpu] [--no-qual] IN.fastq [IN_2.fastq] OUT: the digest of `minicom -K` of one file or of a
+// pair as digest.txt; --no-qual leaves the quality keys out (what -K passes beside -b and -a).  Prints the number of records per file.
+// Exit status 1, no OUT and a message that says why for a file that is not four-line records, or a pair of different record counts.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstdlib>
@@ -97,6 +100,17 @@ int main(int argc, char **argv)
 			fprintf(stderr, "mcomz: %s: %s\n", argv[argc - 3], err[0] ? err : "cannot code the qualities"); return 1;
 		}
 		printf("%llu\n", (unsigned long long)n_even);
+		return 0;
+	}
+	if (argc > 2 && !strcmp(argv[1], "e") && !strcmp(argv[2], "--fastq-digest")) {
+		int k = 3; bool d_gpu = false, no_qual = false;
+		for (; k < argc; ++k) { if (!strcmp(argv[k], "--gpu") && !d_gpu) d_gpu = true; else if (!strcmp(argv[k], "--no-qual") && !no_qual) no_qual = true; else break; }
+		if (argc - k != 2 && argc - k != 3) { fprintf(stderr, "usage: mcomz e --fastq-digest [--gpu] [--no-qual] IN.fastq [IN_2.fastq] OUT\n"); return 1; }
+		char err[480] = ""; uint64_t n = 0;
+		if (mcomh_fastq_digest_files(argv[k], argc - k == 3 ? argv[k + 1] : nullptr, 4, no_qual ? 0 : 1, d_gpu ? 0 : -1, 0, argv[argc - 1], &n, err, sizeof err)) {
+			fprintf(stderr, "mcomz: no digest: %s\n", err[0] ? err : "cannot take the digest"); return 1;
+		}
+		printf("%llu\n", (unsigned long long)n);
 		return 0;
 	}
 	bool gpu = false, bwt = false, names = false, fastq_names = false;

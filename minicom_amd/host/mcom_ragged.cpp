@@ -181,6 +181,7 @@ struct Job {                                                // what one call hol
 	uint64_t *d_start = nullptr; uint32_t *d_flag = nullptr;
 	std::vector<void*> dev;                                 // the pass's own tables
 	gzFile f = nullptr;
+	bool own_ctx = true;                                    // false: the caller's context, which outlives the job
 	~Job()
 	{
 		if (copy) (void)hipStreamSynchronize(copy);
@@ -191,21 +192,22 @@ struct Job {                                                // what one call hol
 		if (d_flag) (void)hipFree(d_flag);
 		for (void *p : dev) if (p) (void)hipFree(p);
 		if (copy) (void)hipStreamDestroy(copy);
-		if (ctx) mcom_destroy(ctx);
+		if (ctx && own_ctx) mcom_destroy(ctx);
 	}
 	template <class T> T *alloc(size_t n) { void *p = nullptr; if (hipMalloc(&p, (n ? n : 1) * sizeof(T) + 16) != hipSuccess) return nullptr; dev.push_back(p); return (T*)p; }
 	void release(void *p) { for (void *&q : dev) if (q == p) { (void)hipFree(q); q = nullptr; } }
 	void disown(void *p) { for (void *&q : dev) if (q == p) q = nullptr; }
 };
 
-int open_job(Job &J, const char *path, int device, char *err, size_t err_cap)
+int open_job(Job &J, const char *path, int device, char *err, size_t err_cap, mcom_ctx *ctx = nullptr)
 {
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return fail(err, err_cap, "no GPU %llu (%llu visible)", (unsigned long long)device, (unsigned long long)n_dev);
 	if (hipSetDevice(device) != hipSuccess) return fail(err, err_cap, "cannot select the GPU");
 	J.f = gzopen(path, "rb");
 	if (!J.f) return fail(err, err_cap, "cannot open the file");
-	if (mcom_create(&J.ctx, device, nullptr) != MCOM_OK) { J.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
+	if (ctx) { J.ctx = ctx; J.own_ctx = false; }
+	else if (mcom_create(&J.ctx, device, nullptr) != MCOM_OK) { J.ctx = nullptr; return fail(err, err_cap, "cannot create a context on the GPU"); }
 	if (hipStreamCreate(&J.copy) != hipSuccess) return fail(err, err_cap, "no stream");
 	if (hipMalloc((void**)&J.d_flag, 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
 	return 0;
@@ -231,13 +233,14 @@ bool clear_flags(Job &J)
 }
 
 // every record of the file through `pass`, *n = their number.  again(): the pass forgets what it has seen (the BGZF route gave the file up
-// and zlib's reader starts it again)
-int for_each_piece(Job &J, const char *path, size_t piece_bytes, const PieceFn &pass, const std::function<bool()> &again, uint64_t *n_out, char *err, size_t err_cap)
+// and zlib's reader starts it again).  lpr: the lines of a record, 4, or 1 for a file of one read per line (which
+// always goes through zlib's reader: the BGZF route hands four-line records on)
+int for_each_piece(Job &J, const char *path, size_t piece_bytes, const PieceFn &pass, const std::function<bool()> &again, uint64_t *n_out, char *err, size_t err_cap, size_t lpr = 4)
 {
 	size_t piece = piece_bytes ? piece_bytes : DEFAULT_PIECE;
 	if (piece < LEAST_PIECE) piece = LEAST_PIECE;
 	uint64_t n = 0;
-	const bool on_device = mcom_gz_device_route(path, J.ctx, piece, [&](const uint8_t *d_text, uint64_t bytes, uint64_t records, const uint64_t *d_line_start) {
+	const bool on_device = lpr == 4 && mcom_gz_device_route(path, J.ctx, piece, [&](const uint8_t *d_text, uint64_t bytes, uint64_t records, const uint64_t *d_line_start) {
 		if (n + records >= ((uint64_t)1 << 32) || !clear_flags(J) || pass(d_text, bytes, records, d_line_start, n)) return false;
 		n += records;
 		return true;
@@ -263,7 +266,7 @@ int for_each_piece(Job &J, const char *path, size_t piece_bytes, const PieceFn &
 	auto whole_records = [&](const uint8_t *buf, size_t len, size_t &bytes, size_t &records) {
 		size_t lines = 0; bytes = 0; records = 0;
 		const uint8_t *p = buf, *const e = buf + len;
-		while (p < e) { const uint8_t *q = (const uint8_t*)memchr(p, '\n', (size_t)(e - p)); if (!q) break; p = q + 1; if ((++lines & 3) == 0) { bytes = (size_t)(p - buf); records = lines / 4; } }
+		while (p < e) { const uint8_t *q = (const uint8_t*)memchr(p, '\n', (size_t)(e - p)); if (!q) break; p = q + 1; if (++lines % lpr == 0) { bytes = (size_t)(p - buf); records = lines / lpr; } }
 	};
 	size_t len = 0, cap_lines = 0; bool eof = false;
 	if (!fill(J.pin[0], 0, len, eof)) return fail(err, err_cap, "cannot read the file (a damaged gzip stream?)");
@@ -281,14 +284,14 @@ int for_each_piece(Job &J, const char *path, size_t piece_bytes, const PieceFn &
 		}
 		if (records) {
 			if (hipEventSynchronize(J.ev[k]) != hipSuccess) return fail(err, err_cap, "upload failed");
-			if (4 * records + 1 > cap_lines) {
+			if (lpr * records + 1 > cap_lines) {
 				if (J.d_start) (void)hipFree(J.d_start);
-				J.d_start = nullptr; cap_lines = 4 * records + 1;
+				J.d_start = nullptr; cap_lines = lpr * records + 1;
 				if (hipMalloc((void**)&J.d_start, cap_lines * 8 + 16) != hipSuccess) return fail(err, err_cap, "no room on the card");
 			}
 			if (!clear_flags(J)) return fail(err, err_cap, "upload failed");
 			uint64_t got_lines = 0;
-			if (mcom_decode_line_index(J.ctx, J.d_text[k], bytes, J.d_start, 4 * records, &got_lines, J.d_flag + 2) || got_lines != 4 * records) {
+			if (mcom_decode_line_index(J.ctx, J.d_text[k], bytes, J.d_start, lpr * records, &got_lines, J.d_flag + 2) || got_lines != lpr * records) {
 				if (err && err_cap) snprintf(err, err_cap, "device call failed: %s", mcom_last_error(J.ctx));
 				return -1;
 			}
@@ -433,6 +436,16 @@ extern "C" int mcomh_fastq_ragged_files(const char *fastq, int which, int L, int
 }
 
 #ifndef MCOM_ENTROPY_HOST_ONLY
+int mcom_fastq_for_each_piece(const char *path, mcom_ctx *ctx, int device, int lines_per_record, size_t piece_bytes, const McomPiecePass &pass, const std::function<bool()> &again,
+                              uint64_t *n, char *err, size_t err_cap)
+{
+	Job J;
+	if (open_job(J, path, device, err, err_cap, ctx)) return -1;
+	return for_each_piece(J, path, piece_bytes, [&](const uint8_t *d_text, uint64_t bytes, uint64_t records, const uint64_t *d_line_start, uint64_t first) {
+		return pass(d_text, bytes, records, d_line_start, first, J.d_flag);
+	}, again, n, err, err_cap, lines_per_record == 1 ? 1 : 4);
+}
+
 int mcom_ragged_split_to_device(const char *path, int device, int which, int L, const char *len_path, uint8_t **d_rows, std::vector<uint8_t> &odd, uint64_t *n_even, char *err, size_t err_cap)
 {
 	std::vector<uint8_t> len;

@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -22,3 +23,16 @@ int mcom_ragged_split_to_device(const char *path, int device, int which, int L, 
 bool mcom_ragged_present(const char *folder);
 // false with `why` set: the parts disagree
 bool mcom_ragged_load(const char *folder, int L, uint64_t n_even, bool want_qual, McomRaggedParts &P, std::string &why);
+
+#ifndef MCOM_ENTROPY_HOST_ONLY
+#include "../../include/mcom.h"
+// The piece loop of the FASTQ passes (plain or gzip text through zlib's reader, the unfinished record of a piece carried in front of the
+// next one; a BGZF file of four-line records inflated on the card) for a pass that lives elsewhere: every record
+// of the file at `path` goes through `pass` on the caller's context, `records` whole records of lines_per_record (4 or 1) lines from
+// record `first` of the file with their text and line index; d_flag: the four flag words, cleared in front of the line index (words 0
+// and 1: the pass's own, word 2: the index's).  pass returns 0 to go on; again(): the pass forgets what it has seen, the file starts again
+// from its beginning.  *n = the records of the file.  -1 with a message in err (the pass words its own).
+typedef std::function<int(const uint8_t *d_text, uint64_t bytes, uint64_t records, const uint64_t *d_line_start, uint64_t first, uint32_t *d_flag)> McomPiecePass;
+int mcom_fastq_for_each_piece(const char *path, mcom_ctx *ctx, int device, int lines_per_record, size_t piece_bytes, const McomPiecePass &pass, const std::function<bool()> &again,
+                              uint64_t *n, char *err, size_t err_cap);
+#endif

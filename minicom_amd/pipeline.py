@@ -19,6 +19,20 @@ class VerifyReport(C.Structure):
                 ("times_ms", C.c_double * 8)]
 
 
+class Digest(C.Structure):
+    """mcomh_digest of include/mcom_host.h"""
+    _fields_ = [("files", C.c_uint32), ("present", C.c_uint32), ("n", C.c_uint64), ("sums", C.c_uint64 * 16)]
+
+
+class DigestReport(C.Structure):
+    """mcomh_digest_report of include/mcom_host.h"""
+    _fields_ = [("identical", C.c_int32), ("first_diff", C.c_int32), ("compared", C.c_uint32), ("differing", C.c_uint32), ("files", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_stored", C.c_uint64), ("n_output", C.c_uint64), ("message", C.c_char * 256)]
+
+
+DIGEST_KEYS = ("seq.ordered.1", "qual.ordered.1", "name.ordered.1", "seq.ordered.2", "qual.ordered.2", "name.ordered.2", "seq.multiset", "rec.multiset")
+
+
 class Params(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("k", "e", "m", "w", "cbthr", "max_rounds", "step", "maxthr", "numdict", "host_threads", "maxsearch", "window_scan",
                                          "full_consensus", "full_sketch", "overlap_screen", "host_dump", "stream_sets", "stage2_join", "read_batches")]
@@ -168,6 +182,12 @@ def load_host_library():
     L.mcomh_fastq_quality_member_ragged.restype = i32; L.mcomh_fastq_quality_member_ragged.argtypes = [cp, i32, i32, cp, cp, cp, C.POINTER(u64), C.c_char_p, sz]
     L.mcomh_fastq_emit_ragged.restype = i32; L.mcomh_fastq_emit_ragged.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64)]
     L.mcomh_verify_ragged_gpu.restype = i32; L.mcomh_verify_ragged_gpu.argtypes = [cp, cp, i32, C.POINTER(VerifyReport), C.POINTER(i32)]
+    L.mcomh_fastq_record_hashes.restype = i32; L.mcomh_fastq_record_hashes.argtypes = [vp, u64, vp, u64, u64, i32, u64, vp, vp, vp, vp]
+    L.mcomh_digest_reduce.restype = i32; L.mcomh_digest_reduce.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp]
+    L.mcomh_fastq_digest_files.restype = i32; L.mcomh_fastq_digest_files.argtypes = [cp, cp, i32, i32, i32, sz, cp, C.POINTER(u64), C.c_char_p, sz]
+    L.mcomh_digest_print.restype = i32; L.mcomh_digest_print.argtypes = [C.POINTER(Digest), C.c_char_p, sz, C.POINTER(sz)]
+    L.mcomh_digest_parse.restype = i32; L.mcomh_digest_parse.argtypes = [C.c_char_p, sz, C.POINTER(Digest), C.c_char_p, sz]
+    L.mcomh_digest_check.restype = i32; L.mcomh_digest_check.argtypes = [cp, cp, cp, i32, C.POINTER(DigestReport)]
     _lib = L
     return L
 
@@ -215,6 +235,8 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     # reads of differing lengths (`minicom -p -V`, host/mcom_ragged.cpp)
                     "mcomh_fastq_lengths_file", "mcomh_fastq_ragged_files", "mcomh_fastq_to_device_ragged", "mcomh_fastq_quality_member_ragged",
                     "mcomh_fastq_emit_ragged", "mcomh_verify_ragged_gpu",
+                    # self-checking archives (`minicom -K`, host/mcom_digest.cpp)
+                    "mcomh_fastq_record_hashes", "mcomh_digest_reduce", "mcomh_fastq_digest_files", "mcomh_digest_print", "mcomh_digest_parse", "mcomh_digest_check",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -591,6 +613,79 @@ def fastq_quality_member_ragged(fastq: str, L: int, len_path: str, out_mcq: str,
                                                              os.fsencode(out_odd_qual), C.byref(ne), err, 320):
         raise McomError(f"{fastq}: {err.value.decode() or 'cannot code the qualities'}")
     return int(ne.value)
+
+
+# ---- self-checking archives (`minicom -K`, host/mcom_digest.cpp) ----
+def fastq_digest(path: str, path2: str | None = None, lines_per_record: int = 4, with_qual: bool = True, device: int | None = None, piece_bytes: int = 0, out_path: str | None = None) -> str:
+    """mcomh_fastq_digest_files: the text of digest.txt for one FASTQ file (plain or .gz), or for a pair.  lines_per_record 1: a file of one
+    read per line (sequence keys only); with_qual=False leaves the quality keys out.  device=None: the host twin; an integer: on that GPU,
+    the text going up in pieces of piece_bytes (0: 32 MiB).  out_path: the file is kept there as well.  McomError names the first record
+    that is none, or says that the two files differ in their record counts; no file is left behind then."""
+    import tempfile
+    err = C.create_string_buffer(400)
+    n = C.c_uint64()
+    with tempfile.TemporaryDirectory() as td:
+        out = out_path if out_path is not None else os.path.join(td, "digest.txt")
+        if load_host_library().mcomh_fastq_digest_files(os.fsencode(path), None if path2 is None else os.fsencode(path2), int(lines_per_record), 1 if with_qual else 0,
+                                                        -1 if device is None else int(device), int(piece_bytes), os.fsencode(out), C.byref(n), err, 400):
+            raise McomError(err.value.decode() or f"{path}: cannot take the digest")
+        with open(out, "rb") as f:
+            return f.read().decode()
+
+
+def digest_parse(text) -> dict:
+    """mcomh_digest_parse: {"files", "n", key: (word of seed 1, word of seed 2)} of a digest.txt; McomError with the reason for anything
+    not written exactly as mcomh_digest_print writes it."""
+    b = text.encode() if isinstance(text, str) else bytes(text)
+    d = Digest()
+    why = C.create_string_buffer(128)
+    if load_host_library().mcomh_digest_parse(b, len(b), C.byref(d), why, 128):
+        raise McomError("not a digest: " + why.value.decode())
+    out = {"files": int(d.files), "n": int(d.n)}
+    for k, name in enumerate(DIGEST_KEYS):
+        if d.present >> k & 1:
+            out[name] = (int(d.sums[2 * k]), int(d.sums[2 * k + 1]))
+    return out
+
+
+def digest_check(folder: str, out1: str, out2: str | None = None, device: int | None = None) -> dict:
+    """mcomh_digest_check: the decoder's output files against folder/digest.txt.  Returns {"identical", "compared": [keys], "differing":
+    [keys], "first_diff": a key, "n" or None, "n_stored", "n_output"}; McomError when the check is refused."""
+    r = DigestReport()
+    if load_host_library().mcomh_digest_check(os.fsencode(folder), os.fsencode(out1), None if out2 is None else os.fsencode(out2), -1 if device is None else int(device), C.byref(r)):
+        raise McomError("digest check refused: " + (r.message.decode() or "error"))
+    keys = lambda bits: [name for k, name in enumerate(DIGEST_KEYS) if bits >> k & 1]  # noqa: E731
+    return {"identical": bool(r.identical), "compared": keys(r.compared), "differing": keys(r.differing),
+            "first_diff": None if r.first_diff == -1 else "n" if r.first_diff == -2 else DIGEST_KEYS[r.first_diff], "n_stored": int(r.n_stored), "n_output": int(r.n_output)}
+
+
+def fastq_record_hashes_host(text: bytes, lines_per_record: int = 4, first_record: int = 0, n_total: int | None = None, with_qual: bool = True, with_names: bool = True):
+    """mcomh_fastq_record_hashes over a text of whole records (the line index is made here).  Returns (hS, hQ, hN, flag bits, first flagged
+    record or None): uint64 arrays [n_total, 2] (None where not asked for, or with lines_per_record 1)."""
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    nl = np.flatnonzero(buf == 10)
+    start = np.concatenate([[0], nl + 1]).astype(np.uint64)
+    n_rec = (len(start) - 1) // lines_per_record
+    n_total = first_record + n_rec if n_total is None else int(n_total)
+    four = lines_per_record == 4
+    hS = np.zeros((max(n_total, 1), 2), dtype=np.uint64)
+    hQ = np.zeros((max(n_total, 1), 2), dtype=np.uint64) if four and with_qual else None
+    hN = np.zeros((max(n_total, 1), 2), dtype=np.uint64) if four and with_names else None
+    flag = np.array([0, 0xFFFFFFFF], dtype=np.uint32)
+    if load_host_library().mcomh_fastq_record_hashes(buf.ctypes.data if len(buf) else None, len(buf), start.ctypes.data, int(first_record), n_rec, int(lines_per_record), n_total,
+                                                     hS.ctypes.data, None if hQ is None else hQ.ctypes.data, None if hN is None else hN.ctypes.data, flag.ctypes.data):
+        raise McomError("fastq_record_hashes: bad arguments")
+    return hS[:n_total], None if hQ is None else hQ[:n_total], None if hN is None else hN[:n_total], int(flag[0]), (None if flag[1] == 0xFFFFFFFF else int(flag[1]))
+
+
+def digest_reduce_host(hS1, hQ1=None, hN1=None, hS2=None, hQ2=None, hN2=None):
+    """mcomh_digest_reduce: the sixteen sums (word 2 * key + seed, keys in the order of DIGEST_KEYS) of uint64 arrays [n, 2]"""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64) for a in (hS1, hQ1, hN1, hS2, hQ2, hN2)]
+    n = int(arrs[0].shape[0])
+    sums = np.zeros(16, dtype=np.uint64)
+    if load_host_library().mcomh_digest_reduce(*[None if a is None else a.ctypes.data for a in arrs], n, sums.ctypes.data):
+        raise McomError("digest_reduce: bad arguments")
+    return [int(v) for v in sums]
 
 
 def ragged_index(len_bin: bytes, L: int):
