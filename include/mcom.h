@@ -701,6 +701,21 @@ typedef struct {
  * per row, zeroed by the caller; a row written twice is flagged.  Asynchronous.                                                  */
 int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
                       uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag);
+/* ---- a window of rows: the rows [win_first, win_first + win_count) of the table without the table ----
+ * mcom_range_check_dest: mcom_decode_reads' placement check on its own, over ALL n reads of a source: a destination (d_dest[m], NULL:
+ * dest0 + m) >= n_rows raises MCOM_DECODE_F_DEST, a row named twice MCOM_DECODE_F_DUP (d_seen: one bit per row of the FULL row space,
+ * zeroed by the caller, shared by the sources of an archive).  Nothing is decoded.  Where the reads of all sources are as many as the
+ * rows, no flag means every row is named exactly once -- so every row of any window is.  Asynchronous.
+ * mcom_range_decode_reads: the reads of the source whose destination lies inside the window are decoded to row (destination -
+ * win_first) of d_out, win_count rows of L characters and a newline; the bytes of a row equal those mcom_decode_reads writes.  No other
+ * read is decoded and nothing outside d_out is written.  A selection pass (one thread per read) makes a compacted list of the reads
+ * inside the window, then mcom_decode_reads' row body runs over that list: a window of 1 % of the rows launches about 1 % of the
+ * sixteen-lane groups.  MCOM_DECODE_F_BOUNDS and _F_LINE are raised for the reads it decodes ONLY: a read outside the window whose
+ * reference window leaves ref.bin is not noticed.  No d_seen: run mcom_range_check_dest first; more reads inside the window than it
+ * has rows raise MCOM_DECODE_F_DUP.  Takes 8 (min(n, win_count) + 1) bytes of HBM for the list.  Asynchronous.                        */
+int mcom_range_check_dest(mcom_ctx *ctx, const uint64_t *d_dest, uint64_t dest0, uint64_t n, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag);
+int mcom_range_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
+                             uint64_t win_first, uint64_t win_count, uint8_t *d_out, uint32_t *d_flag);
 
 /* ---- consensus agreement (`minicom -a Q[:C]`; csrc/decode.hip, csrc/qual_agree.hip; definitions: DESIGN.md section 3.17) ----
  * mcom_agree_coverage: d_cov[b] (ref_bases bytes) = number of the n_members member reads of ONE stream set whose window
@@ -812,6 +827,16 @@ int mcom_qual_encode(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n_rows, uint
 int mcom_qual_info(const uint8_t *h_member_prefix, uint64_t len, uint64_t *n_rows, uint32_t *L);
 int mcom_qual_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_rows, uint64_t pitch, uint64_t cap_rows,
                      uint64_t *n_rows, uint32_t *L);
+/* Rows first_row .. first_row + count - 1 of a member (count is clipped at the member's end) to rows 0 .. of d_rows, `pitch` >= L apart;
+ * *n_rows, *L = the member's own.  Refused (MCOM_E_ARG): what mcom_qual_decode refuses in header, tables and run lengths, and
+ * first_row > n_rows.  Kind 0, models 1 to 4: the tables and ALL run lengths are judged as ever, the decoder runs over the segments
+ * first_row / rps .. (first_row + count - 1) / rps only, into an image of at most two segments more than the window.  Stored: a copy.
+ * Kind 1 (an embedded `.rans` member) is decoded whole into a temporary and sliced: this kind costs n_rows * L bytes of HBM.
+ * The member's CRC-32 is over all raw bytes and CANNOT be checked for a part: a range is guarded by the per-segment checks alone (run
+ * used up exactly, final state 2^23, slot owned, symbol < A; a stored member by nothing; kind 1 by the embedded member's own CRC).
+ * first_row == 0 with count >= n_rows is mcom_qual_decode, CRC included.  Synchronous.  Bytes and refusals equal mcomh_qual_decode_rows'. */
+int mcom_qual_decode_rows(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t first_row, uint64_t count, uint8_t *d_rows, uint64_t pitch,
+                          uint64_t *n_rows, uint32_t *L);
 
 /* ---- FASTQ text <-> rows on the device (csrc/qual.hip): the two ends of `minicom -Q` ----
  * mcom_fastq_quality_rows: record r of this call is lines 4r .. 4r + 3 of a line index made by mcom_decode_line_index over d_text

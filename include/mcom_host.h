@@ -634,6 +634,33 @@ int mcomh_digest_print(const mcomh_digest *d, char *out, size_t cap, size_t *len
 int mcomh_digest_parse(const char *text, size_t bytes, mcomh_digest *out, char *why, size_t why_cap);
 int mcomh_digest_check(const char *folder, const char *out1, const char *out2, int device, mcomh_digest_report *rep);
 
+/* ---- a record range of a -p archive: `minicom -d -R FIRST:COUNT` ----
+ * Records first .. first + count - 1 (first from 0) of what the full decode writes, and nothing else: the outputs of ranges that tile
+ * [0, n), concatenated, are the full decode byte for byte, and record i keeps its identity (without name.mcn it is still `@<i+1>`).  The
+ * range is clipped at the archive's end, as `head` clips; first == n or count == 0 gives an empty file and success; first > n is refused.
+ * *n_written = the records written.  device >= 0: on that GPU -- phase A of the decoders unchanged, mcom_range_check_dest over every
+ * source, mcom_range_decode_reads, mcom_qual_decode_rows, the names decoded whole (their CRC checked) and emitted from `first`; the
+ * rows on the card are count x (L + 1) bytes, not n x (L + 1), beside the stream files, which stay whole.  A path that ends in `.gz` is
+ * written as BGZF.  device == -1: the plain C++ twin, which decodes the whole table in memory and writes the slice -- the specification
+ * and the cross-check, not a fast path.  Both write the same bytes and refuse the same folders.
+ *   mcomh_decompress_order_range     reads, one per line
+ *   mcomh_decompress_fastq_range     four-line records with qual.mcq, and name.mcn when present
+ *   mcomh_decompress_order_pe_range  the same record range of BOTH files of a pair kept in input order (pe_order.txt): rows [first,
+ *                                    first + count) and [half + first, half + first + count); fastq != 0: four-line records with
+ *                                    qual_1.mcq / qual_2.mcq, and name_1.mcn / name_2.mcn when present
+ *   mcomh_qual_decode_rows           the host twin of mcom_qual_decode_rows (include/mcom.h): rows first_row .. of a `.mcq` member, a plain
+ *                                    loop over the segments they touch; the same bytes, the same members refused
+ * What a range does NOT check: the CRC-32 of a quality member (it covers all rows; the touched segments' own checks stay), and, on the
+ * GPU, whether a read OUTSIDE the range has its reference window inside ref.bin -- the one ground on which a range may be decoded from
+ * an archive that the full decode refuses.  The syntax of every line, every size and every destination are checked as ever.
+ * Refused, with a message on stderr and before a file is written: a folder that is not a -p archive (no input order to count in), a
+ * `minicom -q` archive (rqual*.mcq), a ragged archive (len.bin), first > n.  -1 then, and no output file.                              */
+int mcomh_decompress_order_range(const char *folder, const char *out_path, uint64_t first, uint64_t count, uint64_t *n_written, int device);
+int mcomh_decompress_fastq_range(const char *folder, const char *out_path, uint64_t first, uint64_t count, uint64_t *n_written, int device);
+int mcomh_decompress_order_pe_range(const char *folder, const char *out_path1, const char *out_path2, uint64_t first, uint64_t count, uint64_t *n_written, int device,
+                                    int fastq);
+int mcomh_qual_decode_rows(const uint8_t *in, uint64_t in_len, uint64_t first_row, uint64_t count, uint8_t *rows, uint64_t pitch, uint64_t *n_rows, uint32_t *L);
+
 /* results */
 size_t mcomh_n_contigs(const mcomh_pipeline *p);
 const char *mcomh_contig_ref(const mcomh_pipeline *p, size_t i, size_t *len);   /* consensus, NOT NUL-terminated */

@@ -480,7 +480,8 @@ def _quality_member(fastq: str, n: int, L: int, device: int, out_path: str, loss
         f.write(member.cpu().numpy().tobytes())
 
 
-def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None, gzip: bool = False) -> int:
+def decompress_file(path: str, out_path: str, out_path2: str | None = None, threads: int = 8, device: int | None = None, gzip: bool = False,
+                    records: tuple[int, int] | None = None) -> int:
     """`.minicom` -> reads, one per line: the original order for an archive written with -p, two files (line i of both a
     pair) for a paired-end archive.  Returns the number of reads (pairs for paired end).  device=None: host only; an
     integer: `.rans` and `.bwt` members decoded and the reads rebuilt on that GPU (pipeline.decompress(..., device=)); the other codecs
@@ -492,19 +493,27 @@ def decompress_file(path: str, out_path: str, out_path2: str | None = None, thre
     pipeline.bgzf_file turns it into the same bytes.  An archive made with quality_agree (qual_agree.txt) is decoded as ever; that its
     quality values are lossy is said in one line on stderr, as `minicom -d` says it.  An archive made with digest=True (digest.txt) is
     checked: the files just written are digested as the input was (pipeline.digest_check, on `device` when given) and McomError says which
-    part differs; the files are kept."""
+    part differs; the files are kept.  records=(first, count): only records first .. first + count - 1 (first from 0, clipped at the
+    archive's end) of a -p archive (pipeline.decompress_range, DESIGN.md section 3.19): the slice of what the call writes without it;
+    McomError for an archive without the input order, one made with -q or -V, and first > n.  A range is not checked against a digest."""
     import tempfile
     outs = [o for o in (out_path, out_path2) if o is not None]
     if gzip and not (device is not None and all(o.endswith(".gz") for o in outs)):
         from .pipeline import bgzf_file
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as plain:
             tmp = [os.path.join(plain, "out_%d" % k) for k in range(len(outs))]
-            n = decompress_file(path, tmp[0], tmp[1] if len(tmp) > 1 else None, threads=threads, device=device)
+            n = decompress_file(path, tmp[0], tmp[1] if len(tmp) > 1 else None, threads=threads, device=device, records=records)
             for t, o in zip(tmp, outs):
                 bgzf_file(t, o, device=device)
         return n
     with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
         kinds = unpack(path, td, threads=threads, device=device)
+        if records is not None:
+            from .pipeline import decompress_range
+            if kinds.get("pair_order") and out_path2 is None:
+                raise ValueError("an archive of a pair decodes into two files")
+            return decompress_range(td, out_path, int(records[0]), int(records[1]), device=device, fastq=bool(kinds.get("quality") or kinds.get("names")),
+                                    out_path2=out_path2 if kinds.get("pair_order") else None)
         n = _decode_folder(td, kinds, out_path, out_path2, device)
         if kinds.get("digest"):
             from .hip import McomError

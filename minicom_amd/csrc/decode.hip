@@ -11,6 +11,8 @@
 //   line check    every line parsed once by one lane with the host decoder's rules, before anything is decoded   (k_dc_check_lines)
 //   decode        sixteen lanes per read: the reference window (or a constant base) into an LDS row, the literals of the line patched
 //                 in, the row stored -- reverse-complemented when the direction bit is set -- as aligned 16-byte pieces (k_dc_reads)
+//   window        a range of rows alone: the placement check over all reads, a compacted list of the reads whose destination lies in
+//                 the window, the decode over that list                                        (k_dc_check_dest, k_dc_select, k_dc_reads_sel)
 // The only serial part is the chain of contig headers ("header c + 1 sits 4 + 2 num bytes behind header c"): mcom_decode_walk_headers
 // follows it on the host, four bytes read per contig.
 //
@@ -280,20 +282,17 @@ __device__ __forceinline__ void dc_row_steps(const DcReads &a, uint64_t m, bool 
 	__syncthreads();
 }
 
-__global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
+// Steps 1 to 4 of read m, for the sixteen lanes of group g: the body of k_dc_reads and of k_dc_reads_sel.  The row is stored at row
+// (destination - row0) of a.out; a destination below row0 is skipped (k_dc_reads: row0 = 0).  Every thread of the workgroup calls it.
+__device__ __forceinline__ void dc_read_body(const DcReads &a, uint64_t m, bool live, uint64_t row0, int g, int lane, uint8_t *row, uint64_t *s_dest)
 {
-	__shared__ __align__(16) uint8_t s_row[DC_RPB][DC_PITCH];
-	__shared__ uint64_t s_dest[DC_RPB];
-	const int g = threadIdx.x / DC_G, lane = threadIdx.x % DC_G;
-	const uint64_t m = (uint64_t)blockIdx.x * DC_RPB + g;
-	const bool live = m < a.n;
 	const int L = a.L;
-	uint8_t *row = s_row[g];
 	bool have; uint64_t off;
 	dc_row_steps<false>(a, m, live, g, lane, row, nullptr, 0, s_dest, have, off);
 	if (!live) return;
-	const uint64_t d = s_dest[g];
-	if (d == ~0ull) return;
+	uint64_t d = s_dest[g];
+	if (d == ~0ull || d < row0) return;
+	d -= row0;
 	bool rev = false;
 	if (a.dir && (m >> 3) < a.dir_bytes) rev = (a.dir[m >> 3] >> (m & 7)) & 1u;
 	// 4. the row, L characters and the newline, as the aligned 16-byte pieces of the output it covers
@@ -317,6 +316,68 @@ __global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
 			for (int j = 0; j < 16; ++j) { const int i = s + j; if (i >= 0 && i <= L) dst[i] = chr(i); }
 		}
 	}
+}
+
+__global__ __launch_bounds__(DC_THREADS) void k_dc_reads(const DcReads a)
+{
+	__shared__ __align__(16) uint8_t s_row[DC_RPB][DC_PITCH];
+	__shared__ uint64_t s_dest[DC_RPB];
+	const int g = threadIdx.x / DC_G, lane = threadIdx.x % DC_G;
+	const uint64_t m = (uint64_t)blockIdx.x * DC_RPB + g;
+	dc_read_body(a, m, m < a.n, 0, g, lane, s_row[g], s_dest);
+}
+
+// ---- a window of rows ---------------------------------------------------------------------------------
+//   placement  the check of step 3 on its own, over ALL reads of a source: one thread per read                      (k_dc_check_dest)
+//   selection  one thread per read: is its destination inside [win_first, win_first + win_count)?  The reads that are get a place in
+//              a compacted list, one atomic per wave from a ballot; the order of the list does not matter            (k_dc_select)
+//   decode     the body of k_dc_reads over the list: group k takes read sel[k], its row is destination - win_first.  The grid covers
+//              min(n, win_count) groups -- a row of the window is named by at most one read of an archive that has passed the
+//              placement check -- and a group beyond the list's length, which the kernel reads from the device, exits (k_dc_reads_sel)
+__global__ __launch_bounds__(DC_THREADS) void k_dc_check_dest(const uint64_t *__restrict__ dest, uint64_t dest0, uint64_t n, uint64_t n_rows,
+                                                              uint32_t *__restrict__ seen, uint32_t *__restrict__ flag)
+{
+	const uint64_t m = (uint64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+	if (m >= n) return;
+	const uint64_t d = dest ? dest[m] : dest0 + m;
+	if (d >= n_rows) { atomicOr(flag, MCOM_DECODE_F_DEST); return; }
+	const uint32_t bit = 1u << (d & 31);
+	if (atomicOr(seen + (d >> 5), bit) & bit) atomicOr(flag, MCOM_DECODE_F_DUP);
+}
+
+// sel: room for `cap` read indices; *count: cleared by the caller.  More reads inside the window than `cap` (a row named twice: cap is
+// at least the window's rows, or all reads) raise F_DUP and get no place.
+__global__ __launch_bounds__(DC_THREADS) void k_dc_select(const uint64_t *__restrict__ dest, uint64_t dest0, uint64_t n, uint64_t win_first, uint64_t win_count,
+                                                          uint64_t *__restrict__ sel, uint64_t cap, unsigned long long *__restrict__ count, uint32_t *__restrict__ flag)
+{
+	const uint64_t m = (uint64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+	const int lane = threadIdx.x & 63;
+	bool in = false;
+	if (m < n) { const uint64_t d = dest ? dest[m] : dest0 + m; in = d >= win_first && d - win_first < win_count; }
+	const unsigned long long mask = __ballot(in);
+	if (!mask) return;
+	const int leader = __ffsll(mask) - 1;
+	unsigned long long base = 0;
+	if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(mask));
+	base = __shfl(base, leader, 64);
+	if (!in) return;
+	const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1));
+	if (at < cap) sel[at] = m; else atomicOr(flag, MCOM_DECODE_F_DUP);
+}
+
+// a.n_rows = win_first + win_count and a.seen = nullptr: step 3 flags a destination behind the window, and the list holds none
+__global__ __launch_bounds__(DC_THREADS) void k_dc_reads_sel(const DcReads a, const uint64_t *__restrict__ sel, const unsigned long long *__restrict__ count, uint64_t cap,
+                                                             uint64_t win_first)
+{
+	__shared__ __align__(16) uint8_t s_row[DC_RPB][DC_PITCH];
+	__shared__ uint64_t s_dest[DC_RPB];
+	const int g = threadIdx.x / DC_G, lane = threadIdx.x % DC_G;
+	const uint64_t k = (uint64_t)blockIdx.x * DC_RPB + g;
+	uint64_t n_sel = *count; if (n_sel > cap) n_sel = cap;
+	bool live = k < n_sel;
+	const uint64_t m = live ? sel[k] : 0;
+	if (m >= a.n) live = false;                                            // (cannot be: the list is k_dc_select's)
+	dc_read_body(a, m, live, win_first, g, lane, s_row[g], s_dest);
 }
 
 // ---- entry points -----------------------------------------------------------------------------------------------------------
@@ -460,6 +521,15 @@ extern "C" int mcom_decode_check_lines(mcom_ctx *ctx, const uint8_t *d_text, uin
 	return MCOM_OK;
 }
 
+static void dc_fill(DcReads &a, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0, uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag)
+{
+	a.text = src->d_text; a.text_bytes = src->text_bytes; a.line_start = src->d_line_start; a.verbatim = src->verbatim;
+	a.ref = src->d_ref; a.ref_bytes = src->ref_bytes; a.ref_const = src->ref_const;
+	a.cid = src->d_cid; a.pos = src->d_pos; a.coff = src->d_coff; a.n_contigs = src->n_contigs;
+	a.dir = src->d_dir; a.dir_bytes = src->dir_bytes;
+	a.dest = d_dest; a.dest0 = dest0; a.n = n; a.L = L; a.out = d_out; a.n_rows = n_rows; a.seen = d_seen; a.flag = d_flag;
+}
+
 extern "C" int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
                                  uint8_t *d_out, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag)
 {
@@ -469,12 +539,40 @@ extern "C" int mcom_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint
 	if (src->d_text && !src->d_line_start) return mcom_fail(ctx, MCOM_E_ARG, "decode_reads: a text without its line index");
 	if (src->d_cid && (!src->d_ref || !src->d_pos || !src->d_coff)) return mcom_fail(ctx, MCOM_E_ARG, "decode_reads: a member table without its reference");
 	DcReads a;
-	a.text = src->d_text; a.text_bytes = src->text_bytes; a.line_start = src->d_line_start; a.verbatim = src->verbatim;
-	a.ref = src->d_ref; a.ref_bytes = src->ref_bytes; a.ref_const = src->ref_const;
-	a.cid = src->d_cid; a.pos = src->d_pos; a.coff = src->d_coff; a.n_contigs = src->n_contigs;
-	a.dir = src->d_dir; a.dir_bytes = src->dir_bytes;
-	a.dest = d_dest; a.dest0 = dest0; a.n = n; a.L = L; a.out = d_out; a.n_rows = n_rows; a.seen = d_seen; a.flag = d_flag;
+	dc_fill(a, src, n, L, d_dest, dest0, d_out, n_rows, d_seen, d_flag);
 	MCOM_LAUNCH(k_dc_reads, dim3((unsigned)((n + DC_RPB - 1) / DC_RPB)), dim3(DC_THREADS), 0, ctx->stream, a);
+	MCOM_LAUNCH_CHECK(ctx);
+	return MCOM_OK;
+}
+
+extern "C" int mcom_range_check_dest(mcom_ctx *ctx, const uint64_t *d_dest, uint64_t dest0, uint64_t n, uint64_t n_rows, uint32_t *d_seen, uint32_t *d_flag)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (n == 0) return MCOM_OK;
+	if (!d_seen || !d_flag || n >= DC_MAX_ITEMS) return mcom_fail(ctx, MCOM_E_ARG, "range_check_dest: bad argument");
+	MCOM_LAUNCH(k_dc_check_dest, dim3(dc_blocks(n)), dim3(DC_THREADS), 0, ctx->stream, d_dest, dest0, n, n_rows, d_seen, d_flag);
+	MCOM_LAUNCH_CHECK(ctx);
+	return MCOM_OK;
+}
+
+extern "C" int mcom_range_decode_reads(mcom_ctx *ctx, const mcom_decode_src *src, uint64_t n, int L, const uint64_t *d_dest, uint64_t dest0,
+                                        uint64_t win_first, uint64_t win_count, uint8_t *d_out, uint32_t *d_flag)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (n == 0 || win_count == 0) return MCOM_OK;
+	if (!src || !d_out || !d_flag || L < 1 || L > 256 || n >= (1ull << 34) || win_first + win_count < win_first) return mcom_fail(ctx, MCOM_E_ARG, "range_decode_reads: bad argument");
+	if (src->d_text && !src->d_line_start) return mcom_fail(ctx, MCOM_E_ARG, "range_decode_reads: a text without its line index");
+	if (src->d_cid && (!src->d_ref || !src->d_pos || !src->d_coff)) return mcom_fail(ctx, MCOM_E_ARG, "range_decode_reads: a member table without its reference");
+	const uint64_t cap = n < win_count ? n : win_count;
+	uint64_t *sel = nullptr;                                               // the count, then the list
+	MCOM_HIP(ctx, mcom_dmalloc(&sel, (cap + 1) * 8));
+	mcom_dfree_later(ctx, sel);
+	MCOM_HIP(ctx, hipMemsetAsync(sel, 0, 8, ctx->stream));
+	MCOM_LAUNCH(k_dc_select, dim3(dc_blocks(n)), dim3(DC_THREADS), 0, ctx->stream, d_dest, dest0, n, win_first, win_count, sel + 1, cap, (unsigned long long*)sel, d_flag);
+	MCOM_LAUNCH_CHECK(ctx);
+	DcReads a;
+	dc_fill(a, src, n, L, d_dest, dest0, d_out, win_first + win_count, nullptr, d_flag);
+	MCOM_LAUNCH(k_dc_reads_sel, dim3((unsigned)((cap + DC_RPB - 1) / DC_RPB)), dim3(DC_THREADS), 0, ctx->stream, a, (const uint64_t*)(sel + 1), (const unsigned long long*)sel, cap, win_first);
 	MCOM_LAUNCH_CHECK(ctx);
 	return MCOM_OK;
 }
@@ -588,12 +686,7 @@ extern "C" int mcom_agree_mask(mcom_ctx *ctx, const mcom_decode_src *src, uint64
 	if (src->d_text && !src->d_line_start) return mcom_fail(ctx, MCOM_E_ARG, "agree_mask: a text without its line index");
 	if (src->d_cid && (!src->d_ref || !src->d_pos || !src->d_coff || !d_cov)) return mcom_fail(ctx, MCOM_E_ARG, "agree_mask: a member table without its reference or its coverage");
 	DcAgree b;
-	DcReads &a = b.r;
-	a.text = src->d_text; a.text_bytes = src->text_bytes; a.line_start = src->d_line_start; a.verbatim = src->verbatim;
-	a.ref = src->d_ref; a.ref_bytes = src->ref_bytes; a.ref_const = src->ref_const;
-	a.cid = src->d_cid; a.pos = src->d_pos; a.coff = src->d_coff; a.n_contigs = src->n_contigs;
-	a.dir = src->d_dir; a.dir_bytes = src->dir_bytes;
-	a.dest = d_dest; a.dest0 = dest0; a.n = n; a.L = L; a.out = nullptr; a.n_rows = n_rows; a.seen = nullptr; a.flag = d_flag;
+	dc_fill(b.r, src, n, L, d_dest, dest0, nullptr, n_rows, nullptr, d_flag);
 	b.cov = d_cov; b.cov_bases = cov_bases; b.min_cov = min_cov; b.mask = d_mask; b.mask_pitch = mask_pitch;
 	MCOM_LAUNCH(k_dc_agree, dim3((unsigned)((n + DC_RPB - 1) / DC_RPB)), dim3(DC_THREADS), 0, ctx->stream, b);
 	MCOM_LAUNCH_CHECK(ctx);

@@ -172,12 +172,14 @@ __global__ __launch_bounds__(QV_THREADS) void k_qual_lens(const uint8_t *__restr
 	lens64[seg] = seg < n_seg ? (uint64_t)(lens16[2 * seg] | (uint32_t)lens16[2 * seg + 1] << 8) : 0ull;
 }
 
-// out: the flat image, n_rows * L bytes.  top: the largest power of two below A (0 for A = 1): the first step of the bisection.
+// Segments seg_base .. n_seg - 1 are decoded (n_seg: at most the member's).  out: the flat image of these segments, which begins with
+// segment seg_base: (n_seg - seg_base) * rps * L bytes, fewer where the member's last segment is short (seg_base = 0 and all segments:
+// the n_rows * L bytes of the whole member).  top: the largest power of two below A (0 for A = 1): the first step of the bisection.
 template <int LDS_TAB>
 __global__ __launch_bounds__(QV_THREADS) void k_qual_decode(const uint8_t *__restrict__ runs, const uint64_t *__restrict__ off, uint64_t payload_bytes,
                                                             const uint16_t *__restrict__ cum, uint32_t cum_words, const uint8_t *__restrict__ tabs, int id, uint32_t A, uint32_t Q,
-                                                            uint32_t top, uint8_t *__restrict__ out, uint64_t n_rows, uint32_t L, uint32_t rps, uint64_t n_seg,
-                                                            uint32_t *__restrict__ flag)
+                                                            uint32_t top, uint8_t *__restrict__ out, uint64_t n_rows, uint32_t L, uint32_t rps, uint64_t seg_base,
+                                                            uint64_t n_seg, uint32_t *__restrict__ flag)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t stage[QV_THREADS * QV_STAGE_PITCH];
 	__shared__ uint8_t s_val[256], s_mbin[256];
@@ -187,8 +189,8 @@ __global__ __launch_bounds__(QV_THREADS) void k_qual_decode(const uint8_t *__res
 	__syncthreads();
 	const uint16_t *const tab = LDS_TAB ? (const uint16_t*)s_cum : cum;
 	const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	const uint64_t seg = (uint64_t)blockIdx.x * QV_THREADS + threadIdx.x, wave_seg0 = seg - lane;
-	const uint64_t seg_bytes = (uint64_t)rps * L, raw_len = n_rows * L;
+	const uint64_t seg = seg_base + (uint64_t)blockIdx.x * QV_THREADS + threadIdx.x, wave_seg0 = seg - lane;
+	const uint64_t seg_bytes = (uint64_t)rps * L, raw_len = n_rows * L, out_at = seg_base * seg_bytes;   // out[0] is byte out_at of the member's image
 	uint32_t len = 0, x = 0, bad = 0;
 	const uint8_t *p = runs, *end = runs;
 	if (seg < n_seg) {
@@ -249,11 +251,12 @@ __global__ __launch_bounds__(QV_THREADS) void k_qual_decode(const uint8_t *__res
 			const uint64_t goff = seg_at + (uint64_t)r * 64 + piece * 16;
 			if (goff >= seg_end) continue;
 			const uint4 v = *(const uint4*)(wave_stage + (size_t)sseg * QV_STAGE_PITCH + piece * 16);
-			if (goff + 16 <= seg_end && ((uintptr_t)(out + goff) & 15) == 0) *(uint4*)(out + goff) = v;
+			uint8_t *const dst = out + (goff - out_at);                         // (gseg >= seg_base: goff >= out_at)
+			if (goff + 16 <= seg_end && ((uintptr_t)dst & 15) == 0) *(uint4*)dst = v;
 			else {
 				const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-				for (int k = 0; k < 16; ++k) if (goff + k < seg_end) out[goff + k] = (uint8_t)(vv[k >> 2] >> ((k & 3) * 8));
+				for (int k = 0; k < 16; ++k) if (goff + k < seg_end) dst[k] = (uint8_t)(vv[k >> 2] >> ((k & 3) * 8));
 			}
 		}
 		__syncthreads();
@@ -426,6 +429,54 @@ extern "C" int mcom_qual_encode(mcom_ctx *ctx, const uint8_t *d_rows, uint64_t n
 	return MCOM_OK;
 }
 
+namespace {
+// The coded form (kind 0, models 1 to 4) of a member whose header read_qheader has accepted: the tables parsed and uploaded, ALL run
+// lengths scanned and their sum set against the payload, then segments seg0 .. seg1 - 1 (seg1 <= n_seg) decoded into d_img, the flat image
+// that begins with segment seg0.  Synchronous.  MCOM_E_ARG with a message under `who` for what section 3.9 refuses.
+int decode_segments(mcom_ctx *ctx, Blocks &B, const QHeader &hd, const uint8_t *d_in, uint64_t seg0, uint64_t seg1, uint8_t *d_img, const char *who)
+{
+	const uint32_t L = hd.L;
+	const uint64_t n_seg = hd.n_seg();
+	int rc;
+	Geometry g; g.set(hd.map, L);
+	std::vector<uint8_t> ser(hd.table_bytes); std::vector<uint16_t> cum;
+	if (hd.table_bytes) { MCOM_HIP(ctx, hipMemcpyAsync(ser.data(), d_in + QHEADER_BYTES, hd.table_bytes, hipMemcpyDeviceToHost, ctx->stream)); MCOM_HIP(ctx, mcom_stream_sync(ctx)); }
+	if (!parse_tables(ser.data(), ser.size(), g, hd.model, cum)) return mcom_fail(ctx, MCOM_E_ARG, "%s: malformed tables", who);
+	uint8_t *d_tabs = nullptr; uint16_t *d_cum = nullptr; uint64_t *lens = nullptr, *off = nullptr; uint32_t *d_flag = nullptr;
+	if ((rc = upload_tabs(ctx, B, g, &d_tabs))) return rc;
+	MCOM_HIP(ctx, B.get(&d_cum, cum.size() * 2));
+	MCOM_HIP(ctx, B.get(&lens, 2 * (n_seg + 1) * 8 + 16));
+	off = lens + n_seg + 1; d_flag = (uint32_t*)(off + n_seg + 1);
+	MCOM_HIP(ctx, hipMemcpyAsync(d_cum, cum.data(), cum.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+	MCOM_HIP(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
+	const uint8_t *lens16 = d_in + QHEADER_BYTES + hd.table_bytes, *runs = lens16 + 2 * n_seg;
+	MCOM_LAUNCH(k_qual_lens, dim3(blocks_for(n_seg + 1)), dim3(QV_THREADS), 0, ctx->stream, lens16, n_seg, lens);
+	MCOM_LAUNCH_CHECK(ctx);
+	if ((rc = mcom_scan64(ctx, lens, off, n_seg + 1, nullptr))) return rc;
+	uint64_t payload = 0;
+	MCOM_HIP(ctx, hipMemcpyAsync(&payload, off + n_seg, 8, hipMemcpyDeviceToHost, ctx->stream));
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	if (payload != hd.payload_bytes) return mcom_fail(ctx, MCOM_E_ARG, "%s: the run lengths do not add up to the payload", who);
+	if (seg1 <= seg0) return MCOM_OK;
+	uint32_t top = 0;
+	if (g.A > 1) { top = 1; while (top * 2 < g.A) top *= 2; }
+	const size_t cum_bytes = cum.size() * 2;
+	const uint32_t cum_words = (uint32_t)cum.size();
+	if (cum_bytes <= QV_LDS_TABLE_BYTES)
+		MCOM_LAUNCH(k_qual_decode<1>, dim3(blocks_for(seg1 - seg0)), dim3(QV_THREADS), cum_bytes, ctx->stream, runs, (const uint64_t*)off, payload, (const uint16_t*)d_cum, cum_words,
+		            (const uint8_t*)d_tabs, (int)hd.model, g.A, g.Q, top, d_img, hd.n_rows, L, hd.rps, seg0, seg1, d_flag);
+	else
+		MCOM_LAUNCH(k_qual_decode<0>, dim3(blocks_for(seg1 - seg0)), dim3(QV_THREADS), 0, ctx->stream, runs, (const uint64_t*)off, payload, (const uint16_t*)d_cum, cum_words,
+		            (const uint8_t*)d_tabs, (int)hd.model, g.A, g.Q, top, d_img, hd.n_rows, L, hd.rps, seg0, seg1, d_flag);
+	MCOM_LAUNCH_CHECK(ctx);
+	uint32_t flag = 0;
+	MCOM_HIP(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	if (flag) return mcom_fail(ctx, MCOM_E_ARG, "%s: corrupt member (flag 0x%x)", who, flag);
+	return MCOM_OK;
+}
+}  // namespace
+
 extern "C" int mcom_qual_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint8_t *d_rows, uint64_t pitch, uint64_t cap_rows, uint64_t *n_rows, uint32_t *L_out)
 {
 	if (!ctx) return MCOM_E_ARG;
@@ -458,44 +509,59 @@ extern "C" int mcom_qual_decode(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_
 		if (crc != hd.crc) return refuse("CRC mismatch");
 		if (raw) MCOM_HIP(ctx, hipMemcpyAsync(d_flat, d_in + QHEADER_BYTES, raw, hipMemcpyDeviceToDevice, ctx->stream));
 	} else {
-		Geometry g; g.set(hd.map, L);
-		std::vector<uint8_t> ser(hd.table_bytes); std::vector<uint16_t> cum;
-		if (hd.table_bytes) { MCOM_HIP(ctx, hipMemcpyAsync(ser.data(), d_in + QHEADER_BYTES, hd.table_bytes, hipMemcpyDeviceToHost, ctx->stream)); MCOM_HIP(ctx, mcom_stream_sync(ctx)); }
-		if (!parse_tables(ser.data(), ser.size(), g, hd.model, cum)) return refuse("malformed tables");
-		uint8_t *d_tabs = nullptr; uint16_t *d_cum = nullptr; uint64_t *lens = nullptr, *off = nullptr; uint32_t *d_flag = nullptr;
-		if ((rc = upload_tabs(ctx, B, g, &d_tabs))) return rc;
-		MCOM_HIP(ctx, B.get(&d_cum, cum.size() * 2));
-		MCOM_HIP(ctx, B.get(&lens, 2 * (n_seg + 1) * 8 + 16));
-		off = lens + n_seg + 1; d_flag = (uint32_t*)(off + n_seg + 1);
-		MCOM_HIP(ctx, hipMemcpyAsync(d_cum, cum.data(), cum.size() * 2, hipMemcpyHostToDevice, ctx->stream));
-		MCOM_HIP(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-		const uint8_t *lens16 = d_in + QHEADER_BYTES + hd.table_bytes, *runs = lens16 + 2 * n_seg;
-		MCOM_LAUNCH(k_qual_lens, dim3(blocks_for(n_seg + 1)), dim3(QV_THREADS), 0, ctx->stream, lens16, n_seg, lens);
-		MCOM_LAUNCH_CHECK(ctx);
-		if ((rc = mcom_scan64(ctx, lens, off, n_seg + 1, nullptr))) return rc;
-		uint64_t payload = 0;
-		MCOM_HIP(ctx, hipMemcpyAsync(&payload, off + n_seg, 8, hipMemcpyDeviceToHost, ctx->stream));
-		MCOM_HIP(ctx, mcom_stream_sync(ctx));
-		if (payload != hd.payload_bytes) return refuse("the run lengths do not add up to the payload");
-		uint32_t top = 0;
-		if (g.A > 1) { top = 1; while (top * 2 < g.A) top *= 2; }
-		const size_t cum_bytes = cum.size() * 2;
-		const uint32_t cum_words = (uint32_t)cum.size();
-		if (cum_bytes <= QV_LDS_TABLE_BYTES)
-			MCOM_LAUNCH(k_qual_decode<1>, dim3(blocks_for(n_seg)), dim3(QV_THREADS), cum_bytes, ctx->stream, runs, (const uint64_t*)off, payload, (const uint16_t*)d_cum, cum_words,
-			            (const uint8_t*)d_tabs, (int)hd.model, g.A, g.Q, top, d_flat, hd.n_rows, L, hd.rps, n_seg, d_flag);
-		else
-			MCOM_LAUNCH(k_qual_decode<0>, dim3(blocks_for(n_seg)), dim3(QV_THREADS), 0, ctx->stream, runs, (const uint64_t*)off, payload, (const uint16_t*)d_cum, cum_words,
-			            (const uint8_t*)d_tabs, (int)hd.model, g.A, g.Q, top, d_flat, hd.n_rows, L, hd.rps, n_seg, d_flag);
-		MCOM_LAUNCH_CHECK(ctx);
-		uint32_t flag = 0;
-		MCOM_HIP(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-		MCOM_HIP(ctx, mcom_stream_sync(ctx));
-		if (flag) { *n_rows = 0; *L_out = 0; return mcom_fail(ctx, MCOM_E_ARG, "qual_decode: corrupt member (flag 0x%x)", flag); }
+		if ((rc = decode_segments(ctx, B, hd, d_in, 0, n_seg, d_flat, "qual_decode"))) { if (rc == MCOM_E_ARG) { *n_rows = 0; *L_out = 0; } return rc; }
 		if ((rc = mcom_device_crc32(ctx, d_flat, raw, &crc))) return rc;
 		if (crc != hd.crc) return refuse("CRC mismatch");
 	}
 	if (raw && pitch != L) MCOM_HIP(ctx, hipMemcpy2DAsync(d_rows, pitch, d_flat, L, L, hd.n_rows, hipMemcpyDeviceToDevice, ctx->stream));
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	return MCOM_OK;
+}
+
+// Rows first_row .. first_row + count - 1 alone.  Only the segments that hold them are decoded; the member's
+// CRC-32 covers all raw bytes and is not checked here -- a range that is the whole member takes mcom_qual_decode's path, CRC included.
+// Kind 1 (an embedded `.rans` member) has no segments of rows: it is decoded whole into a temporary of n_rows * L bytes and sliced.
+extern "C" int mcom_qual_decode_rows(mcom_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t first_row, uint64_t count, uint8_t *d_rows, uint64_t pitch,
+                                     uint64_t *n_rows, uint32_t *L_out)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (!n_rows || !L_out || (in_len && !d_in)) return mcom_fail(ctx, MCOM_E_ARG, "qual_decode_rows: null pointer");
+	*n_rows = 0; *L_out = 0;
+	if (in_len < QHEADER_BYTES) return mcom_fail(ctx, MCOM_E_ARG, "qual_decode_rows: not a .mcq member (%llu bytes)", (unsigned long long)in_len);
+	uint8_t hb[QHEADER_BYTES + mcom_rans::HEADER_BYTES] = {0};
+	const size_t head_bytes = in_len < sizeof hb ? (size_t)in_len : sizeof hb;
+	MCOM_HIP(ctx, hipMemcpyAsync(hb, d_in, head_bytes, hipMemcpyDeviceToHost, ctx->stream));
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	QHeader hd;
+	if (!read_qheader(hb, in_len, hd)) return mcom_fail(ctx, MCOM_E_ARG, "qual_decode_rows: the header does not describe this member");
+	if (first_row > hd.n_rows) return mcom_fail(ctx, MCOM_E_ARG, "qual_decode_rows: row %llu of %llu", (unsigned long long)first_row, (unsigned long long)hd.n_rows);
+	if (count > hd.n_rows - first_row) count = hd.n_rows - first_row;
+	if (first_row == 0 && count == hd.n_rows) return mcom_qual_decode(ctx, d_in, in_len, d_rows, pitch, hd.n_rows, n_rows, L_out);
+	*n_rows = hd.n_rows; *L_out = hd.L;
+	auto refuse = [&](const char *why) { *n_rows = 0; *L_out = 0; return mcom_fail(ctx, MCOM_E_ARG, "qual_decode_rows: %s", why); };
+	if (pitch < hd.L || (count && !d_rows)) return refuse("null pointer or a pitch below L");
+	Blocks B(ctx);
+	const uint32_t L = hd.L;
+	const uint64_t raw = hd.raw_len();
+	int rc;
+	const uint8_t *src = nullptr;                                          // row first_row of a flat image
+	if (hd.kind == KIND_RANS) {
+		uint8_t *d_flat = nullptr; uint64_t got = 0;
+		MCOM_HIP(ctx, B.get(&d_flat, raw));
+		if ((rc = mcom_rans_decode(ctx, d_in + QHEADER_BYTES, in_len - QHEADER_BYTES, d_flat, raw, &got)) || got != raw) { *n_rows = 0; *L_out = 0; return rc ? rc : mcom_fail(ctx, MCOM_E_ARG, "qual_decode_rows: embedded length"); }
+		src = d_flat + first_row * L;
+	} else if (hd.model == Q_STORED) src = d_in + QHEADER_BYTES + first_row * L;
+	else {
+		// every table and run length is judged as ever; a kernel runs over the touched segments only
+		const uint64_t seg0 = count ? first_row / hd.rps : 0, seg1 = count ? (first_row + count - 1) / hd.rps + 1 : 0;
+		uint64_t img_bytes = (seg1 - seg0) * (uint64_t)hd.rps * L;
+		if (seg1 && raw - seg0 * (uint64_t)hd.rps * L < img_bytes) img_bytes = raw - seg0 * (uint64_t)hd.rps * L;
+		uint8_t *d_img = nullptr;
+		MCOM_HIP(ctx, B.get(&d_img, img_bytes));
+		if ((rc = decode_segments(ctx, B, hd, d_in, seg0, seg1, d_img, "qual_decode_rows"))) { if (rc == MCOM_E_ARG) { *n_rows = 0; *L_out = 0; } return rc; }
+		src = d_img + (first_row - seg0 * hd.rps) * L;
+	}
+	if (count) MCOM_HIP(ctx, hipMemcpy2DAsync(d_rows, pitch, src, L, L, count, hipMemcpyDeviceToDevice, ctx->stream));
 	MCOM_HIP(ctx, mcom_stream_sync(ctx));
 	return MCOM_OK;
 }

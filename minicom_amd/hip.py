@@ -213,6 +213,8 @@ def load_library():
     L.mcom_decode_pe_dest.restype = i32; L.mcom_decode_pe_dest.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, u64, vp, C.POINTER(u64), vp]
     L.mcom_decode_check_lines.restype = i32; L.mcom_decode_check_lines.argtypes = [vp, vp, u64, vp, u64, i32, i32, vp]
     L.mcom_decode_reads.restype = i32; L.mcom_decode_reads.argtypes = [vp, C.POINTER(DecodeSrc), u64, i32, vp, u64, vp, u64, vp, vp]
+    L.mcom_range_check_dest.restype = i32; L.mcom_range_check_dest.argtypes = [vp, vp, u64, u64, u64, vp, vp]
+    L.mcom_range_decode_reads.restype = i32; L.mcom_range_decode_reads.argtypes = [vp, C.POINTER(DecodeSrc), u64, i32, vp, u64, u64, u64, vp, vp]
     L.mcom_verify_room.restype = u64; L.mcom_verify_room.argtypes = [u64, u64]
     L.mcom_verify_ordered.restype = i32; L.mcom_verify_ordered.argtypes = [vp, C.POINTER(VerifyTable), C.POINTER(VerifyTable), i32, C.POINTER(VerifyReport)]
     L.mcom_verify_multiset.restype = i32; L.mcom_verify_multiset.argtypes = [vp, C.POINTER(VerifyTable), C.POINTER(VerifyTable), i32, C.POINTER(VerifyReport)]
@@ -238,6 +240,7 @@ def load_library():
     L.mcom_test_qual_pblock_tile_rows.restype = C.c_uint32; L.mcom_test_qual_pblock_tile_rows.argtypes = []
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.mcom_qual_decode_rows.restype = i32; L.mcom_qual_decode_rows.argtypes = [vp, vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_name_bound.restype = u64; L.mcom_name_bound.argtypes = [u64]
     L.mcom_name_encode.restype = i32; L.mcom_name_encode.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_name_info.restype = i32; L.mcom_name_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64)]
@@ -977,6 +980,17 @@ class Context:
         if out is None:
             out = torch.zeros(n_rows * (L + 1), dtype=torch.uint8, device=self.device)
         flag = self._dflag()
+        src, ptr, keep = self._decode_src(n, text, line_start, verbatim, ref, ref_const, cid, pos, coff, dirbits)
+        if check and src.d_text:
+            self._check(self.lib.mcom_decode_check_lines(self._h, src.d_text, src.text_bytes, src.d_line_start, n, L, int(verbatim), self._p(flag)))
+        self._check(self.lib.mcom_decode_reads(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, self._p(out), n_rows, self._p(seen) if seen is not None else None, self._p(flag)))
+        self.sync()
+        return out, int(flag.item())
+
+    def _decode_src(self, n, text, line_start, verbatim, ref, ref_const, cid, pos, coff, dirbits):
+        """the mcom_decode_src of decode_reads' keyword arguments: (src, ptr, keep) -- ptr(tensor, dtype) gives a device address and keeps the
+        tensor alive in `keep`, which the caller holds until the call has been synchronised"""
+        torch = _torch()
         src = DecodeSrc()
         keep = []
         def ptr(t, dt):
@@ -994,9 +1008,35 @@ class Context:
         src.d_ref = ptr(ref, torch.uint8); src.ref_bytes = int(ref.shape[0]) if ref is not None else 0; src.ref_const = ord(ref_const)
         src.d_cid = ptr(cid, torch.int32); src.d_pos = ptr(pos, torch.int32); src.d_coff = ptr(coff, torch.int64); src.n_contigs = (int(coff.shape[0]) - 1) if coff is not None else 0
         src.d_dir = ptr(dirbits, torch.uint8); src.dir_bytes = int(dirbits.shape[0]) if dirbits is not None else 0
-        if check and src.d_text:
-            self._check(self.lib.mcom_decode_check_lines(self._h, src.d_text, src.text_bytes, src.d_line_start, n, L, int(verbatim), self._p(flag)))
-        self._check(self.lib.mcom_decode_reads(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, self._p(out), n_rows, self._p(seen) if seen is not None else None, self._p(flag)))
+        return src, ptr, keep
+
+    # ---- a window of rows (`minicom -d -R`) ----
+    def decode_check_dest(self, n: int, n_rows: int, dest=None, dest0: int = 0, seen=None):
+        """mcom_range_check_dest over the n reads of one source: destinations dest (int64 device vector; None: dest0 + m) against n_rows
+        rows.  seen: an int32 device vector of n_rows / 32 + 1 zeroed words shared by the sources of an archive (made when None).  Returns
+        (flag, seen): DECODE_F_DEST for a destination >= n_rows, DECODE_F_DUP for a row named twice.  Nothing is decoded."""
+        torch = _torch()
+        if seen is None:
+            seen = torch.zeros(n_rows // 32 + 1, dtype=torch.int32, device=self.device)
+        flag = self._dflag()
+        d = dest.contiguous() if dest is not None and dest.numel() else None
+        self._check(self.lib.mcom_range_check_dest(self._h, self._p(d, torch.int64) if d is not None else None, dest0, n, n_rows, self._p(seen), self._p(flag)))
+        self.sync()
+        return int(flag.item()), seen
+
+    def decode_reads_window(self, n: int, L: int, win_first: int, win_count: int, text=None, line_start=None, verbatim=False, ref=None, ref_const="A", cid=None, pos=None,
+                            coff=None, dirbits=None, dest=None, dest0: int = 0, out=None):
+        """mcom_range_decode_reads: the reads of the source (decode_reads' keyword arguments) whose destination lies in [win_first,
+        win_first + win_count) to row destination - win_first of `out` (uint8, win_count * (L + 1) bytes at any address, made when None).
+        Nothing else is decoded or written.  Returns (out, flag)."""
+        torch = _torch()
+        if out is None:
+            out = torch.zeros(max(win_count * (L + 1), 1), dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < win_count * (L + 1):
+            raise McomError("decode_reads_window: out must hold %d rows of %d + 1 bytes" % (win_count, L))
+        flag = self._dflag()
+        src, ptr, keep = self._decode_src(n, text, line_start, verbatim, ref, ref_const, cid, pos, coff, dirbits)
+        self._check(self.lib.mcom_range_decode_reads(self._h, C.byref(src), n, L, ptr(dest, torch.int64), dest0, win_first, win_count, out.data_ptr(), self._p(flag)))
         self.sync()
         return out, int(flag.item())
 
@@ -1178,6 +1218,33 @@ class Context:
         gn, gL = C.c_uint64(), C.c_uint32()
         self._check(self.lib.mcom_qual_decode(self._h, self._p(member, torch.uint8), n_in, out.data_ptr(), pitch, int(out.shape[0]), C.byref(gn), C.byref(gL)))
         return out[:n, :L]
+
+    def qual_decode_rows(self, member, first: int, count: int, pitch: int | None = None, out=None):
+        """mcom_qual_decode_rows: rows first .. first + count - 1 of a `.mcq` member (uint8 device tensor; count
+        clipped at the member's end) as a uint8 device matrix [count, L].  Only the touched segments are decoded and the member's CRC-32 is
+        not checked, unless the range is the whole member.  pitch: the row stride of a fresh result (default L); out: a uint8 device matrix
+        [>= count, >= L] with contiguous rows to decode into instead.  McomError for a refused member and for first > n."""
+        torch = _torch()
+        n_in = int(member.shape[0])
+        head = bytes(member[:64].cpu().numpy())
+        n, L = C.c_uint64(), C.c_uint32()
+        if self.lib.mcom_qual_info(head if head else None, n_in, C.byref(n), C.byref(L)):
+            raise McomError("qual_decode_rows: not a .mcq member")
+        n, L = int(n.value), int(L.value)
+        if first < 0 or count < 0 or first > n:
+            raise McomError("qual_decode_rows: rows %d .. + %d of %d" % (first, count, n))
+        count = min(int(count), n - int(first))
+        if out is None:
+            pitch = L if pitch is None else int(pitch)
+            if pitch < L:
+                raise McomError("qual_decode_rows: pitch %d below L = %d" % (pitch, L))
+            out = torch.empty((max(count, 1), pitch), dtype=torch.uint8, device=self.device)
+        if out.dim() != 2 or out.dtype != torch.uint8 or out.stride(1) != 1 or int(out.shape[1]) < L or int(out.shape[0]) < count:
+            raise McomError("qual_decode_rows: out must be a uint8 matrix of at least %d contiguous rows of at least %d bytes" % (count, L))
+        row_pitch = int(out.stride(0)) if int(out.shape[0]) > 1 else max(L, int(out.shape[1]))
+        gn, gL = C.c_uint64(), C.c_uint32()
+        self._check(self.lib.mcom_qual_decode_rows(self._h, self._p(member, torch.uint8), n_in, int(first), count, out.data_ptr(), row_pitch, C.byref(gn), C.byref(gL)))
+        return out[:count, :L]
 
     GATHER_F_BOUNDS, GATHER_F_DUP = 1, 2
 

@@ -27,9 +27,23 @@
 // decompress --check-digest [--gpu] DIR OUT1 [OUT2]: an archive made with -K (DIR holds digest.txt): the output
 // files are digested as the input was (on GPU 0 with --gpu, by the host twin without) and set against it, every key that the archive's
 // kind can answer; one line says what was compared.  Exit status as --verify: 0 identical, 2 different, 1 refused or error.
+// decompress --range FIRST COUNT ...: in front of the plain decoder of a -p archive (`[--gpu] DIR OUT false true nthr`), of --fastq and of
+// --order-pe / --fastq-order-pe: records FIRST .. FIRST + COUNT - 1 (FIRST from 0, the range clipped at the archive's end) of what the mode
+// writes without it, and nothing else (mcomh_decompress_*_range).  A default-mode, -q or -V archive is refused.
 #include "../../../include/mcom_host.h"
 #include <cstdio>
 #include <cstring>
+
+static bool g_range = false;                           // --range FIRST COUNT
+static uint64_t g_first = 0, g_count = 0;
+
+static bool decimal(const char *p, uint64_t *v)
+{
+	if (!*p || strlen(p) > 19) return false;
+	*v = 0;
+	for (; *p; ++p) { if (*p < '0' || *p > '9') return false; *v = *v * 10 + (uint64_t)(*p - '0'); }
+	return true;
+}
 
 static void examples(const char *what, const uint64_t *ex, uint32_t n)
 {
@@ -158,7 +172,7 @@ static int fastq(int argc, char **argv)
 	if (gpu) { --argc; ++argv; }
 	if (argc < 3) { fprintf(stderr, "usage: decompress --fastq [--gpu] DIR OUT.fastq\n"); return 1; }
 	uint64_t n = 0;
-	if (gpu ? mcomh_decompress_fastq_gpu(argv[1], argv[2], &n, 0) : mcomh_decompress_fastq(argv[1], argv[2], &n)) {
+	if (g_range ? mcomh_decompress_fastq_range(argv[1], argv[2], g_first, g_count, &n, gpu ? 0 : -1) : gpu ? mcomh_decompress_fastq_gpu(argv[1], argv[2], &n, 0) : mcomh_decompress_fastq(argv[1], argv[2], &n)) {
 		fprintf(stderr, "decompress: %s is not a complete, consistent -p archive with quality values%s\n", argv[1], gpu ? ", or the GPU route is not available" : "");
 		return 1;
 	}
@@ -201,7 +215,8 @@ static int order_pe(int argc, char **argv, bool fastq)
 	if (gpu) { --argc; ++argv; }
 	if (argc < 4) { fprintf(stderr, "usage: decompress %s [--gpu] DIR OUT_1 OUT_2\n", fastq ? "--fastq-order-pe" : "--order-pe"); return 1; }
 	uint64_t n = 0;
-	const int rc = fastq ? (gpu ? mcomh_decompress_fastq_order_pe_gpu(argv[1], argv[2], argv[3], &n, 0) : mcomh_decompress_fastq_order_pe(argv[1], argv[2], argv[3], &n))
+	const int rc = g_range ? mcomh_decompress_order_pe_range(argv[1], argv[2], argv[3], g_first, g_count, &n, gpu ? 0 : -1, fastq)
+	             : fastq ? (gpu ? mcomh_decompress_fastq_order_pe_gpu(argv[1], argv[2], argv[3], &n, 0) : mcomh_decompress_fastq_order_pe(argv[1], argv[2], argv[3], &n))
 	                     : (gpu ? mcomh_decompress_order_pe_gpu(argv[1], argv[2], argv[3], &n, 0) : mcomh_decompress_order_pe(argv[1], argv[2], argv[3], &n));
 	if (rc) { fprintf(stderr, "decompress: %s is not a complete, consistent archive of a pair kept in input order%s%s\n", argv[1], fastq ? " with quality values" : "", gpu ? ", or the GPU route is not available" : ""); return 1; }
 	fprintf(stdout, "%llu pairs\n", (unsigned long long)n);
@@ -246,6 +261,14 @@ static int verify_ragged(int argc, char **argv)
 
 int main(int argc, char **argv)
 {
+	if (argc > 1 && !strcmp(argv[1], "--range")) {
+		if (argc < 4 || !decimal(argv[2], &g_first) || !decimal(argv[3], &g_count)) { fprintf(stderr, "usage: decompress --range FIRST COUNT (decimal numbers, FIRST from 0) in front of a -p decode, --fastq, --order-pe or --fastq-order-pe\n"); return 1; }
+		g_range = true;
+		argv[3] = argv[0]; argc -= 3; argv += 3;
+		const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+		const bool mode_ok = argc > 1 && (!strcmp(argv[1], "--fastq") || !strcmp(argv[1], "--order-pe") || !strcmp(argv[1], "--fastq-order-pe") || gpu || argv[1][0] != '-');
+		if (!mode_ok) { fprintf(stderr, "decompress: --range goes with the plain decode of a -p archive, --fastq, --order-pe and --fastq-order-pe only\n"); return 1; }
+	}
 	if (argc > 1 && !strcmp(argv[1], "--check-digest")) return check_digest(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify-ragged")) return verify_ragged(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--agree-mask")) return agree_mask(argc - 1, argv + 1);
@@ -267,7 +290,11 @@ int main(int argc, char **argv)
 	int rc;
 	if (pe) {
 		if (argc < 7) { fprintf(stderr, "decompress: paired-end archives need OUT2\n"); return 1; }
+		if (g_range) { fprintf(stderr, "decompress: --range needs a -p archive: a paired-end archive of the default mode keeps no input order\n"); return 1; }
 		rc = gpu ? mcomh_decompress_pe_gpu(argv[1], argv[2], argv[6], &n, 0) : mcomh_decompress_pe(argv[1], argv[2], argv[6], &n);
+	} else if (g_range) {
+		if (!order) { fprintf(stderr, "decompress: --range needs a -p archive: without the input order there is nothing to count a range in\n"); return 1; }
+		rc = mcomh_decompress_order_range(argv[1], argv[2], g_first, g_count, &n, gpu ? 0 : -1);
 	} else if (gpu) rc = order ? mcomh_decompress_order_gpu(argv[1], argv[2], &n, 0) : mcomh_decompress_gpu(argv[1], argv[2], &n, 0);
 	else rc = order ? mcomh_decompress_order(argv[1], argv[2], &n) : mcomh_decompress(argv[1], argv[2], &n);
 	if (rc) { fprintf(stderr, "decompress: %s does not hold a complete, consistent set of stream files%s\n", argv[1], gpu ? ", or the GPU route is not available" : ""); return 1; }

@@ -7,6 +7,7 @@
 #include "../../include/mcom_host.h"
 #include "mcom_ragged.hpp"
 #include "mcom_agree.hpp"
+#include "mcom_range.hpp"
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -604,19 +605,20 @@ bool index_names(NameText &t, uint64_t n)
 	for (uint64_t i = 0; i < t.len; ++i) if (t.text[i] == '\n') t.at.push_back(i + 1);
 	return t.at.size() == 2 * n + 1;
 }
-// reads: rows of L characters from row `first`; names NULL: records `@<i+1>` with a bare '+'
-bool write_records_named(const char *path, const char *reads, const std::vector<uint8_t> &quals, const NameText *names, uint64_t n, int L)
+// reads, quals: rows of L characters, row 0 the first record written; names NULL: records `@<i+1>` with a bare '+'.  base: the number the
+// first record has in the archive (a range, section 3.19): it picks the names and numbers the records
+bool write_records_named(const char *path, const char *reads, const std::vector<uint8_t> &quals, const NameText *names, uint64_t n, int L, uint64_t base = 0)
 {
 	FILE *out = fopen(path, "wb");
 	if (!out) return false;
 	bool ok = true;
 	for (uint64_t i = 0; i < n && ok; ++i) {
 		if (names) {
-			const uint64_t a = names->at[2 * i], b = names->at[2 * i + 1], c = names->at[2 * i + 2];
+			const uint64_t a = names->at[2 * (base + i)], b = names->at[2 * (base + i) + 1], c = names->at[2 * (base + i) + 2];
 			ok = fputc('@', out) != EOF && fwrite(names->text.data() + a, 1, b - a, out) == b - a && fwrite(reads + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+", out) >= 0 &&
 			     fwrite(names->text.data() + b, 1, c - b, out) == c - b;
 		} else
-			ok = fprintf(out, "@%llu\n", (unsigned long long)(i + 1)) > 0 && fwrite(reads + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0;
+			ok = fprintf(out, "@%llu\n", (unsigned long long)(base + i + 1)) > 0 && fwrite(reads + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputs("\n+\n", out) >= 0;
 		ok = ok && fwrite(quals.data() + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
 	}
 	if (fclose(out) != 0 || !ok) { remove(path); return false; }
@@ -681,6 +683,108 @@ extern "C" int mcomh_decompress_order_pe(const char *folder, const char *out_pat
 extern "C" int mcomh_decompress_fastq_order_pe(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs)
 {
 	try { return decompress_fastq_order_pe_impl(folder, out_path1, out_path2, n_pairs); } catch (...) { return -1; }
+}
+
+// ---- a record range of a -p archive (`minicom -d -R FIRST:COUNT`) -------------------------------------------
+// The host route is the specification and the cross-check, not a fast path: the whole table by decompress_order_impl -- so every check of
+// the full decode is made -- then the slice.  Quality rows come from mcomh_qual_decode_rows, which decodes the touched segments alone
+// and, like the device, cannot check the member's CRC for a part; the names are decoded whole.  The refusals that need no decoding are
+// made here for both routes, before a file is written.
+namespace {
+const char *range_refusal(const std::string &dir)
+{
+	if (!exists(dir + "/info.txt")) return "no info.txt: not a folder of stream files";
+	if (exists(dir + "/rqual.mcq") || exists(dir + "/rqual_1.mcq") || exists(dir + "/rqual_2.mcq")) return "an archive made with -q keeps its records in an order of its own: there is no input order to count a range in";
+	if (!exists(dir + "/allA.ids.bin")) return "not a -p archive: there is no input order to count a range in";
+	if (mcom_ragged_present(dir.c_str())) return "an archive made with -V (len.bin): a range of records of differing lengths is not built";
+	return nullptr;
+}
+
+// the rows [first, first + count) of a quality member that must state n rows of L bytes
+bool load_quals_rows(const std::string &path, uint64_t n, int L, uint64_t first, uint64_t count, std::vector<uint8_t> &quals)
+{
+	std::vector<uint8_t> member;
+	if (!slurp(path, member)) return false;
+	uint64_t qn = 0; uint32_t qL = 0;
+	if (mcomh_qual_info(member.data(), member.size(), &qn, &qL) || qn != n || (int)qL != L) return false;
+	quals.assign((size_t)count * (size_t)L + 1, 0);
+	return !mcomh_qual_decode_rows(member.data(), member.size(), first, count, quals.data(), (uint64_t)L, &qn, &qL) && qn == n && (int)qL == L;
+}
+
+int range_host(const char *folder, const char *out_path1, const char *out_path2, uint64_t first, uint64_t count, uint64_t *n_written, bool pair, bool fastq)
+{
+	const std::string dir(folder);
+	std::vector<char> reads; int L = 0; uint64_t n_rows = 0, n = 0;
+	if (decompress_order_impl(folder, nullptr, &n_rows, &reads, &L)) { fprintf(stderr, "minicom decoder: %s is not a complete, consistent -p archive\n", folder); return -1; }
+	n = n_rows;
+	if (pair && !pair_count(dir, n_rows, n)) { fprintf(stderr, "minicom decoder: %s: no pe_order.txt that states half the reads' number: not a pair kept in input order\n", folder); return -1; }
+	if (first > n) { fprintf(stderr, "minicom decoder: the range begins at record %llu (from 0), the archive holds %llu\n", (unsigned long long)first, (unsigned long long)n); return -1; }
+	if (count > n - first) count = n - first;
+	const int n_files = pair ? 2 : 1;
+	const char *paths[2] = {out_path1, out_path2};
+	std::vector<uint8_t> q[2];
+	NameText nm[2];
+	bool named = false;
+	if (fastq) {
+		const char *qname[2] = {pair ? "/qual_1.mcq" : "/qual.mcq", "/qual_2.mcq"}, *nname[2] = {pair ? "/name_1.mcn" : "/name.mcn", "/name_2.mcn"};
+		for (int k = 0; k < n_files; ++k) if (!load_quals_rows(dir + qname[k], n, L, first, count, q[k])) { fprintf(stderr, "minicom decoder: %s%s is missing, refused or states another number or length than the reads\n", folder, qname[k]); return -1; }
+		std::vector<uint8_t> m[2];
+		const bool has1 = slurp(dir + nname[0], m[0]), has2 = pair && slurp(dir + nname[1], m[1]);
+		if (pair && has1 != has2) return -1;                                    // name_2 is coded against name_1; one alone is no archive
+		named = has1;
+		for (int k = 0; k < n_files && named; ++k) {
+			uint64_t nn = 0, tl = 0;
+			if ((k ? mcomh_name_info_mate(m[k].data(), m[k].size(), &nn, &tl) : mcomh_name_info(m[k].data(), m[k].size(), &nn, &tl)) || nn != n) return -1;
+			nm[k].text.resize(tl + 1);
+			if ((k ? mcomh_name_decode_mate(m[k].data(), m[k].size(), nm[0].text.data(), nm[0].len, nm[k].text.data(), tl, &tl, &nn)
+			       : mcomh_name_decode(m[k].data(), m[k].size(), nm[k].text.data(), tl, &tl, &nn)) || nn != n) return -1;
+			nm[k].len = tl;
+			if (!index_names(nm[k], n)) return -1;
+		}
+	}
+	for (int k = 0; k < n_files; ++k) {
+		const char *rows = reads.data() + ((uint64_t)k * n + first) * (size_t)L;
+		bool ok;
+		if (fastq) ok = write_records_named(paths[k], rows, q[k], named ? &nm[k] : nullptr, count, L, first);
+		else {
+			FILE *out = fopen(paths[k], "wb");
+			ok = out != nullptr;
+			for (uint64_t i = 0; i < count && ok; ++i) ok = fwrite(rows + i * (size_t)L, 1, (size_t)L, out) == (size_t)L && fputc('\n', out) != EOF;
+			if (out && fclose(out) != 0) ok = false;
+		}
+		if (!ok) { for (int j = 0; j <= k; ++j) remove(paths[j]); return -1; }
+	}
+	if (n_written) *n_written = count;
+	return 0;
+}
+
+int range_any(const char *folder, const char *out_path1, const char *out_path2, uint64_t first, uint64_t count, uint64_t *n_written, int device, bool pair, bool fastq)
+{
+	if (!folder || !out_path1 || (pair && !out_path2)) return -1;
+	if (const char *why = range_refusal(folder)) { fprintf(stderr, "minicom decoder: a range of %s is refused: %s\n", folder, why); return -1; }
+	try {
+		if (device < 0) return range_host(folder, out_path1, out_path2, first, count, n_written, pair, fastq);
+#ifdef MCOM_ENTROPY_HOST_ONLY
+		fprintf(stderr, "minicom decoder: this build has no GPU route\n");
+		return -1;
+#else
+		return mcom_range_gpu(folder, out_path1, out_path2, first, count, n_written, device, pair, fastq);
+#endif
+	} catch (...) { return -1; }   // no C++ exception crosses the C boundary
+}
+}  // namespace
+
+extern "C" int mcomh_decompress_order_range(const char *folder, const char *out_path, uint64_t first, uint64_t count, uint64_t *n_written, int device)
+{
+	return range_any(folder, out_path, nullptr, first, count, n_written, device, false, false);
+}
+extern "C" int mcomh_decompress_fastq_range(const char *folder, const char *out_path, uint64_t first, uint64_t count, uint64_t *n_written, int device)
+{
+	return range_any(folder, out_path, nullptr, first, count, n_written, device, false, true);
+}
+extern "C" int mcomh_decompress_order_pe_range(const char *folder, const char *out_path1, const char *out_path2, uint64_t first, uint64_t count, uint64_t *n_written, int device, int fastq)
+{
+	return range_any(folder, out_path1, out_path2, first, count, n_written, device, true, fastq != 0);
 }
 
 // ---- the agreement mask of a folder on the host (`minicom -a Q[:C]`): the default / -p decoder with its rows kept

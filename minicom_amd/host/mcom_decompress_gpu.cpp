@@ -7,6 +7,8 @@
 //      word the kernels raise are compared on the host.  An archive that fails here is refused before anything is decoded.
 //   B. one mcom_decode_reads per list / stream set writes its reads into a table of rows in HBM (L characters and a newline each:
 //      the file image); the table comes back through two page-locked buffers, the copy of piece i + 1 under the write of piece i.
+//   B'. a record range (`minicom -d -R`): A unchanged, then mcom_range_check_dest over every source -- the placement
+//      check of the full decode -- and mcom_range_decode_reads into a table of the window's rows alone: count x (L + 1) bytes, not n x (L + 1).
 //   C. what becomes of the rows is the caller's tail: the three decoders write the file(s) (write_files); mcomh_verify_gpu compares the table,
 //      still in HBM, with the reads of the FASTQ file(s) (compare_rows over csrc/verify.hip) and writes nothing.
 // The only serial step is the chain of contig headers in beg_pos.bin (mcom_decode_walk_headers: four bytes read per contig).
@@ -16,6 +18,7 @@
 #include "mcom_fastq.hpp"
 #include "mcom_ragged.hpp"
 #include "mcom_agree.hpp"
+#include "mcom_range.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -157,7 +160,13 @@ using Tail = std::function<int(Arena &A, const uint8_t *table, uint64_t n_rows, 
 // an archive that has passed every check of A and B.  It throws Refuse like everything inside run().
 using Between = std::function<void(Arena &A, const std::vector<Seg> &segs, uint64_t n_rows, int L, uint32_t *d_flag)>;
 
-int run(Mode mode, const char *folder, int device, const Tail &tail, const Between *between = nullptr)
+// a record range: run() decodes the rows [first, first + count) alone -- pair: and [half + first, half + first + count), the same records of
+// the second file of a pair kept in input order, behind them -- and hands the tail that table.  It clips count at the last record and
+// states n_records, the records (of one file) in the archive, for the tails that set the side members against it.
+struct Window { uint64_t first, count; bool pair; uint64_t n_records = 0; };
+uint64_t pair_count(const char *folder, uint64_t n_rows);
+
+int run(Mode mode, const char *folder, int device, const Tail &tail, const Between *between = nullptr, Window *win = nullptr)
 {
 	const double t_begin = now_ms();
 	memset(g_times, 0, sizeof(g_times));
@@ -348,11 +357,23 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 		if (mode == DEFAULT) { uint64_t at = 0; for (Seg &s : segs) { s.dest0 = at; at += s.n; } }
 		// everything the files say about sizes has been checked: a raised flag refuses the archive before a read is decoded
 		if (read_flag(A, d_flag)) throw Refuse{"the stream files are inconsistent"};
-		const uint64_t row = (uint64_t)L + 1, table_bytes = n_rows * row;
+		// a range: the window's rows alone are made, so they alone must fit (the stream files and the tables above stay whole)
+		uint64_t table_rows = n_rows;
+		if (win) {
+			if (mode != ORDER) throw Refuse{"a range needs the input order of a -p archive"};
+			win->n_records = win->pair ? pair_count(folder, n_rows) : n_rows;
+			if (win->first > win->n_records) {
+				fprintf(stderr, "minicom gpu decoder: the range begins at record %llu (from 0), the archive holds %llu\n", (unsigned long long)win->first, (unsigned long long)win->n_records);
+				throw Refuse{"the range begins behind the last record"};
+			}
+			if (win->count > win->n_records - win->first) win->count = win->n_records - win->first;
+			table_rows = (win->pair ? 2 : 1) * win->count;
+		}
+		const uint64_t row = (uint64_t)L + 1, table_bytes = table_rows * row;
 		{
 			size_t fr = 0, tot = 0;
 			if (hipMemGetInfo(&fr, &tot) != hipSuccess || table_bytes + n_rows / 8 + ((size_t)64 << 20) > fr) {
-				fprintf(stderr, "minicom gpu decoder: %llu rows of %d + 1 bytes do not fit the card (%zu bytes free)\n", (unsigned long long)n_rows, L, fr);
+				fprintf(stderr, "minicom gpu decoder: %llu rows of %d + 1 bytes do not fit the card (%zu bytes free)\n", (unsigned long long)table_rows, L, fr);
 				throw Refuse{"the rows do not fit the card"};
 			}
 		}
@@ -368,7 +389,14 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 		if (hipEventCreate(&A.ev[0]) != hipSuccess || hipEventCreate(&A.ev[1]) != hipSuccess) throw Refuse{"no events"};
 		t0 = now_ms();
 		(void)hipEventRecord(A.ev[0], nullptr);
-		for (const Seg &s : segs) ok(A.ctx, mcom_decode_reads(A.ctx, &s.src, s.n, L, s.d_dest, s.dest0, table, n_rows, seen, d_flag));
+		if (win) {
+			// as many reads as rows (A.3): no destination outside and none twice means every row, of any window, exactly once
+			for (const Seg &s : segs) ok(A.ctx, mcom_range_check_dest(A.ctx, s.d_dest, s.dest0, s.n, n_rows, seen, d_flag));
+			for (int w = 0; w < (win->pair ? 2 : 1); ++w)
+				for (const Seg &s : segs) ok(A.ctx, mcom_range_decode_reads(A.ctx, &s.src, s.n, L, s.d_dest, s.dest0, (uint64_t)w * win->n_records + win->first, win->count, table + (uint64_t)w * win->count * row, d_flag));
+		} else {
+			for (const Seg &s : segs) ok(A.ctx, mcom_decode_reads(A.ctx, &s.src, s.n, L, s.d_dest, s.dest0, table, n_rows, seen, d_flag));
+		}
 		(void)hipEventRecord(A.ev[1], nullptr);
 		const uint32_t fl = read_flag(A, d_flag);
 		{ float ms = 0; if (hipEventElapsedTime(&ms, A.ev[0], A.ev[1]) == hipSuccess) g_times[3] = ms; }
@@ -377,7 +405,7 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 		if (between) (*between)(A, segs, n_rows, L, d_flag);
 
 		// ---- C. what becomes of the rows: the file(s), or the comparison of mcomh_verify_gpu
-		if (tail(A, table, n_rows, (uint64_t)half, L)) return -1;
+		if (tail(A, table, table_rows, win ? win->count : (uint64_t)half, L)) return -1;
 	} catch (const Refuse &r) {
 		fprintf(stderr, "minicom gpu decoder: %s refused: %s\n", folder, r.why);
 		return -1;
@@ -474,7 +502,8 @@ int guarded(Mode mode, const char *folder, const char *o1, const char *o2, uint6
 // command-line flag that makes such a member ("-Q" for qual.mcq, "-q" for rqual*.mcq): the refusals name the member and the flag
 std::string g_why;                                      // the text of a refusal made of a member's name (Refuse carries a pointer)
 [[noreturn]] void refuse_member(const std::string &why) { g_why = why; throw Refuse{g_why.c_str()}; }
-uint8_t *load_quals(Arena &A, const char *folder, const char *member_name, const char *flag, uint64_t n_rows, int L, uint64_t pitch)
+// rng: the rows [rng->first, rng->first + rng->count) alone, to rows 0 .. (mcom_qual_decode_rows: the touched segments, no CRC of the whole)
+uint8_t *load_quals(Arena &A, const char *folder, const char *member_name, const char *flag, uint64_t n_rows, int L, uint64_t pitch, const Window *rng = nullptr)
 {
 	const std::string name(member_name);
 	std::vector<uint8_t> member;
@@ -482,8 +511,8 @@ uint8_t *load_quals(Arena &A, const char *folder, const char *member_name, const
 	uint64_t qn = 0; uint32_t qL = 0;
 	if (mcom_qual_info(member.data(), member.size(), &qn, &qL) || qn != n_rows || (int)qL != L) refuse_member(name + " does not state the reads' number and length");
 	const uint8_t *d_member = A.upload(member.data(), member.size());
-	uint8_t *quals = A.alloc<uint8_t>(n_rows * pitch);
-	if (mcom_qual_decode(A.ctx, d_member, member.size(), quals, pitch, n_rows, &qn, &qL)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); refuse_member(name + " is refused"); }
+	uint8_t *quals = A.alloc<uint8_t>((rng ? rng->count : n_rows) * pitch);
+	if (rng ? mcom_qual_decode_rows(A.ctx, d_member, member.size(), rng->first, rng->count, quals, pitch, &qn, &qL) : mcom_qual_decode(A.ctx, d_member, member.size(), quals, pitch, n_rows, &qn, &qL)) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); refuse_member(name + " is refused"); }
 	return quals;
 }
 
@@ -495,10 +524,13 @@ struct NamesReady { const uint8_t *d_names; const uint64_t *d_off; uint64_t byte
 
 // quals_ready: the quality rows (pitch L) when the caller has decoded them already (the `minicom -q` tails: no names there, unless the
 // caller hands them in as names_ready)
+// rng (a record range, section 3.19): table and quality rows hold the n_rows = rng->count records from rng->first on; the side members
+// state rng->n_records, the names are those of the whole archive and the records are numbered and named from `base` = rng->first
 int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_rows, int L, const char *out_path, uint64_t *n_out, const uint8_t *quals_ready = nullptr, EmitBufs *shared = nullptr,
-                const NamesReady *names_ready = nullptr)
+                const NamesReady *names_ready = nullptr, const Window *rng = nullptr)
 {
-	const uint8_t *quals = quals_ready ? quals_ready : load_quals(A, folder, "qual.mcq", "-Q", n_rows, L, (uint64_t)L);
+	const uint64_t base = rng ? rng->first : 0, n_all = rng ? rng->n_records : n_rows;
+	const uint8_t *quals = quals_ready ? quals_ready : load_quals(A, folder, "qual.mcq", "-Q", n_all, L, (uint64_t)L, rng);
 	// folder/name.mcn (`minicom -N`, section 3.10): decoded on the device too; the records then carry its names and '+' texts
 	std::vector<uint8_t> nmember;
 	const bool own_names = !quals_ready && !names_ready && slurp(std::string(folder) + "/name.mcn", nmember), named = own_names || names_ready;
@@ -507,13 +539,13 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	if (names_ready) { d_names = names_ready->d_names; d_off = names_ready->d_off; names_bytes = names_ready->bytes; }
 	if (own_names) {
 		uint64_t nn = 0;
-		if (mcom_name_info(nmember.data(), nmember.size(), &nn, &names_bytes) || nn != n_rows) throw Refuse{"name.mcn does not state the reads' number"};
+		if (mcom_name_info(nmember.data(), nmember.size(), &nn, &names_bytes) || nn != n_all) throw Refuse{"name.mcn does not state the reads' number"};
 		const uint8_t *d_nm = A.upload(nmember.data(), nmember.size());
-		uint8_t *dn = A.alloc<uint8_t>(names_bytes); uint64_t *dof = A.alloc<uint64_t>(n_rows + 1);
-		if (mcom_name_decode(A.ctx, d_nm, nmember.size(), dn, names_bytes, &names_bytes, &nn, dof) || nn != n_rows) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"name.mcn is refused"}; }
+		uint8_t *dn = A.alloc<uint8_t>(names_bytes); uint64_t *dof = A.alloc<uint64_t>(n_all + 1);
+		if (mcom_name_decode(A.ctx, d_nm, nmember.size(), dn, names_bytes, &names_bytes, &nn, dof) || nn != n_all) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"name.mcn is refused"}; }
 		d_names = dn; d_off = dof;
-		off_own.resize(n_rows + 1);
-		if (hipMemcpy(off_own.data(), d_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+		off_own.resize(n_all + 1);
+		if (hipMemcpy(off_own.data(), d_off, (n_all + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
 	}
 	const std::vector<uint64_t> &off = names_ready ? *names_ready->off : off_own;
 	const double t0 = now_ms();
@@ -527,7 +559,7 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 		uint64_t end = first + per_piece < n_rows ? first + per_piece : n_rows;
 		if (named) {
 			uint64_t lo = first + 1, hi = n_rows;                              // (one record always fits: at most 2 L + 4 + 512 bytes)
-			while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if ((2 * (uint64_t)L + 4) * (mid - first) + off[mid] - off[first] <= PIECE_BYTES) lo = mid; else hi = mid - 1; }
+			while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if ((2 * (uint64_t)L + 4) * (mid - first) + off[base + mid] - off[base + first] <= PIECE_BYTES) lo = mid; else hi = mid - 1; }
 			end = lo;
 		}
 		piece_at.push_back(end);
@@ -553,9 +585,9 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 		GzSink &Z = *sink;
 		for (uint64_t i = 0; i < pieces && wrote_ok; ++i) {
 			const uint64_t first = piece_at[i], count = piece_at[i + 1] - first;
-			const int rc = named ? mcom_fastq_emit_named(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, d_names, names_bytes, d_off + first, count,
+			const int rc = named ? mcom_fastq_emit_named(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, d_names, names_bytes, d_off + base + first, count,
 			                                             (uint32_t)L, d_out[0], &bytes[0])
-			                     : mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, first, count, (uint32_t)L, d_out[0], &bytes[0]);
+			                     : mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, base + first, count, (uint32_t)L, d_out[0], &bytes[0]);
 			wrote_ok = !rc && bytes[0] <= PIECE_BYTES && Z.feed(d_out[0], (size_t)bytes[0], i + 1 == pieces, out);
 		}
 		if (!pieces && wrote_ok) wrote_ok = Z.feed(nullptr, 0, true, out);
@@ -568,9 +600,9 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	for (uint64_t i = 0; i <= pieces && wrote_ok; ++i) {
 		if (i < pieces) {
 			const uint64_t first = piece_at[i], count = piece_at[i + 1] - first;
-			const int rc = named ? mcom_fastq_emit_named(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, d_names, names_bytes, d_off + first, count,
+			const int rc = named ? mcom_fastq_emit_named(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, d_names, names_bytes, d_off + base + first, count,
 			                                             (uint32_t)L, d_out[i & 1], &bytes[i & 1])
-			                     : mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, first, count, (uint32_t)L, d_out[i & 1], &bytes[i & 1]);
+			                     : mcom_fastq_emit(A.ctx, table + first * ((uint64_t)L + 1), (uint64_t)L + 1, quals + first * (uint64_t)L, (uint64_t)L, base + first, count, (uint32_t)L, d_out[i & 1], &bytes[i & 1]);
 			if (rc ||
 			    bytes[i & 1] > PIECE_BYTES) { wrote_ok = false; break; }       // (synchronous on the context's stream: d_out[i & 1] is complete)
 			if (hipMemcpyAsync(pin[i & 1], d_out[i & 1], bytes[i & 1], hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
@@ -1019,6 +1051,30 @@ extern "C" int mcomh_decompress_fastq_order_pe_gpu(const char *folder, const cha
 		});
 	} catch (...) { return -1; }
 }
+// ---- a record range of a -p archive (`minicom -d -R`; the host twin and the refusals that need no decoding:
+// mcom_decompress.cpp).  run() makes the window's rows; the tails are the plain file(s), the FASTQ emit in pieces and the BGZF sink of
+// `.gz` paths over them, with `first` carried into the names.  Every side member is decoded before a file is opened.
+int mcom_range_gpu(const char *folder, const char *o1, const char *o2, uint64_t first, uint64_t count, uint64_t *n_written, int device, bool pair, bool fastq)
+{
+	try {
+		Window W{first, count, pair};
+		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
+			const uint64_t cnt = W.count, row = (uint64_t)L + 1;                   // (clipped by run(); n_rows = cnt, or 2 cnt for a pair)
+			if (!fastq) return write_files(pair ? PE : ORDER, A, table, n_rows, cnt, L, o1, o2, n_written);
+			if (!pair) return write_fastq(A, folder, table, cnt, L, o1, n_written, nullptr, nullptr, nullptr, &W);
+			const uint8_t *q1 = load_quals(A, folder, "qual_1.mcq", "-Q", W.n_records, L, (uint64_t)L, &W), *q2 = load_quals(A, folder, "qual_2.mcq", "-Q", W.n_records, L, (uint64_t)L, &W);
+			PairNames P;
+			const bool named = load_pair_names(A, folder, W.n_records, P);
+			EmitBufs bufs;
+			if (write_fastq(A, folder, table, cnt, L, o1, n_written, q1, &bufs, named ? &P.r[0] : nullptr, &W)) return -1;
+			int rc = -1;
+			try { rc = write_fastq(A, folder, table + cnt * row, cnt, L, o2, n_written, q2, &bufs, named ? &P.r[1] : nullptr, &W); } catch (...) { remove(o1); throw; }
+			if (rc) remove(o1);
+			return rc;
+		}, nullptr, &W);
+	} catch (...) { return -1; }   // no C++ exception crosses the C boundary
+}
+
 // the reads of such an archive against the two FASTQ files, line against line over both files: the report's mode is 1
 extern "C" int mcomh_verify_order_pe_reads_gpu(const char *folder, const char *fastq1, const char *fastq2, int device, mcomh_verify_report *rep)
 {

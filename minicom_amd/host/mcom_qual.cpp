@@ -108,6 +108,34 @@ int encode(const uint8_t *rows, uint64_t n_rows, uint32_t L, uint64_t pitch, uin
 	return 0;
 }
 
+// One segment of the coded form: its run of rl bytes at p, n rows to dst, `pitch` apart.  false: the run is shorter than a state, the
+// state leaves [2^23, 2^31), a slot no symbol owns, a symbol >= A, the run read beyond its end or not used up exactly.
+bool decode_segment(const QHeader &hd, const Geometry &g, const std::vector<uint16_t> &cum, const uint8_t *p, uint32_t rl, uint64_t n, uint8_t *dst, uint64_t pitch)
+{
+	const uint32_t A = g.A, L = hd.L;
+	const uint8_t *const end = p + rl;
+	if (rl < 4) return false;
+	uint32_t x = get_u32(p); p += 4;
+	if (x < STATE_L || x >= (1u << 31)) return false;
+	for (uint64_t r = 0; r < n; ++r) {
+		uint8_t *d = dst + r * pitch;
+		uint32_t p1 = 0, p2 = 0, p3 = 0;
+		for (uint32_t j = 0; j < L; ++j) {
+			const uint16_t *row = &cum[(size_t)g.ctx(hd.model, p1, p2, p3, j) * (A + 1)];
+			const uint32_t slot = x & (PROB_M - 1);
+			uint32_t sym = 0, st = 128;
+			for (; st; st >>= 1) if (sym + st < A && row[sym + st] <= slot) sym += st;
+			const uint32_t c = row[sym], f = row[sym + 1] - c;
+			if (sym >= A || slot - c >= f) return false;
+			x = f * (x >> PROB_BITS) + slot - c;
+			while (x < STATE_L) { if (p >= end) return false; x = (x << 8) | *p++; }
+			d[j] = g.value[sym];
+			p3 = p2; p2 = p1; p1 = sym;
+		}
+	}
+	return p == end && x == STATE_L;
+}
+
 // Accepts exactly what mcom_qual_decode accepts (section 3.9, "Untrusted input").
 int decode(const uint8_t *in, uint64_t in_len, uint8_t *rows, uint64_t pitch, uint64_t cap_rows, uint64_t *n_rows, uint32_t *L_out)
 {
@@ -134,7 +162,6 @@ int decode(const uint8_t *in, uint64_t in_len, uint8_t *rows, uint64_t pitch, ui
 		return 0;
 	}
 	Geometry g; g.set(hd.map, L);
-	const uint32_t A = g.A;
 	std::vector<uint16_t> cum;
 	if (!parse_tables(in + QHEADER_BYTES, hd.table_bytes, g, hd.model, cum)) return refuse();
 	const uint64_t n_seg = hd.n_seg();
@@ -146,32 +173,58 @@ int decode(const uint8_t *in, uint64_t in_len, uint8_t *rows, uint64_t pitch, ui
 	uint32_t crc = 0;
 	for (uint64_t seg = 0; seg < n_seg; ++seg) {
 		const uint32_t rl = get_u16(lens + 2 * seg);
-		const uint8_t *p = runs + at_run, *const end = p + rl;
-		at_run += rl;
-		if (rl < 4) return refuse();
-		uint32_t x = get_u32(p); p += 4;
-		if (x < STATE_L || x >= (1u << 31)) return refuse();
 		const uint64_t r0 = seg * hd.rps, r1 = r0 + hd.rps < hd.n_rows ? r0 + hd.rps : hd.n_rows;
-		for (uint64_t r = r0; r < r1; ++r) {
-			uint8_t *d = rows + r * pitch;
-			uint32_t p1 = 0, p2 = 0, p3 = 0;
-			for (uint32_t j = 0; j < L; ++j) {
-				const uint16_t *row = &cum[(size_t)g.ctx(hd.model, p1, p2, p3, j) * (A + 1)];
-				const uint32_t slot = x & (PROB_M - 1);
-				uint32_t sym = 0, st = 128;
-				for (; st; st >>= 1) if (sym + st < A && row[sym + st] <= slot) sym += st;
-				const uint32_t c = row[sym], f = row[sym + 1] - c;
-				if (sym >= A || slot - c >= f) return refuse();
-				x = f * (x >> PROB_BITS) + slot - c;
-				while (x < STATE_L) { if (p >= end) return refuse(); x = (x << 8) | *p++; }
-				d[j] = g.value[sym];
-				p3 = p2; p2 = p1; p1 = sym;
-			}
-			crc = mcom_crc32(crc, d, L);
-		}
-		if (p != end || x != STATE_L) return refuse();
+		if (!decode_segment(hd, g, cum, runs + at_run, rl, r1 - r0, rows + r0 * pitch, pitch)) return refuse();
+		at_run += rl;
+		for (uint64_t r = r0; r < r1; ++r) crc = mcom_crc32(crc, rows + r * pitch, L);
 	}
 	if (crc != hd.crc) return refuse();
+	return 0;
+}
+
+// Rows first_row .. first_row + count - 1 alone: accepts exactly what mcom_qual_decode_rows accepts.  The CRC-32
+// covers all rows and is not checked for a part; a range that is the whole member is decode(), CRC included.
+int decode_rows(const uint8_t *in, uint64_t in_len, uint64_t first_row, uint64_t count, uint8_t *rows, uint64_t pitch, uint64_t *n_rows, uint32_t *L_out)
+{
+	if (!n_rows || !L_out || (in_len && !in)) return -1;
+	*n_rows = 0; *L_out = 0;
+	QHeader hd;
+	if (!in || !read_qheader(in, in_len, hd)) return -1;
+	if (first_row > hd.n_rows) return -1;
+	if (count > hd.n_rows - first_row) count = hd.n_rows - first_row;
+	if (first_row == 0 && count == hd.n_rows) return decode(in, in_len, rows, pitch, hd.n_rows, n_rows, L_out);
+	if (pitch < hd.L || (count && !rows)) return -1;
+	const uint32_t L = hd.L;
+	const uint64_t raw = hd.raw_len();
+	if (hd.kind == KIND_RANS) {                                          // no segments of rows: the whole matrix, then the slice
+		std::vector<uint8_t> flat(raw ? raw : 1);
+		uint64_t got = 0;
+		if (mcomh_rans_decode(in + QHEADER_BYTES, in_len - QHEADER_BYTES, flat.data(), raw, &got) || got != raw) return -1;
+		for (uint64_t r = 0; r < count; ++r) memcpy(rows + r * pitch, &flat[(first_row + r) * L], L);
+	} else if (hd.model == Q_STORED) {
+		for (uint64_t r = 0; r < count; ++r) memcpy(rows + r * pitch, in + QHEADER_BYTES + (first_row + r) * L, L);
+	} else {
+		Geometry g; g.set(hd.map, L);
+		std::vector<uint16_t> cum;
+		if (!parse_tables(in + QHEADER_BYTES, hd.table_bytes, g, hd.model, cum)) return -1;
+		const uint64_t n_seg = hd.n_seg();
+		const uint8_t *lens = in + QHEADER_BYTES + hd.table_bytes, *runs = lens + 2 * n_seg;
+		uint64_t sum = 0;
+		for (uint64_t s = 0; s < n_seg; ++s) sum += get_u16(lens + 2 * s);
+		if (sum != hd.payload_bytes) return -1;
+		const uint64_t seg0 = count ? first_row / hd.rps : 0, seg1 = count ? (first_row + count - 1) / hd.rps + 1 : 0;
+		uint64_t at_run = 0;
+		for (uint64_t s = 0; s < seg0; ++s) at_run += get_u16(lens + 2 * s);
+		std::vector<uint8_t> img((size_t)hd.rps * L);
+		for (uint64_t seg = seg0; seg < seg1; ++seg) {
+			const uint32_t rl = get_u16(lens + 2 * seg);
+			const uint64_t r0 = seg * hd.rps, r1 = r0 + hd.rps < hd.n_rows ? r0 + hd.rps : hd.n_rows;
+			if (!decode_segment(hd, g, cum, runs + at_run, rl, r1 - r0, img.data(), L)) return -1;
+			at_run += rl;
+			for (uint64_t r = r0 > first_row ? r0 : first_row; r < r1 && r < first_row + count; ++r) memcpy(rows + (r - first_row) * pitch, &img[(r - r0) * L], L);
+		}
+	}
+	*n_rows = hd.n_rows; *L_out = hd.L;
 	return 0;
 }
 
@@ -195,6 +248,11 @@ extern "C" int mcomh_qual_encode(const uint8_t *rows, uint64_t n_rows, uint32_t 
 extern "C" int mcomh_qual_decode(const uint8_t *in, uint64_t in_len, uint8_t *rows, uint64_t pitch, uint64_t cap_rows, uint64_t *n_rows, uint32_t *L)
 {
 	try { return decode(in, in_len, rows, pitch, cap_rows, n_rows, L); } catch (const std::bad_alloc &) { if (n_rows) *n_rows = 0; if (L) *L = 0; return -1; }
+}
+
+extern "C" int mcomh_qual_decode_rows(const uint8_t *in, uint64_t in_len, uint64_t first_row, uint64_t count, uint8_t *rows, uint64_t pitch, uint64_t *n_rows, uint32_t *L)
+{
+	try { return decode_rows(in, in_len, first_row, count, rows, pitch, n_rows, L); } catch (const std::bad_alloc &) { if (n_rows) *n_rows = 0; if (L) *L = 0; return -1; }
 }
 
 extern "C" int mcomh_qual_estimate(const uint8_t *rows, uint64_t n_rows, uint32_t L, uint64_t pitch, uint64_t est5[5])

@@ -188,6 +188,10 @@ def load_host_library():
     L.mcomh_digest_print.restype = i32; L.mcomh_digest_print.argtypes = [C.POINTER(Digest), C.c_char_p, sz, C.POINTER(sz)]
     L.mcomh_digest_parse.restype = i32; L.mcomh_digest_parse.argtypes = [C.c_char_p, sz, C.POINTER(Digest), C.c_char_p, sz]
     L.mcomh_digest_check.restype = i32; L.mcomh_digest_check.argtypes = [cp, cp, cp, i32, C.POINTER(DigestReport)]
+    for f in ("mcomh_decompress_order_range", "mcomh_decompress_fastq_range"):
+        getattr(L, f).restype = i32; getattr(L, f).argtypes = [cp, cp, u64, u64, C.POINTER(u64), i32]
+    L.mcomh_decompress_order_pe_range.restype = i32; L.mcomh_decompress_order_pe_range.argtypes = [cp, cp, cp, u64, u64, C.POINTER(u64), i32, i32]
+    L.mcomh_qual_decode_rows.restype = i32; L.mcomh_qual_decode_rows.argtypes = [vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u32)]
     _lib = L
     return L
 
@@ -237,6 +241,8 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_fastq_emit_ragged", "mcomh_verify_ragged_gpu",
                     # self-checking archives (`minicom -K`, host/mcom_digest.cpp)
                     "mcomh_fastq_record_hashes", "mcomh_digest_reduce", "mcomh_fastq_digest_files", "mcomh_digest_print", "mcomh_digest_parse", "mcomh_digest_check",
+                    # a record range of a -p archive (`minicom -d -R`)
+                    "mcomh_decompress_order_range", "mcomh_decompress_fastq_range", "mcomh_decompress_order_pe_range", "mcomh_qual_decode_rows",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -255,6 +261,28 @@ def decompress(folder: str, out_path: str, order: bool = False, device: int | No
         rc = (lib.mcomh_decompress_order_gpu if order else lib.mcomh_decompress_gpu)(folder.encode(), out_path.encode(), C.byref(n), int(device))
     if rc:
         raise McomError(f"cannot decode the stream files in {folder}" + ("" if device is None else f" on GPU {device}"))
+    return int(n.value)
+
+
+def decompress_range(folder: str, out_path: str, first: int, count: int, device: int | None = None, fastq: bool = False, out_path2: str | None = None) -> int:
+    """mcomh_decompress_order_range / _fastq_range / _order_pe_range: records first .. first + count - 1 (first
+    from 0, the range clipped at the archive's end) of a -p archive, and nothing else: one read per line, with fastq=True four-line
+    records; with out_path2 the same range of both files of a pair kept in input order.  Ranges that tile the archive concatenate to the
+    full decode.  device=None: the host twin (the whole table in memory, then the slice); an integer: on that GPU, where only the window's
+    rows are made.  Returns the number of records written.  McomError, and no file, for first > n and for a folder that is not a -p
+    archive, or is one made with -q or -V."""
+    if first < 0 or count < 0 or first >= 2 ** 64 or count >= 2 ** 64:
+        raise McomError(f"decompress_range: records {first} .. + {count}")
+    n = C.c_uint64()
+    lib = load_host_library()
+    dev = -1 if device is None else int(device)
+    if out_path2 is not None:
+        rc = lib.mcomh_decompress_order_pe_range(os.fsencode(folder), os.fsencode(out_path), os.fsencode(out_path2), int(first), int(count), C.byref(n), dev, 1 if fastq else 0)
+    else:
+        rc = (lib.mcomh_decompress_fastq_range if fastq else lib.mcomh_decompress_order_range)(os.fsencode(folder), os.fsencode(out_path), int(first), int(count), C.byref(n), dev)
+    if rc:
+        raise McomError(f"cannot decode records {first} .. + {count} of {folder}" + ("" if device is None else f" on GPU {device}") +
+                        ": the range begins behind the last record, or the folder is not a complete, consistent -p archive (archives made with -q or -V are refused)")
     return int(n.value)
 
 
@@ -912,6 +940,35 @@ def qual_decode(member: bytes, pitch: int | None = None):
     if rc:
         raise McomError(f"qual_decode: error {rc}: not a complete, intact .mcq member")
     return buf[:n * pitch].reshape(n, pitch)[:, :L]
+
+
+def qual_decode_rows(member: bytes, first: int, count: int, pitch: int | None = None, device: int | None = None):
+    """Rows first .. first + count - 1 of a `.mcq` member (count clipped at the member's end) as a uint8 matrix [count, L] (DESIGN.md
+    section 3.19): only the segments that hold them are decoded, and the member's CRC-32, which covers all rows, is NOT checked unless
+    the range is the whole member.  device=None: mcomh_qual_decode_rows on the host; an integer: mcom_qual_decode_rows on that GPU (an
+    error, never the host twin, when there is none).  McomError for a member whose header, tables, run lengths or touched segments are
+    refused, and for first > n."""
+    import numpy as np
+    member = bytes(member)
+    n, L = qual_info(member)
+    first, count = int(first), int(count)
+    if first < 0 or count < 0 or first > n:
+        raise McomError("qual_decode_rows: rows %d .. + %d of %d" % (first, count, n))
+    count = min(count, n - first)
+    pitch = L if pitch is None else int(pitch)
+    if pitch < L or count * pitch > 1 << 40:
+        raise McomError("qual_decode_rows: %d rows of %d bytes at pitch %d" % (count, L, pitch))
+    if device is not None:
+        import torch
+        from .hip import Context
+        d_member = torch.from_numpy(np.frombuffer(member, dtype=np.uint8).copy()).to(f"cuda:{int(device)}")
+        return Context(int(device)).qual_decode_rows(d_member, first, count, pitch=pitch).cpu().numpy()
+    buf = np.zeros(max(count * pitch, 1), dtype=np.uint8)
+    gn, gL = C.c_uint64(), C.c_uint32()
+    rc = load_host_library().mcomh_qual_decode_rows((C.c_char * len(member)).from_buffer_copy(member), len(member), first, count, buf.ctypes.data, pitch, C.byref(gn), C.byref(gL))
+    if rc:
+        raise McomError(f"qual_decode_rows: error {rc}: a refused .mcq member")
+    return buf[:count * pitch].reshape(count, pitch)[:, :L]
 
 
 def qual_estimate(rows) -> list[int]:
