@@ -19,6 +19,7 @@
 #include "mcom_ragged.hpp"
 #include "mcom_agree.hpp"
 #include "mcom_range.hpp"
+#include "mcom_streams.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -30,27 +31,16 @@
 #include <string>
 #include <vector>
 
+using namespace mcom_streams;                         // Mode, what a folder of each mode holds and its loaders: shared with the host decoder
+
 namespace {
 
-enum Mode { DEFAULT = 0, ORDER = 1, PE = 2 };
 size_t PIECE_BYTES = (size_t)64 << 20;                // one page-locked buffer; two of them bound the host memory of the download
                                                         // (mcomh_test_decoder_piece_bytes, include/mcom_test.h, lets a test cross pieces with a few thousand records)
 
 double g_times[8];                                      // ms: read files | upload + indices + destinations | decode, wall | decode, device events |
                                                         //     download + write, wall | of that inside fwrite | whole call | unused
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-bool slurp(const std::string &path, std::vector<uint8_t> &out)
-{
-	FILE *f = fopen(path.c_str(), "rb");
-	if (!f) return false;
-	fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-	if (n < 0) { fclose(f); return false; }
-	out.resize((size_t)n);
-	size_t got = n ? fread(out.data(), 1, (size_t)n, f) : 0;
-	fclose(f);
-	return got == (size_t)n;
-}
 
 struct Refuse { const char *why; };                     // thrown inside run(), caught there: never crosses the C boundary
 
@@ -164,62 +154,38 @@ using Between = std::function<void(Arena &A, const std::vector<Seg> &segs, uint6
 // the second file of a pair kept in input order, behind them -- and hands the tail that table.  It clips count at the last record and
 // states n_records, the records (of one file) in the archive, for the tails that set the side members against it.
 struct Window { uint64_t first, count; bool pair; uint64_t n_records = 0; };
-uint64_t pair_count(const char *folder, uint64_t n_rows);
+// folder/pe_order.txt of a pair kept in input order: the pairs it states, which must be half of n_rows
+uint64_t pairs_of(const char *folder, uint64_t n_rows)
+{
+	uint64_t n_pairs = 0;
+	if (!pair_count(folder, n_rows, n_pairs)) throw Refuse{"no pe_order.txt that states half the reads' number: not a pair kept in input order"};
+	return n_pairs;
+}
 
 int run(Mode mode, const char *folder, int device, const Tail &tail, const Between *between = nullptr, Window *win = nullptr)
 {
 	const double t_begin = now_ms();
 	memset(g_times, 0, sizeof(g_times));
 	const std::string dir(folder);
-	// ---- info.txt, as the host routes read it
-	int L = 0, nth = 0; long na = 0, nt = 0, nn = 0, half = 0; unsigned long n_seq = 0;
-	{
-		FILE *fi = fopen((dir + "/info.txt").c_str(), "r");
-		if (!fi) return -1;
-		int got, want;
-		if (mode == DEFAULT) { want = 5; got = fscanf(fi, "%d %d %ld %ld %ld", &L, &nth, &na, &nt, &nn); }
-		else if (mode == ORDER) { want = 6; got = fscanf(fi, "%d %d %ld %ld %ld %lu", &L, &nth, &na, &nt, &nn, &n_seq); }
-		else { want = 6; got = fscanf(fi, "%d %d %ld %ld %ld %ld", &L, &nth, &half, &na, &nt, &nn); }
-		fclose(fi);
-		if (got != want) return -1;
-	}
-	if (L < 1 || L > 256 || nth < 1 || nth > 4096 || na < 0 || nt < 0 || nn < 0 || half < 0) return -1;
+	// ---- info.txt and the first size checks, by the host routes' own code (mcom_streams.hpp)
+	StreamInfo I;
+	if (!read_info(mode, dir, I) || !counts_fit(mode, dir, I)) return -1;
+	const int L = I.L, nth = I.nth;
+	const long na = I.na, nt = I.nt, nn = I.nn, half = I.half;
+	const unsigned long n_seq = I.n_seq;
 
 	// ---- the stream files, whole
 	double t0 = now_ms();
-	const char *list_txt[3] = {"AA.txt", "TT.txt", "NN.txt"};
-	const char *cnt_ids[3] = {"allA.ids.bin", "allT.ids.bin", "allN.ids.bin"}, *list_ids[3] = {"AA.ids.bin", "TT.ids.bin", "NN.ids.bin"};
-	std::vector<uint8_t> h_txt[3], h_cnt_ids[3], h_list_ids[3], h_nseq, h_nids, h_single, h_sids, h_fsp, h_psp;
-	struct SetFiles { std::vector<uint8_t> ref, pos, dir, dif, ids, fb, pe; };
+	SectionFiles lists[N_SECTIONS];
+	SetFiles sp;                                                            // paired end: the sections' file bits and mate numbers
 	std::vector<SetFiles> sets((size_t)nth);
-	for (int q = 0; q < 3; ++q) {
-		if (!slurp(dir + "/" + list_txt[q], h_txt[q])) return -1;
-		if (mode == ORDER && (!slurp(dir + "/" + cnt_ids[q], h_cnt_ids[q]) || !slurp(dir + "/" + list_ids[q], h_list_ids[q]))) return -1;
-	}
-	if (!slurp(dir + "/single_N.seq", h_nseq) || !slurp(dir + "/single.seq", h_single)) return -1;
-	if (mode == ORDER && (!slurp(dir + "/Nfile.ids.bin", h_nids) || !slurp(dir + "/singleFile.ids.bin", h_sids))) return -1;
-	if (mode == PE && (!slurp(dir + "/file.bin.sp", h_fsp) || !slurp(dir + "/peids.bin.sp", h_psp))) return -1;
-	for (int th = 0; th < nth; ++th) {
-		SetFiles &s = sets[(size_t)th];
-		const std::string sfx = "." + std::to_string(th);
-		if (!slurp(dir + "/ref.bin" + sfx, s.ref) || !slurp(dir + "/beg_pos.bin" + sfx, s.pos) || !slurp(dir + "/dir.bin" + sfx, s.dir) ||
-		    !slurp(dir + "/dif_char.txt" + sfx, s.dif)) return -1;
-		if (mode == ORDER && !slurp(dir + "/ids.bin" + sfx, s.ids)) return -1;
-		if (mode == PE && (!slurp(dir + "/file.bin" + sfx, s.fb) || !slurp(dir + "/peids.bin" + sfx, s.pe))) return -1;
-	}
+	for (int s = 0; s < N_SECTIONS; ++s) if (!load_section(mode, dir, s, lists[s])) return -1;
+	if (mode == PE && !load_pairing(dir, ".sp", sp)) return -1;
+	for (int th = 0; th < nth; ++th) if (!load_set(mode, dir, th, sets[(size_t)th])) return -1;
 	g_times[0] = now_ms() - t0;
-	// the host routes' first size checks
-	if (mode == ORDER) {
-		size_t idb = h_nids.size() + h_sids.size();
-		for (int q = 0; q < 3; ++q) idb += h_cnt_ids[q].size() + h_list_ids[q].size();
-		for (const SetFiles &s : sets) idb += s.ids.size();
-		if ((size_t)n_seq > idb / 4) return -1;
-	}
-	if (mode == PE) {
-		size_t fbb = h_fsp.size();
-		for (const SetFiles &s : sets) fbb += s.fb.size();
-		if ((size_t)half > fbb * 8) return -1;
-	}
+	// (the order of SECTIONS: three counted, three near-constant, the N reads, the unclustered reads)
+	const SectionFiles *h_counted = lists, *h_near = lists + 3;
+	const std::vector<uint8_t> &h_nseq = lists[6].data, &h_nids = lists[6].ids, &h_single = lists[7].data, &h_sids = lists[7].ids, &h_fsp = sp.fb, &h_psp = sp.pe;
 	// the serial part: the chain of contig headers
 	std::vector<std::vector<uint64_t>> moff((size_t)nth);
 	std::vector<uint64_t> n_contigs((size_t)nth), n_members((size_t)nth);
@@ -252,8 +218,8 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 		for (int q = 0; q < 3; ++q) {
 			Seg s = blank(); s.src.ref_const = bases[q]; s.n = (uint64_t)counted[q];
 			if (mode == ORDER) {
-				if (h_cnt_ids[q].size() / 4 < s.n) throw Refuse{"fewer ids than counted reads"};
-				const uint32_t *d = A.upload((const uint32_t*)h_cnt_ids[q].data(), (size_t)s.n);
+				if (h_counted[q].ids.size() / 4 < s.n) throw Refuse{"fewer ids than counted reads"};
+				const uint32_t *d = A.upload((const uint32_t*)h_counted[q].ids.data(), (size_t)s.n);
 				uint64_t *dest = A.alloc<uint64_t>(s.n);
 				ok(A.ctx, mcom_decode_list_ids(A.ctx, d, s.n, dest));
 				s.d_dest = dest;
@@ -275,7 +241,7 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 			}
 			segs.push_back(s);
 		};
-		for (int q = 0; q < 3; ++q) text_seg(h_txt[q], bases[q], 0, h_list_ids[q]);
+		for (int q = 0; q < 3; ++q) text_seg(h_near[q].data, bases[q], 0, h_near[q].ids);
 		auto single_seg = [&]() {
 			Seg s = blank();
 			s.n = (uint64_t)h_single.size() * 4 / (uint64_t)L;                 // whole reads only: the last byte may be padded
@@ -361,7 +327,7 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 		uint64_t table_rows = n_rows;
 		if (win) {
 			if (mode != ORDER) throw Refuse{"a range needs the input order of a -p archive"};
-			win->n_records = win->pair ? pair_count(folder, n_rows) : n_rows;
+			win->n_records = win->pair ? pairs_of(folder, n_rows) : n_rows;
 			if (win->first > win->n_records) {
 				fprintf(stderr, "minicom gpu decoder: the range begins at record %llu (from 0), the archive holds %llu\n", (unsigned long long)win->first, (unsigned long long)win->n_records);
 				throw Refuse{"the range begins behind the last record"};
@@ -621,6 +587,49 @@ int write_fastq(Arena &A, const char *folder, const uint8_t *table, uint64_t n_r
 	g_times[4] = now_ms() - t0;
 	if (n_out) *n_out = n_rows;
 	return 0;
+}
+
+// name_1.mcn and name_2.mcn decoded on the device, name_2 against the decoded name_1 text; false: the archive has neither
+struct PairNames { NamesReady r[2]; std::vector<uint64_t> off[2]; };
+bool load_pair_names(Arena &A, const char *folder, uint64_t half, PairNames &P)
+{
+	std::vector<uint8_t> m[2];
+	const bool has1 = slurp(std::string(folder) + "/name_1.mcn", m[0]), has2 = slurp(std::string(folder) + "/name_2.mcn", m[1]);
+	if (has1 != has2) throw Refuse{"one of name_1.mcn and name_2.mcn is missing: name_2 is coded against name_1"};
+	if (!has1) return false;
+	uint8_t *d_text[2]; uint64_t bytes[2] = {0, 0};
+	for (int k = 0; k < 2; ++k) {
+		uint64_t nn = 0;
+		if ((k ? mcom_name_info_mate(m[k].data(), m[k].size(), &nn, &bytes[k]) : mcom_name_info(m[k].data(), m[k].size(), &nn, &bytes[k])) || nn != half) throw Refuse{"a name member does not state the pairs' number"};
+		const uint8_t *d_nm = A.upload(m[k].data(), m[k].size());
+		d_text[k] = A.alloc<uint8_t>(bytes[k]);
+		uint64_t *d_off = A.alloc<uint64_t>(half + 1);
+		const int rc = k ? (mcom_name_decode_mate(A.ctx, d_nm, m[k].size(), d_text[0], bytes[0], d_text[1], bytes[1], &bytes[1], &nn) || mcom_name_text_offsets(A.ctx, d_text[1], bytes[1], half, d_off))
+		                 : mcom_name_decode(A.ctx, d_nm, m[k].size(), d_text[0], bytes[0], &bytes[0], &nn, d_off);
+		if (rc || nn != half) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"a name member is refused"}; }
+		P.off[k].resize(half + 1);
+		if (hipMemcpy(P.off[k].data(), d_off, (half + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+		P.r[k] = NamesReady{d_text[k], d_off, bytes[k], &P.off[k]};
+	}
+	return true;
+}
+
+// both files of a pair as FASTQ: the rows [0, half) of the table and the `half` behind them, the quality members qname1 / qname2 (made by
+// `flag`) and -- with_pair_names -- name_1.mcn / name_2.mcn.  Every member is decoded before a file is opened, both files travel through
+// the same two pieces, and neither is left when the second fails.  rng: as for write_fastq
+int write_fastq_pair(Arena &A, const char *folder, const uint8_t *table, uint64_t half, int L, const char *o1, const char *o2, uint64_t *n_out, const char *qname1, const char *qname2, const char *flag,
+                     bool with_pair_names, const Window *rng = nullptr)
+{
+	const uint64_t n_all = rng ? rng->n_records : half;
+	const uint8_t *q1 = load_quals(A, folder, qname1, flag, n_all, L, (uint64_t)L, rng), *q2 = load_quals(A, folder, qname2, flag, n_all, L, (uint64_t)L, rng);
+	PairNames P;
+	const bool named = with_pair_names && load_pair_names(A, folder, n_all, P);
+	EmitBufs bufs;
+	if (write_fastq(A, folder, table, half, L, o1, n_out, q1, &bufs, named ? &P.r[0] : nullptr, rng)) return -1;
+	int rc = -1;
+	try { rc = write_fastq(A, folder, table + half * ((uint64_t)L + 1), half, L, o2, n_out, q2, &bufs, named ? &P.r[1] : nullptr, rng); } catch (...) { remove(o1); throw; }
+	if (rc) remove(o1);
+	return rc;
 }
 
 // ---- a ragged archive (`minicom -p -V`): the fourth tail.  The table holds the n_even reads of the modal length;
@@ -958,11 +967,10 @@ extern "C" int mcomh_decompress_fastq_gpu(const char *folder, const char *out_pa
 }
 // ---- `minicom -q` archives: the default / paired-end decoder's rows, the quality rows of rqual*.mcq (stored in
 // the archive's own order) beside them, the records laid out as above.  What the host routes of mcom_decompress.cpp refuse is refused.
-static bool file_exists(const std::string &path) { FILE *f = fopen(path.c_str(), "rb"); if (!f) return false; fclose(f); return true; }
 extern "C" int mcomh_decompress_fastq_reordered_gpu(const char *folder, const char *out_path, uint64_t *n_reads, int device)
 {
 	if (!folder || !out_path) return -1;
-	if (file_exists(std::string(folder) + "/allA.ids.bin") || file_exists(std::string(folder) + "/file.bin.sp")) { fprintf(stderr, "minicom gpu decoder: %s is a -p or a paired-end archive\n", folder); return -1; }
+	if (exists(std::string(folder) + "/allA.ids.bin") || exists(std::string(folder) + "/file.bin.sp")) { fprintf(stderr, "minicom gpu decoder: %s is a -p or a paired-end archive\n", folder); return -1; }
 	try {
 		return run(DEFAULT, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
 			const uint8_t *q = load_quals(A, folder, "rqual.mcq", "-q", n_rows, L, (uint64_t)L);
@@ -973,62 +981,21 @@ extern "C" int mcomh_decompress_fastq_reordered_gpu(const char *folder, const ch
 extern "C" int mcomh_decompress_fastq_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device)
 {
 	if (!folder || !out_path1 || !out_path2) return -1;
-	if (file_exists(std::string(folder) + "/allA.ids.bin")) { fprintf(stderr, "minicom gpu decoder: %s is a -p archive\n", folder); return -1; }
+	if (exists(std::string(folder) + "/allA.ids.bin")) { fprintf(stderr, "minicom gpu decoder: %s is a -p archive\n", folder); return -1; }
 	try {
 		return run(PE, folder, device, [&](Arena &A, const uint8_t *table, uint64_t, uint64_t half, int L) {
-			const uint8_t *q1 = load_quals(A, folder, "rqual_1.mcq", "-q", half, L, (uint64_t)L), *q2 = load_quals(A, folder, "rqual_2.mcq", "-q", half, L, (uint64_t)L);   // (both before a file is opened)
-			EmitBufs bufs;                                                         // both files through the same two pieces
-			if (write_fastq(A, folder, table, half, L, out_path1, n_pairs, q1, &bufs)) return -1;
-			int rc = -1;
-			try { rc = write_fastq(A, folder, table + half * ((uint64_t)L + 1), half, L, out_path2, n_pairs, q2, &bufs); } catch (...) { remove(out_path1); throw; }
-			if (rc) remove(out_path1);
-			return rc;
+			return write_fastq_pair(A, folder, table, half, L, out_path1, out_path2, n_pairs, "rqual_1.mcq", "rqual_2.mcq", "-q", false);
 		});
 	} catch (...) { return -1; }
 }
 // ---- a pair kept in input order (`minicom -1 -2 -p [-Q [-N]]`): the -p decoder's 2 n rows, [0, n) the first file and
 // [n, 2 n) the second; folder/pe_order.txt must state n.  What the host routes of mcom_decompress.cpp refuse is refused, neither file is left.
-namespace {
-uint64_t pair_count(const char *folder, uint64_t n_rows)
-{
-	std::vector<uint8_t> t;
-	if (!slurp(std::string(folder) + "/pe_order.txt", t) || t.size() < 2 || t.size() > 24 || t.back() != '\n') throw Refuse{"no pe_order.txt: not a pair kept in input order"};
-	uint64_t v = 0;
-	for (size_t i = 0; i + 1 < t.size(); ++i) { if (t[i] < '0' || t[i] > '9') throw Refuse{"pe_order.txt is not a number"}; v = v * 10 + (uint64_t)(t[i] - '0'); }
-	if ((n_rows & 1) || v != n_rows / 2) throw Refuse{"pe_order.txt does not state half the reads' number"};
-	return v;
-}
-// name_1.mcn and name_2.mcn decoded on the device, name_2 against the decoded name_1 text; false: the archive has neither
-struct PairNames { NamesReady r[2]; std::vector<uint64_t> off[2]; };
-bool load_pair_names(Arena &A, const char *folder, uint64_t half, PairNames &P)
-{
-	std::vector<uint8_t> m[2];
-	const bool has1 = slurp(std::string(folder) + "/name_1.mcn", m[0]), has2 = slurp(std::string(folder) + "/name_2.mcn", m[1]);
-	if (has1 != has2) throw Refuse{"one of name_1.mcn and name_2.mcn is missing: name_2 is coded against name_1"};
-	if (!has1) return false;
-	uint8_t *d_text[2]; uint64_t bytes[2] = {0, 0};
-	for (int k = 0; k < 2; ++k) {
-		uint64_t nn = 0;
-		if ((k ? mcom_name_info_mate(m[k].data(), m[k].size(), &nn, &bytes[k]) : mcom_name_info(m[k].data(), m[k].size(), &nn, &bytes[k])) || nn != half) throw Refuse{"a name member does not state the pairs' number"};
-		const uint8_t *d_nm = A.upload(m[k].data(), m[k].size());
-		d_text[k] = A.alloc<uint8_t>(bytes[k]);
-		uint64_t *d_off = A.alloc<uint64_t>(half + 1);
-		const int rc = k ? (mcom_name_decode_mate(A.ctx, d_nm, m[k].size(), d_text[0], bytes[0], d_text[1], bytes[1], &bytes[1], &nn) || mcom_name_text_offsets(A.ctx, d_text[1], bytes[1], half, d_off))
-		                 : mcom_name_decode(A.ctx, d_nm, m[k].size(), d_text[0], bytes[0], &bytes[0], &nn, d_off);
-		if (rc || nn != half) { fprintf(stderr, "minicom gpu decoder: %s\n", mcom_last_error(A.ctx)); throw Refuse{"a name member is refused"}; }
-		P.off[k].resize(half + 1);
-		if (hipMemcpy(P.off[k].data(), d_off, (half + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
-		P.r[k] = NamesReady{d_text[k], d_off, bytes[k], &P.off[k]};
-	}
-	return true;
-}
-}  // namespace
 extern "C" int mcomh_decompress_order_pe_gpu(const char *folder, const char *out_path1, const char *out_path2, uint64_t *n_pairs, int device)
 {
 	if (!folder || !out_path1 || !out_path2) return -1;
 	try {
 		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
-			const uint64_t half = pair_count(folder, n_rows);
+			const uint64_t half = pairs_of(folder, n_rows);
 			return write_files(PE, A, table, n_rows, half, L, out_path1, out_path2, n_pairs);
 		});
 	} catch (...) { return -1; }
@@ -1038,16 +1005,7 @@ extern "C" int mcomh_decompress_fastq_order_pe_gpu(const char *folder, const cha
 	if (!folder || !out_path1 || !out_path2) return -1;
 	try {
 		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
-			const uint64_t half = pair_count(folder, n_rows);
-			const uint8_t *q1 = load_quals(A, folder, "qual_1.mcq", "-Q", half, L, (uint64_t)L), *q2 = load_quals(A, folder, "qual_2.mcq", "-Q", half, L, (uint64_t)L);
-			PairNames P;
-			const bool named = load_pair_names(A, folder, half, P);              // (every member is decoded before a file is opened)
-			EmitBufs bufs;
-			if (write_fastq(A, folder, table, half, L, out_path1, n_pairs, q1, &bufs, named ? &P.r[0] : nullptr)) return -1;
-			int rc = -1;
-			try { rc = write_fastq(A, folder, table + half * ((uint64_t)L + 1), half, L, out_path2, n_pairs, q2, &bufs, named ? &P.r[1] : nullptr); } catch (...) { remove(out_path1); throw; }
-			if (rc) remove(out_path1);
-			return rc;
+			return write_fastq_pair(A, folder, table, pairs_of(folder, n_rows), L, out_path1, out_path2, n_pairs, "qual_1.mcq", "qual_2.mcq", "-Q", true);
 		});
 	} catch (...) { return -1; }
 }
@@ -1059,18 +1017,10 @@ int mcom_range_gpu(const char *folder, const char *o1, const char *o2, uint64_t 
 	try {
 		Window W{first, count, pair};
 		return run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
-			const uint64_t cnt = W.count, row = (uint64_t)L + 1;                   // (clipped by run(); n_rows = cnt, or 2 cnt for a pair)
+			const uint64_t cnt = W.count;                                          // (clipped by run(); n_rows = cnt, or 2 cnt for a pair)
 			if (!fastq) return write_files(pair ? PE : ORDER, A, table, n_rows, cnt, L, o1, o2, n_written);
 			if (!pair) return write_fastq(A, folder, table, cnt, L, o1, n_written, nullptr, nullptr, nullptr, &W);
-			const uint8_t *q1 = load_quals(A, folder, "qual_1.mcq", "-Q", W.n_records, L, (uint64_t)L, &W), *q2 = load_quals(A, folder, "qual_2.mcq", "-Q", W.n_records, L, (uint64_t)L, &W);
-			PairNames P;
-			const bool named = load_pair_names(A, folder, W.n_records, P);
-			EmitBufs bufs;
-			if (write_fastq(A, folder, table, cnt, L, o1, n_written, q1, &bufs, named ? &P.r[0] : nullptr, &W)) return -1;
-			int rc = -1;
-			try { rc = write_fastq(A, folder, table + cnt * row, cnt, L, o2, n_written, q2, &bufs, named ? &P.r[1] : nullptr, &W); } catch (...) { remove(o1); throw; }
-			if (rc) remove(o1);
-			return rc;
+			return write_fastq_pair(A, folder, table, cnt, L, o1, o2, n_written, "qual_1.mcq", "qual_2.mcq", "-Q", true, &W);
 		}, nullptr, &W);
 	} catch (...) { return -1; }   // no C++ exception crosses the C boundary
 }
@@ -1088,7 +1038,7 @@ extern "C" int mcomh_verify_order_pe_reads_gpu(const char *folder, const char *f
 		char err[256] = "";
 		if (mcomh_fastq_pair_to_device(fastq1, fastq2, device, &L_in, 0, &in.d, &n_in, err, sizeof(err))) { fprintf(stderr, "minicom verify: cannot read %s and %s: %s\n", fastq1, fastq2, err[0] ? err : "not two FASTQ files of as many reads of one length"); return -1; }
 		const int rr = run(ORDER, folder, device, [&](Arena &A, const uint8_t *table, uint64_t n_rows, uint64_t, int L) {
-			(void)pair_count(folder, n_rows);
+			(void)pairs_of(folder, n_rows);
 			return compare_rows(ORDER, A, table, n_rows, 0, L, in.d, (uint64_t)n_in, L_in, rep);
 		});
 		if (rr) return -1;
@@ -1155,7 +1105,7 @@ extern "C" int mcomh_verify_ragged_gpu(const char *folder, const char *fastq, in
 		if (mcomh_fastq_lengths_file(fastq, device, 0, tmp_len.c_str(), &n_in, &L_in, &n_odd_in, err, sizeof err)) { fprintf(stderr, "minicom verify: cannot read %s: %s\n", fastq, err); return -1; }
 		std::vector<uint8_t> len_in, odd_seq_in, odd_qual_in;
 		if (!slurp(tmp_len, len_in)) return -1;
-		const bool has_qual = file_exists(dir + "/qual.mcq");
+		const bool has_qual = exists(dir + "/qual.mcq");
 		struct Dev { uint8_t *d = nullptr; ~Dev() { mcomh_device_free(d); } } in, qin;
 		if (mcom_ragged_split_to_device(fastq, device, 1, L_in, tmp_len.c_str(), &in.d, odd_seq_in, &ne_in, err, sizeof err) ||
 		    (has_qual && mcom_ragged_split_to_device(fastq, device, 3, L_in, tmp_len.c_str(), &qin.d, odd_qual_in, &ne_q, err, sizeof err))) {
