@@ -81,6 +81,29 @@ int mcom_set_verify_hash_bits(mcom_ctx *ctx, int bits);
 /* mcom_qual_transform's P-block kernel (csrc/qual_lossy.hip) stages tiles of whole rows in LDS, one lane per row: the rows of a tile,
  * so that a test can put its rows on both sides of a tile's edge.                                                                     */
 uint32_t mcom_test_qual_pblock_tile_rows(void);
+/* The one-launch prefix sums (csrc/scan.hip) and the read-back of their totals (mcom_d2h_async, csrc/api.hip), through the functions the
+ * library's own callers use.  None of these changes a result.
+ * mcom_test_scan_u32: the exclusive scan of n uint32 at any 4-byte aligned device addresses, d_in == d_out allowed; it does NOT wait for
+ * the stream (neither does mcom_scan_u64 of mcom.h, the same for uint64 -- it only waits when the context's workspace has to grow).
+ * mcom_test_scan_constants: threads of a workgroup, elements per thread of the uint32 and of the uint64 kernel (a tile = threads x
+ * elements), words of the ring of totals, entries of the table that tracks them.
+ * mcom_test_n_cu: the compute units the context sizes a scan's grid by (at most 2 workgroups each, at most 2048 in all).                */
+int mcom_test_scan_u32(mcom_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, size_t n);
+void mcom_test_scan_constants(uint32_t *threads, uint32_t *per_u32, uint32_t *per_u64, uint32_t *ring_words, uint32_t *tracked);
+int mcom_test_n_cu(const mcom_ctx *ctx);
+/* mcom_test_scan_script runs n_steps steps on the context's stream without waiting between them, waits at the end and returns the
+ * library's error code.  d_in / d_out: two device buffers of in_bytes / out_bytes (16-byte aligned; the same buffer twice is allowed).
+ * Every step is checked against these sizes, and against n_totals / copy_bytes, before the first one runs.
+ *   MCOM_TEST_STEP_SCAN      scan n elements of `width` (4 | 8) bytes from element a of d_in to element b of d_out
+ *   MCOM_TEST_STEP_READBACK  mcom_d2h_async of the last output element of scan step a (an earlier step) into h_totals[b]: the address
+ *                            and the width that scan registered; only `width` bytes of h_totals[b] are written
+ *   MCOM_TEST_STEP_LAUNCH    another kernel through MCOM_LAUNCH; n != 0: it stores the uint32 b at byte a (a multiple of 4) of d_out
+ *   MCOM_TEST_STEP_COPY      mcom_d2h_async of n <= 256 bytes from byte a of d_out (width == 0) or d_in (width == 1) to byte b of h_copy
+ *   MCOM_TEST_STEP_SYNC      mcom_stream_sync                                                                                        */
+enum { MCOM_TEST_STEP_SCAN = 0, MCOM_TEST_STEP_READBACK = 1, MCOM_TEST_STEP_LAUNCH = 2, MCOM_TEST_STEP_COPY = 3, MCOM_TEST_STEP_SYNC = 4 };
+typedef struct { uint32_t op, width; uint64_t a, b, n; } mcom_test_scan_step;
+int mcom_test_scan_script(mcom_ctx *ctx, const mcom_test_scan_step *steps, size_t n_steps, void *d_in, size_t in_bytes, void *d_out, size_t out_bytes,
+                          uint64_t *h_totals, size_t n_totals, uint8_t *h_copy, size_t copy_bytes);
 
 
 /* ---- libmcom_host.so ---- */

@@ -179,10 +179,11 @@ static int scan_one(mcom_ctx *ctx, const T *in, T *out, size_t n)
 	const size_t G = (tiles + per - 1) / per;
 	if (per >= (1ull << 32)) return mcom_fail(ctx, MCOM_E_ARG, "scan of %zu elements", n);
 	if (++ctx->scan_epoch == 0) ctx->scan_epoch = 1;                               // (0 = what the cleared scratch holds)
-	const uint32_t slot = ctx->scan_epoch % mcom_ctx::SCAN_TOTALS, gen_before = ctx->launch_gen;
+	const uint32_t slot = ctx->scan_epoch % mcom_ctx::SCAN_TOTALS;
+	mcom_ring_flush_slot(ctx, slot);                                               // (the ring came round: a read-back still waiting on that word is served BEFORE the launch that overwrites it)
+	const uint32_t gen_before = ctx->launch_gen;
 	MCOM_LAUNCH(k_scan_one<T>, dim3((unsigned)G), dim3(SO_THREADS), 0, ctx->stream, in, out, n, (uint32_t)per, ctx->scan_parts, ctx->scan_epoch, ctx->d_poison, ctx->d_scan_tot + slot);
 	MCOM_LAUNCH_CHECK(ctx);
-	mcom_ring_flush_slot(ctx, slot);                                               // (the ring came round: a read-back still waiting on that word is served now)
 	for (mcom_ctx::ScanTotal &t : ctx->scan_last) {
 		if (t.slot == slot) t.last = nullptr;                                      // (that total is gone)
 		if (t.last && (const char*)t.last >= (const char*)out && (const char*)t.last < (const char*)(out + n)) t.last = nullptr;   // this scan overwrites it (a reused scratch array)
@@ -223,3 +224,88 @@ int mcom_scan_u32(mcom_ctx *ctx, const uint32_t *in, uint32_t *out, size_t n, ui
 size_t mcom_scan_scratch_elems(size_t) { return 1; }
 int mcom_scan64(mcom_ctx *ctx, const uint64_t *in, uint64_t *out, size_t n, uint64_t *) { return scan_one<uint64_t>(ctx, in, out, n); }
 size_t mcom_scan64_scratch_elems(size_t) { return 1; }
+
+// ---- test hooks (include/mcom_test.h): the scans and the read-back of their totals as the library's callers drive them ----------------
+#include "../../include/mcom_test.h"
+
+extern "C" int mcom_test_scan_u32(mcom_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, size_t n)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if (n == 0) return MCOM_OK;
+	if (!d_in || !d_out || (((uintptr_t)d_in | (uintptr_t)d_out) & 3)) return mcom_fail(ctx, MCOM_E_ARG, "scan: null or misaligned device pointer");
+	return mcom_scan_u32(ctx, d_in, d_out, n, nullptr);
+}
+
+extern "C" void mcom_test_scan_constants(uint32_t *threads, uint32_t *per_u32, uint32_t *per_u64, uint32_t *ring_words, uint32_t *tracked)
+{
+	if (threads) *threads = SO_THREADS;
+	if (per_u32) *per_u32 = SoCfg<uint32_t>::PER;
+	if (per_u64) *per_u64 = SoCfg<uint64_t>::PER;
+	if (ring_words) *ring_words = mcom_ctx::SCAN_TOTALS;
+	if (tracked) *tracked = (uint32_t)(sizeof(mcom_ctx::scan_last) / sizeof(mcom_ctx::ScanTotal));
+}
+
+extern "C" int mcom_test_n_cu(const mcom_ctx *ctx) { return ctx ? ctx->n_cu : MCOM_E_ARG; }
+
+// the "other kernel" of a script: one launch that ends the validity of the tracked totals, and may change a word the host reads next
+__global__ void k_test_poke(uint32_t *p, uint32_t v) { if (p && threadIdx.x == 0 && blockIdx.x == 0) *p = v; }
+
+extern "C" int mcom_test_scan_script(mcom_ctx *ctx, const mcom_test_scan_step *steps, size_t n_steps, void *d_in, size_t in_bytes, void *d_out, size_t out_bytes,
+                                     uint64_t *h_totals, size_t n_totals, uint8_t *h_copy, size_t copy_bytes)
+{
+	if (!ctx) return MCOM_E_ARG;
+	if ((n_steps && !steps) || !d_in || !d_out || (((uintptr_t)d_in | (uintptr_t)d_out) & 15)) return mcom_fail(ctx, MCOM_E_ARG, "scan script: null or misaligned buffer");
+	// every step against the buffers first: nothing is launched for a script that would leave them
+	for (size_t i = 0; i < n_steps; ++i) {
+		const mcom_test_scan_step &s = steps[i];
+		bool ok = false;
+		switch (s.op) {
+		case MCOM_TEST_STEP_SCAN:
+			ok = (s.width == 4 || s.width == 8) && s.n > 0 && s.n <= in_bytes / s.width && s.a <= in_bytes / s.width - s.n
+			     && s.n <= out_bytes / s.width && s.b <= out_bytes / s.width - s.n;
+			break;
+		case MCOM_TEST_STEP_READBACK:
+			ok = s.a < i && steps[s.a].op == MCOM_TEST_STEP_SCAN && h_totals && s.b < n_totals;
+			break;
+		case MCOM_TEST_STEP_LAUNCH:
+			ok = s.n == 0 || ((s.a & 3) == 0 && out_bytes >= 4 && s.a <= out_bytes - 4 && s.b <= 0xFFFFFFFFull);
+			break;
+		case MCOM_TEST_STEP_COPY: {
+			const size_t src_bytes = s.width == 1 ? in_bytes : out_bytes;
+			ok = s.width <= 1 && s.n > 0 && s.n <= 256 && s.n <= src_bytes && s.a <= src_bytes - s.n && h_copy && s.n <= copy_bytes && s.b <= copy_bytes - s.n;
+			break;
+		}
+		case MCOM_TEST_STEP_SYNC: ok = true; break;
+		default: break;
+		}
+		if (!ok) return mcom_fail(ctx, MCOM_E_ARG, "scan script: step %zu is out of range", i);
+	}
+	for (size_t i = 0; i < n_steps; ++i) {
+		const mcom_test_scan_step &s = steps[i];
+		int rc = MCOM_OK;
+		switch (s.op) {
+		case MCOM_TEST_STEP_SCAN:
+			rc = s.width == 4 ? mcom_scan_u32(ctx, (const uint32_t*)d_in + s.a, (uint32_t*)d_out + s.b, (size_t)s.n, nullptr)
+			                  : mcom_scan64(ctx, (const uint64_t*)d_in + s.a, (uint64_t*)d_out + s.b, (size_t)s.n, nullptr);
+			break;
+		case MCOM_TEST_STEP_READBACK: {
+			const mcom_test_scan_step &sc = steps[s.a];
+			MCOM_HIP(ctx, mcom_d2h_async(ctx, h_totals + s.b, (const char*)d_out + (sc.b + sc.n - 1) * sc.width, sc.width));
+			break;
+		}
+		case MCOM_TEST_STEP_LAUNCH:
+			MCOM_LAUNCH(k_test_poke, dim3(1), dim3(64), 0, ctx->stream, s.n ? (uint32_t*)((char*)d_out + s.a) : (uint32_t*)nullptr, (uint32_t)s.b);
+			MCOM_LAUNCH_CHECK(ctx);
+			break;
+		case MCOM_TEST_STEP_COPY:
+			MCOM_HIP(ctx, mcom_d2h_async(ctx, h_copy + s.b, (const char*)(s.width == 1 ? d_in : d_out) + s.a, (size_t)s.n));
+			break;
+		default:
+			MCOM_HIP(ctx, mcom_stream_sync(ctx));
+			break;
+		}
+		if (rc) { (void)mcom_stream_sync(ctx); return rc; }
+	}
+	MCOM_HIP(ctx, mcom_stream_sync(ctx));
+	return MCOM_OK;
+}

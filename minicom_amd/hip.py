@@ -86,6 +86,8 @@ def _gzip_member_dtype():
 
 
 GZIP_MEMBER_DTYPE = _gzip_member_dtype()     # mcom_gzip_member of include/mcom.h
+SCAN_STEP_DTYPE = np.dtype([("op", "<u4"), ("width", "<u4"), ("a", "<u8"), ("b", "<u8"), ("n", "<u8")])   # mcom_test_scan_step of include/mcom_test.h
+SCAN_STEP_SCAN, SCAN_STEP_READBACK, SCAN_STEP_LAUNCH, SCAN_STEP_COPY, SCAN_STEP_SYNC = 0, 1, 2, 3, 4
 
 
 def rans_hint(model: int, stride: int = 1) -> int:
@@ -238,6 +240,10 @@ def load_library():
     L.mcom_gzip_walk.restype = i32; L.mcom_gzip_walk.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mcom_gzip_inflate.restype = i32; L.mcom_gzip_inflate.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64), C.POINTER(u64)]
     L.mcom_test_qual_pblock_tile_rows.restype = C.c_uint32; L.mcom_test_qual_pblock_tile_rows.argtypes = []
+    L.mcom_test_scan_u32.restype = i32; L.mcom_test_scan_u32.argtypes = [vp, vp, vp, sz]
+    L.mcom_test_scan_constants.restype = None; L.mcom_test_scan_constants.argtypes = [C.POINTER(u32)] * 5
+    L.mcom_test_n_cu.restype = i32; L.mcom_test_n_cu.argtypes = [vp]
+    L.mcom_test_scan_script.restype = i32; L.mcom_test_scan_script.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz]
     L.mcom_qual_info.restype = i32; L.mcom_qual_info.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode.restype = i32; L.mcom_qual_decode.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.mcom_qual_decode_rows.restype = i32; L.mcom_qual_decode_rows.argtypes = [vp, vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
@@ -1295,6 +1301,37 @@ class Context:
     def qual_pblock_tile_rows() -> int:
         """Test hook (mcom_test_qual_pblock_tile_rows): the rows of one tile of the P-block kernel"""
         return int(load_library().mcom_test_qual_pblock_tile_rows())
+
+    # -- test hooks of the one-launch scans and the read-back of their totals (include/mcom_test.h)
+    @staticmethod
+    def scan_constants() -> dict:
+        """mcom_test_scan_constants: threads of a workgroup, elements per thread by width, words of the ring of totals, tracked entries"""
+        v = [C.c_uint32() for _ in range(5)]
+        load_library().mcom_test_scan_constants(*[C.byref(x) for x in v])
+        return dict(zip(("threads", "per_u32", "per_u64", "ring_words", "tracked"), (int(x.value) for x in v)))
+
+    def n_cu(self) -> int:
+        """mcom_test_n_cu: the compute units the context sizes its grids by"""
+        return int(self.lib.mcom_test_n_cu(self._h))
+
+    def scan_async(self, src, dst, n: int):
+        """mcom_test_scan_u32 (int32 tensors) / mcom_scan_u64 (int64 tensors) of the first n elements of src into dst -- views at any
+        element offset of a larger buffer, or the same view twice.  Does not wait for the stream."""
+        torch = _torch()
+        assert src.dtype == dst.dtype and src.dtype in (torch.int32, torch.int64) and int(src.shape[0]) >= n and int(dst.shape[0]) >= n
+        f = self.lib.mcom_test_scan_u32 if src.dtype == torch.int32 else self.lib.mcom_scan_u64
+        self._check(f(self._h, self._p(src), self._p(dst), int(n)))
+
+    def scan_script(self, steps, d_in, d_out, n_totals: int = 0, copy_bytes: int = 0, fill: int = 0xA5):
+        """mcom_test_scan_script.  steps: SCAN_STEP_DTYPE records; d_in, d_out: device tensors (the two buffers).  Returns (the library's
+        error code, h_totals uint64 [n_totals], h_copy uint8 [copy_bytes]); both host arrays start out as bytes of `fill`."""
+        steps = np.ascontiguousarray(steps, dtype=SCAN_STEP_DTYPE)
+        tot = np.full(max(n_totals, 1), fill * 0x0101010101010101, dtype=np.uint64)
+        cp = np.full(max(copy_bytes, 1), fill, dtype=np.uint8)
+        rc = self.lib.mcom_test_scan_script(self._h, steps.ctypes.data, int(steps.shape[0]),
+                                            self._p(d_in), d_in.numel() * d_in.element_size(), self._p(d_out), d_out.numel() * d_out.element_size(),
+                                            tot.ctypes.data, n_totals, cp.ctypes.data, copy_bytes)
+        return int(rc), tot[:n_totals], cp[:copy_bytes]
 
     def dump_read_order(self, lists, mem, half: int = 0):
         """mcom_dump_read_order (DESIGN.md section 3.11).  lists: int32 device vector, the read ids of the eight lists in the decoder's order;
