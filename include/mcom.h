@@ -1033,6 +1033,43 @@ int mcom_fastq_ragged_rows(mcom_ctx *ctx, const uint8_t *d_text, uint64_t n_byte
 int mcom_fastq_emit_ragged(mcom_ctx *ctx, const mcom_ragged_src *src, uint64_t first, uint64_t count, uint8_t *d_out, uint64_t cap,
                            uint64_t *bytes);
 
+/* ---- the odd reads of a -V archive coded against the contigs (`minicom -p -V -A`; csrc/odd_align.hip, csrc/odd_align_model.hpp;
+ * DESIGN.md section 3.20) ----
+ * T, the reference text, is the bases of ref.bin.0, ref.bin.1, ... back to back, of every set as many as mcom_decode_member_table reports
+ * in *h_ref_bases, below 2^40 in all.  d_t holds it 2 bits per base as ref.bin does, in (t_bases + 31) / 32 + 1 64-bit words: one word
+ * of zeros stands behind the last base, and every call below reads it.  d_off: n_odd + 1 ascending offsets into the full odd text, made
+ * from mcom_ragged_index's slots; a record is at most 256 bytes.  A hit word is ~0 (not aligned) or d << 48 | strand << 40 | p.
+ *   mcom_odd_text_append   `bases` bases of a ref.bin image (d_ref, ref_bytes) behind base `at` of T.  The words of d_t are zeroed by the
+ *                          caller before the first set; sets are appended in order.  Asynchronous.
+ *   mcom_odd_index_build   the seed grid of T, (key, position) for every position that is a multiple of 8, sorted by key with
+ *                          mcom_radix_sort_128x: 16 bytes per entry, about 2 |T| bytes of HBM, and the sort's workspace while it runs.
+ *                          MCOM_E_OVERFLOW when the card has no room (or the grid has 2^32 entries or more).  Synchronous.
+ *   mcom_odd_align         d_hits[r] for the n_odd records of d_odd.  A record shorter than 31 bases or longer than T gets ~0.  The hits
+ *                          equal mcomh_odd_align's.  Synchronous.
+ *   mcom_odd_align_encode  the member odd.aln (d_member) and the text of the records that are not aligned (d_residual).  *member_len and
+ *                          *res_len are always set; with d_member NULL nothing else is written; MCOM_E_OVERFLOW when a capacity is too
+ *                          small.  No aligned record: *member_len = 0 and the residual is the text.  A hit word that the record and T do
+ *                          not bear out (its d is not the number of differences, its window leaves T) and a text outside ACGTN are
+ *                          MCOM_E_ARG.  Bytes equal mcomh_odd_align_encode's.  Synchronous.
+ *   mcom_odd_align_decode  the full odd text (odd_bytes = the last offset) from an UNTRUSTED member, T and the residual.  What section 3.20
+ *                          refuses is MCOM_E_ARG with *flags (host memory) set to the reasons, one bit each (odd_align_model.hpp), and
+ *                          mcom_last_error words the lowest one as the host twin does; d_out then holds nothing valid.  Nothing outside
+ *                          d_out[0 .. odd_bytes) is written.  Synchronous.                                                          */
+typedef struct mcom_odd_index mcom_odd_index;
+int mcom_odd_text_append(mcom_ctx *ctx, uint64_t *d_t, uint64_t t_words, uint64_t at, const uint8_t *d_ref, uint64_t ref_bytes, uint64_t bases);
+int mcom_odd_index_build(mcom_ctx *ctx, const uint64_t *d_t, uint64_t t_bases, mcom_odd_index **idx);
+void mcom_odd_index_free(mcom_ctx *ctx, mcom_odd_index *idx);
+uint64_t mcom_odd_index_size(const mcom_odd_index *idx);
+int mcom_odd_index_copy(mcom_ctx *ctx, const mcom_odd_index *idx, mcom_mm128 *d_out);   /* the sorted entries (x the key, y the position) into d_out; synchronous */
+int mcom_odd_align(mcom_ctx *ctx, const mcom_odd_index *idx, const uint64_t *d_t, uint64_t t_bases, const uint8_t *d_odd, const uint64_t *d_off,
+                   uint64_t n_odd, uint64_t *d_hits);
+int mcom_odd_align_encode(mcom_ctx *ctx, const uint64_t *d_hits, const uint8_t *d_odd, const uint64_t *d_off, uint64_t n_odd, const uint64_t *d_t,
+                          uint64_t t_bases, uint8_t *d_member, uint64_t member_cap, uint64_t *member_len, uint8_t *d_residual, uint64_t res_cap,
+                          uint64_t *res_len);
+int mcom_odd_align_decode(mcom_ctx *ctx, const uint8_t *d_member, uint64_t member_len, const uint64_t *d_t, uint64_t t_bases,
+                          const uint8_t *d_residual, uint64_t res_len, const uint64_t *d_off, uint64_t n_odd, uint64_t odd_bytes, uint8_t *d_out,
+                          uint32_t *flags);
+
 /* ---- the digest of a FASTQ file (`minicom -K`; csrc/digest.hip, csrc/digest_model.hpp) ----
  * A line is the bytes of a FASTQ line without its newline and without the leading '@' / '+' of lines 1 and 3.  Every hash is a pair of
  * 64-bit words, one per seed; the definition is digest_model.hpp's and DESIGN.md's.

@@ -586,6 +586,32 @@ int mcomh_fastq_quality_member_ragged(const char *fastq, int L, int device, cons
 int mcomh_fastq_emit_ragged(const mcomh_ragged_src *src, uint64_t first, uint64_t count, uint8_t *out, uint64_t cap, uint64_t *bytes);
 int mcomh_verify_ragged_gpu(const char *folder, const char *fastq, int device, mcomh_verify_report rep[5], int present[5]);
 
+/* ---- `minicom -p -V -A`: the odd reads coded against the contigs (host/mcom_odd_align.cpp) ----
+ * The plain C++ twins of the mcom_odd_* calls of include/mcom.h, every pointer in host memory: the same text T (2 bits per base in
+ * (t_bases + 31) / 32 + 1 words, the last one zero), the same hits, the same member bytes, the same refusals in the same words.
+ *   mcomh_odd_text_append   `bases` bases of a ref.bin image behind base `at` of T (zeroed by the caller)
+ *   mcomh_odd_index_build   the sorted seed grid; release with mcomh_odd_index_free
+ *   mcomh_odd_align         one hit word per record: ~0, or d << 48 | strand << 40 | p
+ *   mcomh_odd_align_encode  member and residual; sizes always set, member NULL: sizes only; -2 when a capacity is too small; -1 for a hit
+ *                           word that the record and T do not bear out or a text outside ACGTN
+ *   mcomh_odd_align_decode  the full odd text (off[n_odd] bytes) from an untrusted member: -1 with *flags = the reasons
+ *                           (mcomh_odd_align_refusal words the lowest), and out holds nothing valid
+ *   mcomh_odd_align_folder  the UNGROUPED stream files of FOLDER (ref.bin.*, beg_pos.bin.*, info.txt, len.bin, odd.seq): odd.aln written and
+ *                           odd.seq rewritten to the records that are not aligned -- by the device calls on GPU `device`, by the twins
+ *                           with device -1, the same bytes.  No record aligned: nothing is written.  -1 with a message in err.        */
+typedef struct mcomh_odd_index mcomh_odd_index;
+void mcomh_odd_text_append(uint64_t *t, uint64_t at, const uint8_t *ref, uint64_t ref_bytes, uint64_t bases);
+int mcomh_odd_index_build(const uint64_t *t, uint64_t t_bases, mcomh_odd_index **idx);
+void mcomh_odd_index_free(mcomh_odd_index *idx);
+uint64_t mcomh_odd_index_size(const mcomh_odd_index *idx);
+int mcomh_odd_align(const mcomh_odd_index *idx, const uint64_t *t, uint64_t t_bases, const uint8_t *odd, const uint64_t *off, uint64_t n_odd, uint64_t *hits);
+int mcomh_odd_align_encode(const uint64_t *hits, const uint8_t *odd, const uint64_t *off, uint64_t n_odd, const uint64_t *t, uint64_t t_bases, uint8_t *member,
+                           uint64_t member_cap, uint64_t *member_len, uint8_t *residual, uint64_t res_cap, uint64_t *res_len);
+int mcomh_odd_align_decode(const uint8_t *member, uint64_t member_len, const uint64_t *t, uint64_t t_bases, const uint8_t *residual, uint64_t res_len, const uint64_t *off,
+                           uint64_t n_odd, uint8_t *out, uint32_t *flags);
+const char *mcomh_odd_align_refusal(uint32_t flags);
+int mcomh_odd_align_folder(const char *folder, int device, uint64_t *n_odd, uint64_t *n_aligned, uint64_t *residual_bytes, char *err, size_t err_cap);
+
 /* ---- self-checking archives: `minicom -K` stores a digest of the input, `minicom -d` checks it (host/mcom_digest.cpp, DESIGN.md
  * section 3.18) ----
  * digest.txt is plain text, a member stored as it is: `minicom-digest 1`, `files <1|2>`, `n <records per file>`, then one line per key,

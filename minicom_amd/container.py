@@ -47,6 +47,7 @@ PAIR_ORDER = "pe_order.txt"       # marks a pair kept in input order (DESIGN.md 
 PAIR_MEMBERS = ("qual_1.mcq", "qual_2.mcq", "name_1.mcn", "name_2.mcn")     # its quality values and names, file by file; name_2 is coded against name_1
 LOSSY_MARKER = "qual_lossy.txt"   # marks quality values stored with bounded loss: the canonical spec and a newline; stored as it is
 RAGGED_MEMBERS = ("len.bin", "odd.seq", "odd.qual")   # reads of differing lengths: through the codec like the singles; len.bin marks the archive
+ODD_ALIGN_MEMBER = "odd.aln"      # odd reads coded against the contigs: through the codec like odd.seq, which then holds the others
 AGREE_MARKER = "qual_agree.txt"   # marks quality values of agreeing bases stored as one Phred value: `Q C` and a newline; stored as it is
 DIGEST_MEMBER = "digest.txt"      # the digest of the input of an archive made with digest=True (`minicom -K`): plain text, stored as it is
 QUALITY_MEMBER = "qual.mcq"       # quality values of a -p archive: coded by its own coder, stored as it is
@@ -136,7 +137,7 @@ def pack(folder: str, out_path: str, codec: str = "xz", threads: int = 8, device
         names = sorted({os.path.basename(p) for pat in patterns for p in glob.glob(os.path.join(folder, pat))})
         if names:
             members.append((group + ".tar", _inner_tar(folder, names)))
-    for s in SINGLES + RAGGED_MEMBERS:
+    for s in SINGLES + RAGGED_MEMBERS + (ODD_ALIGN_MEMBER,):
         p = os.path.join(folder, s)
         if os.path.isfile(p):
             with open(p, "rb") as f:
@@ -249,7 +250,7 @@ def unpack(path: str, folder: str, threads: int = 8, device: int | None = None) 
 # ---- end to end: what `minicom -r IN [-p]`, `minicom -1 IN1 -2 IN2` and `minicom -d X.minicom` amount to -------------
 def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bool = False, codec: str = "xz",
                    device: int = 0, threads: int = 8, quality: bool = False, names: bool = False, quality_reordered: bool = False,
-                   quality_lossy=None, ragged: bool = False, quality_agree=None, digest: bool = False, **params) -> dict:
+                   quality_lossy=None, ragged: bool = False, quality_agree=None, digest: bool = False, ragged_align: bool = False, **params) -> dict:
     """FASTQ/FASTA (plain or .gz; path2 = the mates' file) -> `.minicom`.  The hot path runs on `device` (there is no CPU
     fallback), the stream writer and the packaging on the host -- except the codecs "rans" and "bwt", whose members are coded on `device` too.
     quality=True (`minicom -Q`; needs order=True and no path2, because only the -p archive keeps the order that says which quality row
@@ -268,6 +269,9 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
     ragged=True (`minicom -p -V`; needs order=True; not with path2, quality_reordered or quality_lossy): the
     reads may differ in length.  Those of the modal length are the archive's reads, the others travel in len.bin, odd.seq and odd.qual;
     a file of one length gives the archive made without it.
+    ragged_align=True (`minicom -p -V -A`; needs ragged=True): the reads of another length are searched for in the
+    contigs on `device`; those found travel in odd.aln as a place and their differences, odd.seq keeps the others.  Where none is found
+    the archive is the one made with ragged alone.
     digest=True (`minicom -K`; every mode): one more pass over the input on `device` stores its digest as
     digest.txt (without the quality keys beside quality_lossy or quality_agree); decompress_file then checks what it wrote against it, and
     test_file tests the archive.  Without it the archive does not change.  Returns pack()'s member sizes plus the read count (with ragged: "n_reads"
@@ -287,9 +291,11 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         raise ValueError("quality_reordered keeps the quality values in the archive's own order: not with order, quality or names")
     if ragged and (not order or path2 is not None or quality_reordered or lossy is not None):
         raise ValueError("ragged keeps reads of differing lengths of one file in its input order: order=True, no path2, no quality_reordered, no quality_lossy")
+    if ragged_align and not ragged:
+        raise ValueError("ragged_align codes the reads of another length that ragged keeps against the contigs: without ragged=True there are none")
     if ragged:
         with tempfile.TemporaryDirectory(dir=os.path.dirname(os.path.abspath(out_path)) or ".") as td:
-            sizes = _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params, digest)
+            sizes = _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params, digest, ragged_align)
         if sizes is not None:
             return sizes                                             # (None: one length after all -- on as without ragged)
     p = Pipeline.from_fastq(path, device=device, path2=path2, host_threads=threads, **params)
@@ -333,7 +339,7 @@ def compress_fastq(path: str, out_path: str, path2: str | None = None, order: bo
         p.close()
 
 
-def _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params, digest=False):
+def _compress_ragged(path, out_path, td, codec, device, threads, quality, names, params, digest=False, align=False):
     """compress_fastq(ragged=True) in the order of `minicom -p -V`: lengths, the core over the reads of the modal length, the quality
     values, the names, the container.  None when every read has one length."""
     from .hip import McomError
@@ -346,6 +352,12 @@ def _compress_ragged(path, out_path, td, codec, device, threads, quality, names,
     try:
         p.pre_process()
         p.cluster_dump(td, order=True, paired=False)
+        if align:                                                    # the odd reads against the contigs just dumped; an empty odd.seq is no member
+            from .pipeline import odd_align_folder
+            odd_align_folder(td, device=device)
+            odd_seq = os.path.join(td, RAGGED_MEMBERS[1])
+            if os.path.isfile(os.path.join(td, ODD_ALIGN_MEMBER)) and os.path.getsize(odd_seq) == 0:
+                os.remove(odd_seq)
         if quality:
             n_rows = fastq_quality_member_ragged(path, L, len_path, os.path.join(td, QUALITY_MEMBER), os.path.join(td, RAGGED_MEMBERS[2]), device=device)
             if n_rows != p.n:

@@ -264,6 +264,14 @@ def load_library():
     L.mcom_ragged_index.restype = i32; L.mcom_ragged_index.argtypes = [vp, vp, u64, C.c_uint32, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mcom_fastq_ragged_rows.restype = i32; L.mcom_fastq_ragged_rows.argtypes = [vp, vp, u64, vp, u64, u64, i32, C.c_uint32, vp, vp, u64, vp, u64, u64, vp, u64, vp]
     L.mcom_fastq_emit_ragged.restype = i32; L.mcom_fastq_emit_ragged.argtypes = [vp, C.POINTER(RaggedSrc), u64, u64, vp, u64, C.POINTER(u64)]
+    L.mcom_odd_text_append.restype = i32; L.mcom_odd_text_append.argtypes = [vp, vp, u64, u64, vp, u64, u64]
+    L.mcom_odd_index_build.restype = i32; L.mcom_odd_index_build.argtypes = [vp, vp, u64, C.POINTER(vp)]
+    L.mcom_odd_index_free.restype = None; L.mcom_odd_index_free.argtypes = [vp, vp]
+    L.mcom_odd_index_size.restype = u64; L.mcom_odd_index_size.argtypes = [vp]
+    L.mcom_odd_index_copy.restype = i32; L.mcom_odd_index_copy.argtypes = [vp, vp, vp]
+    L.mcom_odd_align.restype = i32; L.mcom_odd_align.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
+    L.mcom_odd_align_encode.restype = i32; L.mcom_odd_align_encode.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
+    L.mcom_odd_align_decode.restype = i32; L.mcom_odd_align_decode.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, vp, C.POINTER(u32)]
     L.mcom_bwt_bound.restype = u64; L.mcom_bwt_bound.argtypes = [u64]
     L.mcom_bwt_encode.restype = i32; L.mcom_bwt_encode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.mcom_bwt_decode.restype = i32; L.mcom_bwt_decode.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
@@ -1548,6 +1556,115 @@ class Context:
         sums = (C.c_uint64 * 16)()
         self._check(self.lib.mcom_digest_reduce(self._h, self._p(hS1) if n else None, self._p(hQ1), self._p(hN1), self._p(hS2), self._p(hQ2), self._p(hN2), n, sums))
         return [int(v) for v in sums]
+
+    # ---- the odd reads of a -V archive against the contigs (csrc/odd_align.hip) ----
+    _ODD_GUARD = 0xA5A5A5A5A5A5A5A5 - (1 << 64)                # 0xA5 in every byte of an int64 word
+
+    def _odd_guarded(self, words: int, canary: int, cols: int = 0):
+        """an int64 device buffer of `words` zeroed words (rows of `cols` when given) with canary // 8 words of 0xA5 bytes on either side:
+        (the whole buffer, the zeroed view inside it)"""
+        torch = _torch()
+        if canary % 8:
+            raise McomError("a canary around 64-bit words is a multiple of 8 bytes")
+        cw, n = canary // 8, words * max(cols, 1)
+        buf = torch.full((n + 2 * cw,), self._ODD_GUARD, dtype=torch.int64, device=self.device)
+        buf[cw:cw + n] = 0
+        return buf, buf[cw:cw + n]
+
+    def _odd_guard_check(self, buf, inner_words: int, canary: int, what: str):
+        cw = canary // 8
+        if cw and not (bool((buf[:cw] == self._ODD_GUARD).all()) and bool((buf[cw + inner_words:] == self._ODD_GUARD).all())):
+            raise McomError(what + " wrote outside its output")
+
+    def odd_text(self, refs, canary: int = 0):
+        """mcom_odd_text_append over refs, a list of (ref.bin image: uint8 device vector, bases taken from it): T as an int64 device vector of
+        (|T| + 31) // 32 + 1 words (2 bits per base, the last word zero), and |T|.  canary: that many bytes of 0xA5 (a multiple of 8) are
+        placed around T and checked after the calls."""
+        total = sum(int(b) for _, b in refs)
+        words = (total + 31) // 32 + 1
+        buf, t = self._odd_guarded(words, canary)
+        at = 0
+        for img, bases in refs:
+            self._check(self.lib.mcom_odd_text_append(self._h, self._p(t), words, at, self._p(img, _torch().uint8) if int(img.shape[0]) else None, int(img.shape[0]), int(bases)))
+            at += int(bases)
+        self.sync()
+        self._odd_guard_check(buf, words, canary, "odd_text_append")
+        return t.clone(), total
+
+    def _odd_args(self, t, t_bases, odd, off):
+        torch = _torch()
+        n_odd = int(off.shape[0]) - 1
+        if t.dtype != torch.int64 or int(t.shape[0]) < (int(t_bases) + 31) // 32 + 1 or off.dtype != torch.int64 or n_odd < 0 or odd.dtype != torch.uint8:
+            raise McomError("odd_align: t int64 of (|T| + 31) // 32 + 1 words, odd uint8, off int64 [n_odd + 1]")
+        return n_odd
+
+    def odd_index_build(self, t, t_bases: int):
+        """mcom_odd_index_build: the handle of the sorted seed grid of T (release it with odd_index_free)."""
+        torch = _torch()
+        if t.dtype != torch.int64 or int(t.shape[0]) < (int(t_bases) + 31) // 32 + 1:
+            raise McomError("odd_index_build: t int64 of (|T| + 31) // 32 + 1 words")
+        h = C.c_void_p()
+        self._check(self.lib.mcom_odd_index_build(self._h, self._p(t), int(t_bases), C.byref(h)))
+        return h
+
+    def odd_index_free(self, idx):
+        self.lib.mcom_odd_index_free(self._h, idx)
+
+    def odd_index_entries(self, idx, canary: int = 0):
+        """the sorted grid as an int64 tensor [n, 2] (key, position): a copy, made between canaries when asked for"""
+        n = int(self.lib.mcom_odd_index_size(idx))
+        buf, out = self._odd_guarded(n, canary, cols=2)
+        if n:
+            self._check(self.lib.mcom_odd_index_copy(self._h, idx, self._p(out)))
+        self._odd_guard_check(buf, 2 * n, canary, "odd_index_copy")
+        return out.clone().reshape(n, 2)
+
+    def odd_align(self, idx, t, t_bases: int, odd, off, canary: int = 0):
+        """mcom_odd_align.  odd: the full odd text (uint8 device vector), off: int64 [n_odd + 1].  Returns the hit words, int64 [n_odd]
+        (-1: not aligned; else d << 48 | strand << 40 | p).  canary: that many bytes of 0xA5 (a multiple of 8) are placed around the hit
+        words -- exactly n_odd of them, none for no record -- and checked after the call."""
+        n_odd = self._odd_args(t, t_bases, odd, off)
+        buf, hits = self._odd_guarded(n_odd, canary)
+        self._check(self.lib.mcom_odd_align(self._h, idx, self._p(t), int(t_bases), self._p(odd), self._p(off), n_odd, self._p(hits) if n_odd else None))
+        self._odd_guard_check(buf, n_odd, canary, "odd_align")
+        return hits.clone()
+
+    def odd_align_encode(self, hits, t, t_bases: int, odd, off, canary: int = 0):
+        """mcom_odd_align_encode: (member, residual) as uint8 device vectors; member is empty when no record is aligned.  canary: that many
+        bytes of 0xA5 are placed around both outputs and checked after the call."""
+        torch = _torch()
+        n_odd = self._odd_args(t, t_bases, odd, off)
+        ml, rl = C.c_uint64(), C.c_uint64()
+        args = (self._p(hits, torch.int64) if n_odd else None, self._p(odd), self._p(off), n_odd, self._p(t), int(t_bases))
+        self._check(self.lib.mcom_odd_align_encode(self._h, *args, None, 0, C.byref(ml), None, 0, C.byref(rl)))
+        m, r = int(ml.value), int(rl.value)
+        mem = torch.full((m + 2 * canary + 1,), 0xA5, dtype=torch.uint8, device=self.device)
+        res = torch.full((r + 2 * canary + 1,), 0xA5, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.mcom_odd_align_encode(self._h, *args, C.c_void_p(mem.data_ptr() + canary), m, C.byref(ml), C.c_void_p(res.data_ptr() + canary), r, C.byref(rl)))
+        for buf, n in ((mem, m), (res, r)):
+            if canary and not (bool((buf[:canary] == 0xA5).all()) and bool((buf[canary + n:] == 0xA5).all())):
+                raise McomError("odd_align_encode wrote outside its output")
+        return mem[canary:canary + m].clone(), res[canary:canary + r].clone()
+
+    def odd_align_decode(self, member, t, t_bases: int, residual, off, canary: int = 0):
+        """mcom_odd_align_decode of an untrusted member.  Returns (the full odd text or None, flags, the refusal's words or None)."""
+        torch = _torch()
+        n_odd = int(off.shape[0]) - 1
+        if t.dtype != torch.int64 or int(t.shape[0]) < (int(t_bases) + 31) // 32 + 1 or off.dtype != torch.int64 or n_odd < 0:
+            raise McomError("odd_align_decode: t int64 of (|T| + 31) // 32 + 1 words, off int64 [n_odd + 1]")
+        odd_bytes = int(off[-1].item())
+        out = torch.full((odd_bytes + 2 * canary + 1,), 0xA5, dtype=torch.uint8, device=self.device)
+        flags = C.c_uint32()
+        rc = self.lib.mcom_odd_align_decode(self._h, self._p(member, torch.uint8), int(member.shape[0]), self._p(t), int(t_bases),
+                                            self._p(residual, torch.uint8) if int(residual.shape[0]) else None, int(residual.shape[0]), self._p(off), n_odd, odd_bytes,
+                                            C.c_void_p(out.data_ptr() + canary), C.byref(flags))
+        if canary and not (bool((out[:canary] == 0xA5).all()) and bool((out[canary + odd_bytes:] == 0xA5).all())):
+            raise McomError("odd_align_decode wrote outside its output")
+        if rc:
+            if not flags.value:
+                self._check(rc)
+            return None, int(flags.value), self.lib.mcom_last_error(self._h).decode()
+        return out[canary:canary + odd_bytes].clone(), 0, None
 
     # ---- reads of differing lengths (csrc/ragged.hip; DESIGN.md section 3.16) ----
     def fastq_lengths(self, text, first_record: int = 0, lens=None, hist=None):

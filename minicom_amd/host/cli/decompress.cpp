@@ -24,6 +24,9 @@
 // archive's, part by part; exit status as --verify.  The plain decoder and --fastq pick DIR/len.bin up by themselves.
 // decompress --agree-mask [--gpu] DIR C OUT: the agreement mask of `minicom -a Q[:C]` of the stream files in DIR -- a
 // default-mode or a -p archive -- written to OUT; prints `n L bits_set`.  The quality verifiers pick DIR/qual_agree.txt up by themselves.
+// decompress --odd-align [--gpu] DIR: `minicom -p -V -A` over the ungrouped stream files in DIR: the odd reads of
+// odd.seq are searched for in the contigs of ref.bin.* (on GPU 0 with --gpu, by the host twins without: the same bytes), odd.aln is written and
+// odd.seq rewritten to the reads that were not found; prints `n_odd n_aligned residual_bytes`.  The decoders pick DIR/odd.aln up by themselves.
 // decompress --check-digest [--gpu] DIR OUT1 [OUT2]: an archive made with -K (DIR holds digest.txt): the output
 // files are digested as the input was (on GPU 0 with --gpu, by the host twin without) and set against it, every key that the archive's
 // kind can answer; one line says what was compared.  Exit status as --verify: 0 identical, 2 different, 1 refused or error.
@@ -241,6 +244,18 @@ static int verify_order_pe(int argc, char **argv)
 	return rc;
 }
 
+static int odd_align(int argc, char **argv)
+{
+	const bool gpu = argc > 1 && !strcmp(argv[1], "--gpu");
+	if (gpu) { --argc; ++argv; }
+	if (argc < 2) { fprintf(stderr, "usage: decompress --odd-align [--gpu] DIR\n"); return 1; }
+	uint64_t n_odd = 0, n_aligned = 0, residual = 0;
+	char err[256] = "";
+	if (mcomh_odd_align_folder(argv[1], gpu ? 0 : -1, &n_odd, &n_aligned, &residual, err, sizeof err)) { fprintf(stderr, "decompress --odd-align: %s: %s\n", argv[1], err); return 1; }
+	printf("%llu %llu %llu\n", (unsigned long long)n_odd, (unsigned long long)n_aligned, (unsigned long long)residual);
+	return 0;
+}
+
 static int verify_ragged(int argc, char **argv)
 {
 	if (argc < 3) { fprintf(stderr, "usage: decompress --verify-ragged DIR IN.fastq\n"); return 1; }
@@ -272,6 +287,7 @@ int main(int argc, char **argv)
 	if (argc > 1 && !strcmp(argv[1], "--check-digest")) return check_digest(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--verify-ragged")) return verify_ragged(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--agree-mask")) return agree_mask(argc - 1, argv + 1);
+	if (argc > 1 && !strcmp(argv[1], "--odd-align")) return odd_align(argc - 1, argv + 1);
 	if (argc > 1 && !strcmp(argv[1], "--order-pe")) return order_pe(argc - 1, argv + 1, false);
 	if (argc > 1 && !strcmp(argv[1], "--fastq-order-pe")) return order_pe(argc - 1, argv + 1, true);
 	if (argc > 1 && !strcmp(argv[1], "--verify-order-pe")) return verify_order_pe(argc - 1, argv + 1);

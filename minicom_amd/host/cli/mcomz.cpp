@@ -19,6 +19,8 @@
 // `minicom -a` behind the gather and in front of SPEC: the value of every column whose bit of MASKFILE
 // (`decompress --agree-mask`) is set becomes Phred Q; row r of the member belongs to mask row ROW + r (ROW 0 without --mask-first).  The
 // report goes to stderr in one line, `agree Q: mask_bits B changed C sum_abs A sum_sq S max_abs M`, in front of the lossy one.
+// mcomz e / d take `odd.aln` (`minicom -p -V -A`) as any other side member: it is made by `decompress --odd-align`,
+// not here, and is packed with len.bin, odd.seq and odd.qual through the codec the archive's other members go through.
 // mcomz --lossy-spec SPEC: prints the canonical text of SPEC; exit status 1 when the parser refuses it (what `minicom -b` asks first).
 // mcomz e --names [--gpu] IN OUT: IN is a name text (per record its name and the text of its third line, a line each; DESIGN.md section
 // 3.10), OUT a `.mcn` member; a line above 255 bytes is refused and its record named.  d knows such a member by its magic.

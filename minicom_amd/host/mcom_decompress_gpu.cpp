@@ -49,6 +49,8 @@ struct Arena {
 	std::vector<void*> dev, pinned;
 	hipEvent_t ev[2] = {nullptr, nullptr};
 	mcom_ctx *ctx = nullptr;
+	struct SetRef { const uint8_t *d_ref; uint64_t ref_bytes, bases; };
+	std::vector<SetRef> set_refs;                           // the ref.bin of every stream set in HBM and the bases its contigs hold (run(), A.2)
 	~Arena()
 	{
 		if (ctx) (void)mcom_sync(ctx);
@@ -279,6 +281,7 @@ int run(Mode mode, const char *folder, int device, const Tail &tail, const Betwe
 			ok(A.ctx, mcom_decode_check_lines(A.ctx, t.d, t.bytes, t.start, nm, L, 0, d_flag));
 			s.src.d_text = t.d; s.src.text_bytes = t.bytes; s.src.d_line_start = t.start;
 			s.src.d_ref = A.upload(f.ref.data(), f.ref.size()); s.src.ref_bytes = f.ref.size();
+			A.set_refs.push_back({s.src.d_ref, s.src.ref_bytes, ref_bases});
 			s.src.d_cid = cid; s.src.d_pos = pos; s.src.d_coff = coff; s.src.n_contigs = nc;
 			s.src.d_dir = A.upload(f.dir.data(), f.dir.size()); s.src.dir_bytes = f.dir.size();
 			if (mode == ORDER) {
@@ -641,6 +644,32 @@ struct RaggedDev {
 	mcom_ragged_src S;
 	std::vector<uint64_t> off;                              // record offsets of the name text, on the host (empty: no names)
 };
+// `minicom -V -A`: the full odd text rebuilt on the card from odd.aln, the residual (P.odd_seq as loaded) and the
+// ref.bin images run() has uploaded, set after set into one packed text; P.odd_seq becomes the full text, which stays in HBM
+const uint8_t *rebuild_odd(Arena &A, const char *folder, int L, McomRaggedParts &P)
+{
+	std::vector<uint8_t> member;
+	if (!slurp(std::string(folder) + "/odd.aln", member)) refuse_member("cannot read odd.aln");
+	std::vector<uint64_t> off(1, 0);
+	for (uint8_t b : P.len) if ((int)b + 1 != L) off.push_back(off.back() + (uint64_t)b + 1);
+	uint64_t bases = 0;
+	for (const Arena::SetRef &s : A.set_refs) bases += s.bases;
+	if (bases >= ((uint64_t)1 << 40)) refuse_member("the contigs hold 2^40 bases or more");
+	const uint64_t words = (bases + 31) / 32 + 1;
+	uint64_t *d_t = A.alloc<uint64_t>(words);
+	if (hipMemset(d_t, 0, words * 8) != hipSuccess) throw Refuse{"memset failed"};
+	uint64_t at = 0;
+	for (const Arena::SetRef &s : A.set_refs) { ok(A.ctx, mcom_odd_text_append(A.ctx, d_t, words, at, s.d_ref, s.ref_bytes, s.bases)); at += s.bases; }
+	const uint8_t *d_member = A.upload(member.data(), member.size()), *d_res = A.upload(P.odd_seq.data(), P.odd_seq.size());
+	const uint64_t *d_off = A.upload(off.data(), off.size());
+	uint8_t *d_out = A.alloc<uint8_t>(off.back());
+	uint32_t flags = 0;
+	if (mcom_odd_align_decode(A.ctx, d_member, member.size(), d_t, bases, d_res, P.odd_seq.size(), d_off, off.size() - 1, off.back(), d_out, &flags)) refuse_member(mcom_last_error(A.ctx));
+	P.odd_seq.resize(off.back());
+	if (off.back() && hipMemcpy(P.odd_seq.data(), d_out, off.back(), hipMemcpyDeviceToHost) != hipSuccess) throw Refuse{"download failed"};
+	return d_out;
+}
+
 // the side members and, for fastq, the quality rows and the names, on the device; S ready for the emit call
 void load_ragged(Arena &A, const char *folder, const uint8_t *table, uint64_t n_even, int L, bool fastq, RaggedDev &R)
 {
@@ -648,14 +677,17 @@ void load_ragged(Arena &A, const char *folder, const uint8_t *table, uint64_t n_
 	const bool has_qual = slurp(std::string(folder) + "/qual.mcq", qhead), named = slurp(std::string(folder) + "/name.mcn", nmember);
 	if (fastq && !has_qual) refuse_member("no qual.mcq: not a -Q archive");
 	std::string why;
-	if (!mcom_ragged_load(folder, L, n_even, has_qual, R.P, why)) refuse_member(why);
+	const bool aligned = mcom_odd_align_present(folder);                      // then P.odd_seq is the residual, and the text is rebuilt below
+	if (!mcom_ragged_load(folder, L, n_even, has_qual, R.P, why, !aligned)) refuse_member(why);
 	uint64_t qn = 0, nn = 0, names_bytes = 0; uint32_t qL = 0;
 	if (has_qual && (mcom_qual_info(qhead.data(), qhead.size(), &qn, &qL) || qn != n_even || (int)qL != L)) refuse_member("qual.mcq does not state the number and length of the reads of the modal length");
 	if (named && (mcom_name_info(nmember.data(), nmember.size(), &nn, &names_bytes) || nn != R.P.n)) refuse_member("name.mcn does not state the records' number");
 	mcom_ragged_src &S = R.S;
 	memset(&S, 0, sizeof S);
 	S.d_reads = table; S.read_pitch = (uint64_t)L + 1; S.n_even = n_even; S.L = (uint32_t)L; S.n = R.P.n;
-	S.d_odd_seq = A.upload(R.P.odd_seq.data(), R.P.odd_seq.size()); S.odd_bytes = R.P.odd_seq.size();
+	S.d_odd_seq = aligned ? rebuild_odd(A, folder, L, R.P) : A.upload(R.P.odd_seq.data(), R.P.odd_seq.size());
+	S.odd_bytes = R.P.odd_seq.size();
+	if (has_qual && R.P.odd_qual.size() != S.odd_bytes) refuse_member("the lengths of len.bin do not add up to the size of odd.qual");
 	const uint8_t *d_len = A.upload(R.P.len.data(), R.P.len.size());
 	uint64_t *d_slot = A.alloc<uint64_t>(R.P.n);
 	uint64_t ne = 0, no = 0, ob = 0;

@@ -565,19 +565,25 @@ bool mcom_ragged_present(const char *folder)
 	return true;
 }
 
-bool mcom_ragged_load(const char *folder, int L, uint64_t n_even, bool want_qual, McomRaggedParts &P, std::string &why)
+bool mcom_ragged_load(const char *folder, int L, uint64_t n_even, bool want_qual, McomRaggedParts &P, std::string &why, bool rebuild_odd)
 {
 	const std::string dir(folder);
 	if (L < 1 || L > 256) { why = "reads of a length outside 1 .. 256"; return false; }
 	if (!slurp_file((dir + "/len.bin").c_str(), P.len)) { why = "cannot read len.bin"; return false; }
 	if (P.len.size() >= ((uint64_t)1 << 32)) { why = "len.bin holds 2^32 records or more"; return false; }
-	if (!slurp_file((dir + "/odd.seq").c_str(), P.odd_seq)) { why = "len.bin without odd.seq"; return false; }
+	// `minicom -V -A`: odd.aln codes some of the odd reads against the contigs and odd.seq holds the others; the full
+	// odd text is rebuilt here, before anything else looks at it
+	const bool aligned = mcom_odd_align_present(folder);
+	if (aligned && !rebuild_odd) { P.odd_seq.clear(); (void)slurp_file((dir + "/odd.seq").c_str(), P.odd_seq); }
+	else if (aligned) { if (!mcom_odd_align_rebuild(folder, L, P, why)) return false; }
+	else if (!slurp_file((dir + "/odd.seq").c_str(), P.odd_seq)) { why = "len.bin without odd.seq"; return false; }
 	const bool have_qual = slurp_file((dir + "/odd.qual").c_str(), P.odd_qual);
 	if (have_qual != want_qual) { why = want_qual ? "qual.mcq without odd.qual" : "odd.qual without qual.mcq"; return false; }
 	uint64_t odd_bytes = 0;
 	P.n = P.len.size();
 	host_index(P.len, L, P.slot, P.n_even, odd_bytes);
 	if (P.n_even != n_even) { why = "len.bin counts another number of reads of the modal length than the archive holds"; return false; }
+	if (aligned && !rebuild_odd) return true;                               // (the caller sets the sizes against the text it rebuilds)
 	if (odd_bytes != P.odd_seq.size()) { why = "the lengths of len.bin do not add up to the size of odd.seq"; return false; }
 	if (want_qual && odd_bytes != P.odd_qual.size()) { why = "the lengths of len.bin do not add up to the size of odd.qual"; return false; }
 	return true;

@@ -21,8 +21,13 @@ int mcom_ragged_split_to_device(const char *path, int device, int which, int L, 
                                 size_t err_cap);
 // is it a ragged archive at all (does folder/len.bin exist)?
 bool mcom_ragged_present(const char *folder);
-// false with `why` set: the parts disagree
-bool mcom_ragged_load(const char *folder, int L, uint64_t n_even, bool want_qual, McomRaggedParts &P, std::string &why);
+// false with `why` set: the parts disagree.  rebuild_odd false (the GPU decoder, for a folder with odd.aln): P.odd_seq is the residual as the folder
+// holds it -- empty when odd.seq is missing -- and its size is not set against the lengths: the caller rebuilds the text and does that
+bool mcom_ragged_load(const char *folder, int L, uint64_t n_even, bool want_qual, McomRaggedParts &P, std::string &why, bool rebuild_odd = true);
+// `minicom -V -A` (host/mcom_odd_align.cpp): does folder/odd.aln exist?  ... and the full odd text into P.odd_seq
+// from odd.aln, the contigs of the folder's ref.bin.* and the residual odd.seq (P.len is loaded); false with `why` set: refused
+bool mcom_odd_align_present(const char *folder);
+bool mcom_odd_align_rebuild(const char *folder, int L, McomRaggedParts &P, std::string &why);
 
 #ifndef MCOM_ENTROPY_HOST_ONLY
 #include "../../include/mcom.h"

@@ -192,6 +192,15 @@ def load_host_library():
         getattr(L, f).restype = i32; getattr(L, f).argtypes = [cp, cp, u64, u64, C.POINTER(u64), i32]
     L.mcomh_decompress_order_pe_range.restype = i32; L.mcomh_decompress_order_pe_range.argtypes = [cp, cp, cp, u64, u64, C.POINTER(u64), i32, i32]
     L.mcomh_qual_decode_rows.restype = i32; L.mcomh_qual_decode_rows.argtypes = [vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u32)]
+    L.mcomh_odd_text_append.restype = None; L.mcomh_odd_text_append.argtypes = [vp, u64, vp, u64, u64]
+    L.mcomh_odd_index_build.restype = i32; L.mcomh_odd_index_build.argtypes = [vp, u64, C.POINTER(vp)]
+    L.mcomh_odd_index_free.restype = None; L.mcomh_odd_index_free.argtypes = [vp]
+    L.mcomh_odd_index_size.restype = u64; L.mcomh_odd_index_size.argtypes = [vp]
+    L.mcomh_odd_align.restype = i32; L.mcomh_odd_align.argtypes = [vp, vp, u64, vp, vp, u64, vp]
+    L.mcomh_odd_align_encode.restype = i32; L.mcomh_odd_align_encode.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
+    L.mcomh_odd_align_decode.restype = i32; L.mcomh_odd_align_decode.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u32)]
+    L.mcomh_odd_align_refusal.restype = C.c_char_p; L.mcomh_odd_align_refusal.argtypes = [u32]
+    L.mcomh_odd_align_folder.restype = i32; L.mcomh_odd_align_folder.argtypes = [cp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.c_char_p, sz]
     _lib = L
     return L
 
@@ -243,6 +252,9 @@ HOST_ABI_SYMBOLS = ["mcomh_create", "mcomh_create_streamed", "mcomh_create_packe
                     "mcomh_fastq_record_hashes", "mcomh_digest_reduce", "mcomh_fastq_digest_files", "mcomh_digest_print", "mcomh_digest_parse", "mcomh_digest_check",
                     # a record range of a -p archive (`minicom -d -R`)
                     "mcomh_decompress_order_range", "mcomh_decompress_fastq_range", "mcomh_decompress_order_pe_range", "mcomh_qual_decode_rows",
+                    # the odd reads of a -V archive against the contigs (`minicom -p -V -A`, host/mcom_odd_align.cpp)
+                    "mcomh_odd_text_append", "mcomh_odd_index_build", "mcomh_odd_index_free", "mcomh_odd_index_size", "mcomh_odd_align", "mcomh_odd_align_encode",
+                    "mcomh_odd_align_decode", "mcomh_odd_align_refusal", "mcomh_odd_align_folder",
                     # multi-GPU (bound in minicom_amd/distributed.py)
                     "mcomh_comm_unique_id", "mcomh_comm_create_rccl", "mcomh_comm_create_ops", "mcomh_comm_destroy", "mcomh_comm_rank",
                     "mcomh_comm_world", "mcomh_comm_last_error", "mcomh_comm_alltoallv", "mcomh_comm_allgatherv", "mcomh_comm_allreduce_u64",
@@ -1441,3 +1453,79 @@ class Pipeline:
             ptr = self.lib.mcomh_contig_ref(self._h, i, C.byref(ln))
             out.append((C.string_at(ptr, ln.value), mem))
         return out
+
+
+# ---- the odd reads of a -V archive against the contigs (`minicom -p -V -A`, host/mcom_odd_align.cpp) ----
+def odd_align_folder(folder: str, device: int | None = None):
+    """mcomh_odd_align_folder over the UNGROUPED stream files of `folder` (ref.bin.*, beg_pos.bin.*, info.txt, len.bin, odd.seq): odd.aln is
+    written and odd.seq rewritten to the reads that were not found in the contigs.  device=None: the plain C++ twins; an integer: the
+    kernels of csrc/odd_align.hip on that GPU -- the same bytes.  Returns (n_odd, n_aligned, residual_bytes); nothing is written when no
+    read is aligned."""
+    n, a, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    err = C.create_string_buffer(256)
+    if load_host_library().mcomh_odd_align_folder(os.fsencode(folder), -1 if device is None else int(device), C.byref(n), C.byref(a), C.byref(r), err, 256):
+        raise McomError(f"{folder}: odd reads not aligned: {err.value.decode(errors='replace')}")
+    return int(n.value), int(a.value), int(r.value)
+
+
+def _np_ptr(a):
+    return C.c_void_p(a.ctypes.data) if a.size else C.c_void_p(0)
+
+
+def odd_text_host(refs):
+    """mcomh_odd_text_append over refs, a list of (ref.bin image as bytes, bases taken): (T as uint64 words, the last one zero; |T|)."""
+    L = load_host_library()
+    total = sum(int(b) for _, b in refs)
+    t = np.zeros((total + 31) // 32 + 1, dtype=np.uint64)
+    at = 0
+    for img, bases in refs:
+        a = np.frombuffer(bytes(img), dtype=np.uint8)
+        L.mcomh_odd_text_append(_np_ptr(t), at, _np_ptr(a), a.size, int(bases))
+        at += int(bases)
+    return t, total
+
+
+def odd_align_host(t, t_bases: int, odd: bytes, off):
+    """mcomh_odd_index_build + mcomh_odd_align: the hit words (uint64 [n_odd]) of the records odd[off[j]:off[j + 1]]."""
+    L = load_host_library()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    text = np.frombuffer(bytes(odd), dtype=np.uint8)
+    hits = np.zeros(max(off.size - 1, 1), dtype=np.uint64)
+    idx = C.c_void_p()
+    if L.mcomh_odd_index_build(_np_ptr(t), int(t_bases), C.byref(idx)):
+        raise McomError("odd_align: no seed index (a text of 2^40 bases or more?)")
+    try:
+        if L.mcomh_odd_align(idx, _np_ptr(t), int(t_bases), _np_ptr(text), _np_ptr(off), off.size - 1, _np_ptr(hits)):
+            raise McomError("odd_align: record offsets that do not ascend by 0 .. 256")
+    finally:
+        L.mcomh_odd_index_free(idx)
+    return hits[:off.size - 1]
+
+
+def odd_align_encode_host(hits, t, t_bases: int, odd: bytes, off):
+    """mcomh_odd_align_encode: (member bytes -- empty when no record is aligned --, residual bytes), in buffers of exact size."""
+    L = load_host_library()
+    off = np.ascontiguousarray(off, dtype=np.uint64); hits = np.ascontiguousarray(hits, dtype=np.uint64)
+    text = np.frombuffer(bytes(odd), dtype=np.uint8)
+    ml, rl = C.c_uint64(), C.c_uint64()
+    args = (_np_ptr(hits), _np_ptr(text), _np_ptr(off), off.size - 1, _np_ptr(t), int(t_bases))
+    if L.mcomh_odd_align_encode(*args, None, 0, C.byref(ml), None, 0, C.byref(rl)):
+        raise McomError("odd_align_encode: a hit word that its read and the text do not bear out, or a text outside ACGTN")
+    mem = np.zeros(int(ml.value), dtype=np.uint8); res = np.zeros(int(rl.value), dtype=np.uint8)
+    if L.mcomh_odd_align_encode(*args, _np_ptr(mem), mem.size, C.byref(ml), _np_ptr(res), res.size, C.byref(rl)):
+        raise McomError("odd_align_encode failed")
+    return mem.tobytes(), res.tobytes()
+
+
+def odd_align_decode_host(member: bytes, t, t_bases: int, residual: bytes, off):
+    """mcomh_odd_align_decode of an untrusted member: (the full odd text or None, flags, the refusal's words or None)."""
+    L = load_host_library()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    mem = np.frombuffer(bytes(member), dtype=np.uint8); res = np.frombuffer(bytes(residual), dtype=np.uint8)
+    out = np.zeros(int(off[-1]), dtype=np.uint8)
+    flags = C.c_uint32()
+    if L.mcomh_odd_align_decode(_np_ptr(mem), mem.size, _np_ptr(t), int(t_bases), _np_ptr(res), res.size, _np_ptr(off), off.size - 1, _np_ptr(out), C.byref(flags)):
+        if not flags.value:                                  # the caller's own arguments, not the member
+            raise McomError("odd_align_decode: a null pointer, or record offsets that do not ascend by 0 .. 256")
+        return None, int(flags.value), L.mcomh_odd_align_refusal(flags.value).decode()
+    return out.tobytes(), 0, None
